@@ -40,15 +40,17 @@ inputs resident in HBM when the timed region starts.
     --workload gat-reddit: config 4's layer; with --gpus N (round 6) on a vertex-range partition of the reddit-shaped graph -- the
     one-rank step of the same layer is taken in the run and rank 0's rows are held to it (dist.bench_gat_layer).
     --workload epoch-sage-products | epoch-gcn-products | epoch-gat-reddit | epoch-gcn-cora [--hidden H]: one training EPOCH of the
-    model configs through the trainer CLI per step (bench_epoch).  The default N = 1 run appends configs 2-4 as budgeted legs
+    model configs through the trainer CLI per step (bench_epoch).  The N = 1 run with --full appends configs 2-4 as budgeted legs
     (`other_configs`, --other-configs-s) after the headline record is held.
 
 One JSON line on rank 0.  `roofline` prices the dominant kernel (spmm_gemm_kernel: the one-wave-per-row
 aggregation with the dense product riding on it) by ALGORITHMIC bytes per launch / mean launch time measured
-with HIP events in the timed region, next to the stream-copy rate measured in the same run; `cpu_baseline` times
+with HIP events in the timed region.  A plain N = 1 run stops there: set-up, warm-up, the timed steps, the record.
+With --full it adds the stream-copy rate measured in the same run (roofline.peak_measured); `cpu_baseline` times
 the oracle's restatement of the OpenMP path on the host on the SAME graph and inputs, and `parity` compares the
 GPU layer's forward output, input gradient and weight gradient with that run element by element (exit code 3
-above 1e-4); `sustained_ms_per_step` is the same step kept up for >= 5 s after the timed region.
+above 1e-4); `sustained_ms_per_step` is the same step kept up for >= 5 s after the timed region; then the
+planted-locality leg and the other_configs block.  --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -152,6 +154,24 @@ def host_inputs(nv: int):
     x = rng.standard_normal((nv, D), dtype=np.float32)
     gin = rng.standard_normal((nv, D), dtype=np.float32)
     return x, gin
+
+
+DUMP_ROWS = 32768  # rows of each N x D output written by --dump-outputs: 2 x 16 MiB at D = 128
+
+
+def dump_outputs(out_dir: Path, torch, L, layer, feat_out, grad_out) -> None:
+    """--dump-outputs: what the caller of the timed step receives, as float32 .npy -- the layer output and the input gradient
+    at a fixed sample of rows (seed 0, ascending), and the whole weight gradient"""
+    import numpy as np
+
+    nv, din, dout = layer.nv, layer.din, layer.dout
+    rows = np.arange(nv) if nv <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(nv, DUMP_ROWS, replace=False))
+    rows_d = torch.from_numpy(rows).cuda()
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"feat_out": feat_out[rows_d], "grad_out": grad_out[rows_d], "w_grad": layer.tensor(L.W_NEIGH_GRAD, (din, dout))}
+    for name, t in arrays.items():
+        np.save(out_dir / f"{name}.npy", t.float().cpu().numpy())
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(arrays)} ({len(rows)} of {nv} rows)")
 
 
 def cpu_baseline(sg_rowptr, sg_colidx, nv, x, gin, budget_s=30.0, want_outputs=True):
@@ -842,7 +862,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the element-wise comparison with the oracle's run")
     ap.add_argument("--sustain-s", type=float, default=5.0,
-                    help="after the timed steps, run the same step for this many seconds (0 = skip)")
+                    help="after the timed steps, run the same step for this many seconds (0 = skip; N = 1 GCN record: with --full)")
     ap.add_argument("--cut-fraction", type=float, default=None,
                     help="N>1, weak scaling: fraction of each partition's edges that cross partitions (default: 0.1 as "
                          "`value` and (N-1)/N as config.random_order, both in one run)")
@@ -858,7 +878,7 @@ def main():
                     help="epoch-* workloads: the hidden width (default the workload's own; epoch-sage-products: 256 as "
                          "scripts/run-sage-products.sh passes it, `--hidden 128` = BASELINE config 3's literal \"3-layer D=128\")")
     ap.add_argument("--other-configs-s", type=float, default=float(os.environ.get("GAIB_BENCH_OTHER_CONFIGS_S", "100")),
-                    help="N = 1 default run: wall-clock budget of the `other_configs` block -- BASELINE configs 2-4 as short legs "
+                    help="N = 1 run with --full: wall-clock budget of the `other_configs` block -- BASELINE configs 2-4 as short legs "
                          "after the headline record is held (SAGE layer steps at 128 / 256, the 8-head GAT layer, the epoch "
                          "workloads); 0 = skip")
     ap.add_argument("--no-locality", action="store_true",
@@ -883,7 +903,18 @@ def main():
                          "\"edges/sec at 1/2/4/8\" on ogbn-products: total work fixed); weak = one products-shaped vertex range per "
                          "GPU at --cut-fraction.  A default run measures BOTH: the other one is config.weak_products_range / "
                          "config.strong_products.  gcn-papers (config 5) is weak by construction")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1 GCN record: also run the legs beside the headline -- the sustained leg, the in-run stream-copy "
+                         "probe (roofline.peak_measured), the planted-locality leg, the CPU baseline with the element-wise "
+                         "comparison against the oracle, and the other_configs block.  Without it the N = 1 run sets up, warms "
+                         "up, times --steps steps and prints the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1 GCN record: after the timed steps write what the last timed step computed as float32 .npy files "
+                         "under DIR -- feat_out / grad_out (the layer output and the input gradient at 32768 rows drawn with "
+                         "seed 0, ascending; every row if the graph has fewer) and w_grad (the whole D x D weight gradient)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.workload != "gcn-products"):
+        ap.error("--dump-outputs is written by the N = 1 gcn-products record")
     if args.workload in EPOCH_WORKLOADS and args.gpus > 1:
         ap.error(f"--workload {args.workload} is a one-GPU workload; N > 1 runs gcn-products, gcn-papers or gat-reddit")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -1060,7 +1091,8 @@ def main():
     log(f"[bench] products-shaped graph: nv={nv} ne={ne} (incl. self loops) max_deg={stats['max_degree']} "
         f"heavy rows={stats['n_heavy']} holding {stats['heavy_edges']} edges; gen+upload {time.time()-t0:.1f}s")
     lg = L.LGraph.adopt(g1)
-    want_parity = not (args.no_cpu_baseline or args.no_parity)
+    want_parity = args.full and not (args.no_cpu_baseline or args.no_parity)
+    guard.want_parity = want_parity
     layer = L.Layer(L.GCN, 1, nv, D, D, lg, act=True, lr=0.01)
     if want_parity:
         x_h, gin_h = host_inputs(nv)  # one set of inputs for both legs (element-wise parity below)
@@ -1097,11 +1129,13 @@ def main():
     n_fused, ms_fused = ctx.prof_get("spmm_gemm_fused")
     ctx.prof_reset()
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:  # before anything else runs the step again
+        dump_outputs(Path(args.dump_outputs), torch, L, layer, feat_out, grad_out)
 
     # sustained leg (not the reported value): the same step for >= --sustain-s seconds, to show the timed figure
     # survives seconds of load (clocks / power); the clocks are sampled mid-run by a child process
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         n_sus = max(int(args.sustain_s * 1e3 / ms_per_step) + 1, args.steps)
         clocks = {}
         th = threading.Thread(target=_sample_clocks, args=(clocks, min(2.0, args.sustain_s / 2)), daemon=True)
@@ -1117,7 +1151,7 @@ def main():
                      "vs_timed": (t_sus / n_sus * 1e3) / ms_per_step, "clocks_mid_run": clocks or None}
 
     # the chip's achievable streaming rate, measured in this run: 1 GiB float4 copy, read + written bytes
-    peak_measured = ctx.probe_stream_copy(1 << 30, 20) if args.scale >= 0.05 else None
+    peak_measured = ctx.probe_stream_copy(1 << 30, 20) if args.full and args.scale >= 0.05 else None
 
     edges_per_step = 2 * ne
     value = edges_per_step * args.steps / elapsed
@@ -1208,14 +1242,14 @@ def main():
     guard1.hold(result)
     rc = 0
     try:
-        if args.scale == 1.0 and not args.no_locality and os.environ.get("GAIB_BENCH_LOCALITY", "1") != "0":
+        if args.full and args.scale == 1.0 and not args.no_locality and os.environ.get("GAIB_BENCH_LOCALITY", "1") != "0":
             try:
                 result["roofline"]["planted_locality"] = locality_leg(torch, ctx, capi, synth)
             except Exception as e:  # noqa: BLE001 -- a side measurement must not cost the headline record
                 result["roofline"]["planted_locality"] = {"error": f"{type(e).__name__}: {e}"[:200]}
         if os.environ.get("GAIB_BENCH_FAIL_AFTER_HEADLINE") == "0":  # test hook (tests/test_gpu_dist.py)
             raise RuntimeError("GAIB_BENCH_FAIL_AFTER_HEADLINE: injected failure after the GPU measurement")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             t1 = time.time()
             xs = (x_h, gin_h) if want_parity else host_inputs(nv)
             result["cpu_baseline"], want = cpu_baseline(sg.rowptr, sg.colidx, nv, *xs, want_outputs=want_parity)
@@ -1229,9 +1263,9 @@ def main():
                 if not result["parity"]["ok"]:
                     log("[bench] PARITY FAILED (> 1e-4)")
                     rc = 3
-        # ---- BASELINE configs 2-4 in front of whoever runs the default command: after everything the headline
+        # ---- BASELINE configs 2-4 in the --full run: after everything the headline
         # record needs -- its value, roofline, CPU baseline and parity are complete and held; this block only adds a slot
-        if args.other_configs_s > 0 and os.environ.get("GAIB_BENCH_OTHER_CONFIGS", "1") != "0":
+        if args.full and args.other_configs_s > 0 and os.environ.get("GAIB_BENCH_OTHER_CONFIGS", "1") != "0":
             layer.close()
             lg.close()
             del feat_out, grad_out
@@ -1507,9 +1541,9 @@ def bench_gat_reddit(args, torch, ctx, L, synth, guard) -> int:
     return rc
 
 
-# ---- the other BASELINE configs inside the default N = 1 run ------------------------------------------------
+# ---- the other BASELINE configs inside the N = 1 run with --full --------------------------------------------
 class _Capture:
-    """stands in for the RecordGuard where a leg's record goes into a slot of the default run's record instead of out"""
+    """stands in for the RecordGuard where a leg's record goes into a slot of the --full run's record instead of out"""
     held = None
 
     def hold(self, r):
@@ -1754,7 +1788,7 @@ def epoch_record(args, torch, synth, hold=None, wname=None, hidden=None, data_ro
     first 5 train_loss / train_acc of the trainer on that dataset against it (GAIB_EPOCH_LOSSES: 9 digits, held to 1e-4 relative).
     wname / hidden: the workload (default args.workload) and its hidden width (default the workload's: `--hidden 128` is BASELINE
     config 3's literal "3-layer D=128", 256 what scripts/run-sage-products.sh passes).  data_root + keep_data: a directory that
-    already holds (or will keep) the full-size dataset -- the default run's other_configs block writes the products dataset once
+    already holds (or will keep) the full-size dataset -- the --full run's other_configs block writes the products dataset once
     for its three epoch records."""
     import shutil
     import tempfile

@@ -116,7 +116,7 @@ def build_oracle(force: bool = False, ref: bool = True) -> Path:
     if force:
         _run(["make", "-C", ORACLE, "clean"])
     _run(["make", "-C", ORACLE, "all"])
-    if ref and REFERENCE.exists():
+    if ref and os.path.isdir(REFERENCE):  # (False where it is absent or unreadable)
         _run(["make", "-C", ORACLE, "ref"])
     fake = ROOT / "tests" / "fake_rccl"  # the strict RCCL double of tests/test_gpu_comm.py (test infrastructure too)
     if fake.exists():

@@ -7,7 +7,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/evidence_$ROUND
 mkdir -p $OUT
 cd $ROOT
-echo "== bench.py (N=1)"; python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err; tail -c 600 $OUT/bench_n1.json; echo
+echo "== bench.py (N=1)"; python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err; tail -c 600 $OUT/bench_n1.json; echo
 echo "== bench.py --workload gat-reddit"; python bench.py --workload gat-reddit > $OUT/bench_gat_reddit.json 2> $OUT/bench_gat.err; tail -c 400 $OUT/bench_gat_reddit.json; echo
 echo "== profile_round"; bash scripts/profile_round.sh $ROUND all > $OUT/profile_round.log 2>&1; cp gpurun_out/prof_$ROUND/*.csv gpurun_out/prof_$ROUND/*.json gpurun_out/prof_$ROUND/*.txt $OUT/ 2>/dev/null; ls $OUT
 echo "== layers"; python scripts/microbench_layers.py > $OUT/microbench_layers.jsonl 2> $OUT/microbench_layers.err; python - <<'P' > $OUT/microbench_layers_ms_per_step.txt

@@ -15,5 +15,5 @@ cd "$ROOT"
 python3 scripts/summarize_rocprof.py stats "$OUT/stats" "$OUT/bench_kernel_stats.csv"
 python3 scripts/summarize_rocprof.py pmc "$OUT/bench_pmc_summary.json" fetch="$OUT/fetch" write="$OUT/write" mfma="$OUT/mfma"
 grep -h '"metric"' "$OUT/stats.log" | tail -1 > "$OUT/bench_under_rocprof.json"
-python3 bench.py --steps 10 --warmup 3 > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+python3 bench.py --steps 10 --warmup 3 --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 tail -c 600 "$OUT/bench_n1.json"

@@ -4,7 +4,7 @@
 #   the N = 2 / 4 rehearsals on one device, gat-reddit across 2 ranks
 O=gpurun_out/evidence_r06
 bash scripts/gpu_chain.sh $O \
- "bench_n1|300|python bench.py" \
+ "bench_n1|300|python bench.py --full" \
  "bench_gat_reddit|200|python bench.py --workload gat-reddit" \
  "epoch_sage256|200|python bench.py --workload epoch-sage-products" \
  "epoch_sage128|200|python bench.py --workload epoch-sage-products --hidden 128" \

@@ -471,8 +471,8 @@ def test_bench_n1_keeps_its_record_when_a_later_leg_fails():
     import json
     import subprocess
 
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.02", "--steps", "2", "--warmup", "1", "--sustain-s", "0"],
-                       capture_output=True, text=True, timeout=600, env=dict(_clean_env(), GAIB_BENCH_FAIL_AFTER_HEADLINE="0"))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.02", "--steps", "2", "--warmup", "1", "--sustain-s", "0",
+                        "--full"], capture_output=True, text=True, timeout=600, env=dict(_clean_env(), GAIB_BENCH_FAIL_AFTER_HEADLINE="0"))
     assert r.returncode == 0, r.stderr[-4000:]
     out = r.stdout.strip().splitlines()
     assert len(out) == 1
@@ -483,14 +483,14 @@ def test_bench_n1_keeps_its_record_when_a_later_leg_fails():
 
 
 def test_bench_n1_record_at_small_scale():
-    """`python bench.py --scale 0.05`: the N = 1 record with every block the contract names, element-wise parity, and -- round 5 --
+    """`python bench.py --scale 0.05 --full`: the N = 1 record with every block the contract names, element-wise parity, and -- round 5 --
     the outputs whose relu mask differs from the oracle's checked against an fp64 evaluation (inside the fp32 rounding bound of
     their sums: both signs are correct roundings)"""
     import json
     import subprocess
 
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.05", "--steps", "3", "--warmup", "1", "--sustain-s", "0"],
-                       capture_output=True, text=True, timeout=600, env=_clean_env())
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.05", "--steps", "3", "--warmup", "1", "--sustain-s", "0",
+                        "--full"], capture_output=True, text=True, timeout=600, env=_clean_env())
     assert r.returncode == 0, r.stderr[-3000:]
     out = r.stdout.strip().splitlines()
     assert len(out) == 1
@@ -514,6 +514,32 @@ def test_bench_n1_record_at_small_scale():
         assert e["value"] > 0 and e["ms_per_epoch"] > 0 and e["hidden"] == hid and e["steps"] == 10 and e["roofline"]["frac"] > 0, (k, e)
         assert len(e["train_loss_timed_epochs"]) == 10 and e["train_loss_timed_epochs"][-1] < e["train_loss_timed_epochs"][0]
     assert oc["epoch_gcn_cora"]["recorded_epochs"] is True and oc["elapsed_s"] < oc["budget_s"] + 60
+
+
+def test_bench_n1_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline record of K timed steps and nothing
+    beside it, and the last timed step's outputs as float32 .npy (a seeded row sample of the N x D outputs, the whole W_grad)"""
+    import json
+    import subprocess
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.02", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=_clean_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = r.stdout.strip().splitlines()
+    assert len(out) == 1
+    res = json.loads(out[0])
+    assert res["metric"] == "GCN-layer fwd+bwd aggregated edges/sec" and res["unit"] == "edges/s" and res["dtype"] == "f32"
+    assert res["higher_is_better"] is True and res["steps"] == 4 and res["value"] > 0 and res["ms_per_step"] > 0
+    for k in ("cpu_baseline", "parity", "other_configs", "sustained", "partial"):
+        assert k not in res, k
+    assert res["roofline"]["peak_measured"] is None and "planted_locality" not in res["roofline"]
+    nv = res["config"]["nv"]
+    dumped = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(dumped) == {"feat_out", "grad_out", "w_grad"}
+    assert dumped["feat_out"].shape == dumped["grad_out"].shape == (min(nv, 32768), 128) and dumped["w_grad"].shape == (128, 128)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    assert (dumped["feat_out"] >= 0).all() and dumped["feat_out"].any() and dumped["w_grad"].any()  # (relu output)
 
 
 def test_bench_budget_skips_sub_cases_and_keeps_the_headline():

@@ -30,13 +30,13 @@ def documented_objects():
 def test_documented_object_list_is_exact():
     srcs = documented_objects()
     assert "train.cpp" in srcs and "net.cpp" in srcs
-    if REF.exists():
+    if os.path.isdir(REF):
         assert all((REF / "src" / "gnn" / s).exists() for s in srcs), srcs
 
 
 @pytest.mark.parametrize("flag,name", [("", "gcn"), ("-DUSE_SAGE", "sage"), ("-DUSE_GAT", "gat")])
 def test_reference_driver_compiles_and_links_unchanged(tmp_path, flag, name):
-    if not REF.exists():
+    if not os.path.isdir(REF):  # (absent, or unreadable to this user)
         pytest.skip("no /root/reference on this machine")
     assert (LIB / "libgaib_gnn.so").exists() and (LIB / "libgaib_hip.so").exists(), "run graphaibench_amd.build"
     hdr = tmp_path / "driver_hdr"
