@@ -52,6 +52,8 @@ SIGNATURES = {
     "gaib_memcpy_d2d": (_i, [_vp, _vp, _vp, C.c_size_t]),
     "gaib_fill_f32": (_i, [_vp, _i64, _f, _vp]),
     "gaib_scale_f32": (_i, [_vp, _i64, _f, _vp]),
+    "gaib_cast_f32_bf16": (_i, [_vp, _i64, _vp, _vp]),
+    "gaib_cast_bf16_f32": (_i, [_vp, _i64, _vp, _vp]),
     "gaib_graph_create": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_create_rect": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_destroy": (_i, [_vp]),
@@ -73,6 +75,7 @@ SIGNATURES = {
     "gaib_spmm_gemm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "gaib_spmm_gemm2": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_mh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i]),
+    "gaib_spmm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "gaib_graph_split_classes": (_i, [_vp, _vp, _vp, _pp, _pp, _pp, _pp, C.POINTER(_i64), C.POINTER(_i64), _i]),
     "gaib_graph_split_pieces": (_i, [_vp, _vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _pp]),
     "gaib_graph_set_row_map": (_i, [_vp, _vp, _vp, _i64]),
@@ -474,6 +477,39 @@ class Context:
         flags = (1 if accumulate else 0) | (2 if relu else 0)
         _check(self.lib.gaib_spmm_mh(self.h, g.h, kind, _ptr(edge_w), heads, x.shape[1], _ptr(x), _ptr(out), flags),
                "gaib_spmm")
+        return out
+
+    # ---- bf16 feature tables (torch.bfloat16 tensors hold the raw bits) -------------------
+    def cast_f32_bf16(self, x, out=None):
+        """f32 -> bf16, round to nearest even (torch's .to(torch.bfloat16) on every non-NaN value)"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.float32
+        if out is None:
+            out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == x.numel()
+        _check(self.lib.gaib_cast_f32_bf16(self.h, x.numel(), _ptr(x), _ptr(out)), "gaib_cast_f32_bf16")
+        return out
+
+    def cast_bf16_f32(self, x, out=None):
+        """bf16 -> f32 (exact)"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.bfloat16
+        if out is None:
+            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == x.numel()
+        _check(self.lib.gaib_cast_bf16_f32(self.h, x.numel(), _ptr(x), _ptr(out)), "gaib_cast_bf16_f32")
+        return out
+
+    def spmm_bf16(self, g: "Graph", kind: int, x, out, edge_w=None, accumulate: bool = False, relu: bool = False):
+        """gaib_spmm_bf16: x a [nc x len] torch.bfloat16 table, out fp32 [nv x len]"""
+        import torch
+
+        assert x.is_contiguous() and out.is_contiguous() and x.dim() == 2 and x.dtype == torch.bfloat16
+        flags = (1 if accumulate else 0) | (2 if relu else 0)
+        _check(self.lib.gaib_spmm_bf16(self.h, g.h, kind, _ptr(edge_w), x.shape[1], _ptr(x), _ptr(out), flags),
+               "gaib_spmm_bf16")
         return out
 
     def spmm_gemm(self, g: "Graph", kind: int, x, agg, W, out, transW: bool = False, relu: bool = False,

@@ -85,6 +85,8 @@ struct gaib_ctx {
   int spmm_addr_mode;        // 0 = auto (buffer loads when the table is < 4 GB), 2 = force 64-bit global
   int spmm_gather_mode;      // 0/1 default cache policy, 2 = nt gathers, 3 = nt for cold columns only
   int spmm_hot_bytes;        // L2 budget for the hot rows of gather mode 3
+  int spmm_bf16_layout;      // gaib_spmm_bf16's lane layout: 0 = one row per wave (auto lane width), 4 / 8 = sub-wave rows of 4 / 8 elements per lane
+  int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16)
   int sgemm_variant;         // 0 = auto
   int gat_fast;              // reserved
   int gat_chunk_colsum;      // GAT backward column sums by ordered chunks: -1 = dense graphs, 0 never, 1 always
@@ -129,8 +131,10 @@ constexpr double GAIB_MFMA_F32_PEAK_FLOPS = 157.3e12;
 // algorithmic bytes of one aggregation launch over `edges` edges into `rows` rows of `cols` columns --
 // every gathered row counted (4 cols), the column id (4) and the per-edge weight where there is one, `stored` [rows x cols]
 // matrices written (or read back), the row pointers (8 B here: rowptr is int64)
-static inline double gaib_alg_spmm_bytes(double edges, double rows, double cols, double w_bytes_per_edge, double stored) {
-  return edges * (4.0 * cols + 4.0 + w_bytes_per_edge) + stored * rows * 4.0 * cols + (rows + 1.0) * 8.0;
+// (elem_bytes: bytes per gathered element -- 2 for a bf16 table, whose output rows are still fp32)
+static inline double gaib_alg_spmm_bytes(double edges, double rows, double cols, double w_bytes_per_edge, double stored,
+                                         double elem_bytes = 4.0) {
+  return edges * (elem_bytes * cols + 4.0 + w_bytes_per_edge) + stored * rows * 4.0 * cols + (rows + 1.0) * 8.0;
 }
 
 struct ProfScope {

@@ -488,6 +488,73 @@ __global__ void adam_advance_kernel(float* pw, float b1, float b2) {
   pw[1] *= b2;
 }
 
+// ---- bf16 feature tables: f32 <-> bf16 (raw bits in uint16_t) -----------------------------------------------------
+// f32 -> bf16 rounds to nearest, ties to even, on the bit pattern (what torch's CPU .to(torch.bfloat16) does): subnormals
+// are kept, finite values past the largest bf16 round up to +-inf, +-inf stay.  A NaN stays a NaN of the same sign: its
+// upper half with the quiet bit set (a NaN whose payload sits in the low half alone must not become inf).
+// bf16 -> f32 is exact: bits << 16.
+__device__ __forceinline__ unsigned f32_to_bf16_bits(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+// one thread per 8 elements: two 16-B loads, one 16-B store (vec: both pointers 16-B aligned); the n % 8 tail by the
+// thread of group n / 8
+__global__ __launch_bounds__(256) void cast_f32_bf16_kernel(int64_t n, const float* __restrict__ in, uint16_t* __restrict__ out,
+                                                            int vec) {
+  const int64_t n8 = vec ? n / 8 : 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n8; i += stride) {
+    if (i < n8) {
+      const f4 a = reinterpret_cast<const f4*>(in)[2 * i], b = reinterpret_cast<const f4*>(in)[2 * i + 1];
+      u4v o;
+      o[0] = f32_to_bf16_bits(a[0]) | (f32_to_bf16_bits(a[1]) << 16);
+      o[1] = f32_to_bf16_bits(a[2]) | (f32_to_bf16_bits(a[3]) << 16);
+      o[2] = f32_to_bf16_bits(b[0]) | (f32_to_bf16_bits(b[1]) << 16);
+      o[3] = f32_to_bf16_bits(b[2]) | (f32_to_bf16_bits(b[3]) << 16);
+      reinterpret_cast<u4v*>(out)[i] = o;
+    } else {
+      for (int64_t k = 8 * n8; k < n; ++k) out[k] = (uint16_t)f32_to_bf16_bits(in[k]);
+    }
+  }
+}
+// scalar form (unaligned pointers): one element per thread
+__global__ __launch_bounds__(256) void cast_f32_bf16_scalar_kernel(int64_t n, const float* __restrict__ in,
+                                                                   uint16_t* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint16_t)f32_to_bf16_bits(in[i]);
+}
+__global__ __launch_bounds__(256) void cast_bf16_f32_scalar_kernel(int64_t n, const uint16_t* __restrict__ in,
+                                                                   float* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = __uint_as_float((unsigned)in[i] << 16);
+}
+// one thread per 8 elements: one 16-B load, two 16-B stores (vec: both pointers 16-B aligned)
+__global__ __launch_bounds__(256) void cast_bf16_f32_kernel(int64_t n, const uint16_t* __restrict__ in, float* __restrict__ out,
+                                                            int vec) {
+  const int64_t n8 = vec ? n / 8 : 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n8; i += stride) {
+    if (i < n8) {
+      const u4v w = reinterpret_cast<const u4v*>(in)[i];
+      f4 a, b;
+      a[0] = __uint_as_float(w[0] << 16);
+      a[1] = __uint_as_float(w[0] & 0xffff0000u);
+      a[2] = __uint_as_float(w[1] << 16);
+      a[3] = __uint_as_float(w[1] & 0xffff0000u);
+      b[0] = __uint_as_float(w[2] << 16);
+      b[1] = __uint_as_float(w[2] & 0xffff0000u);
+      b[2] = __uint_as_float(w[3] << 16);
+      b[3] = __uint_as_float(w[3] & 0xffff0000u);
+      reinterpret_cast<f4*>(out)[2 * i] = a;
+      reinterpret_cast<f4*>(out)[2 * i + 1] = b;
+    } else {
+      for (int64_t k = 8 * n8; k < n; ++k) out[k] = __uint_as_float((unsigned)in[k] << 16);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int gaib_fill_f32(gaib_ctx* ctx, int64_t n, float value, float* d_x) {
@@ -502,6 +569,32 @@ extern "C" int gaib_scale_f32(gaib_ctx* ctx, int64_t n, float alpha, float* d_x)
   GAIB_CHECK(ctx && (d_x || n == 0), "gaib_scale_f32: NULL argument");
   if (n <= 0) return GAIB_OK;
   scale_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, alpha, d_x);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_cast_f32_bf16(gaib_ctx* ctx, int64_t n, const float* d_in, uint16_t* d_out) {
+  GAIB_CHECK(ctx && ((d_in && d_out) || n == 0), "gaib_cast_f32_bf16: NULL argument");
+  GAIB_CHECK(n >= 0, "gaib_cast_f32_bf16: n < 0");
+  if (n == 0) return GAIB_OK;
+  GAIB_CHECK((const void*)d_in != (const void*)d_out, "gaib_cast_f32_bf16: in and out must not alias");
+  const int vec = ((((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0);
+  ProfScope ps(ctx, "cast_f32_bf16", 6.0 * (double)n);
+  if (vec) cast_f32_bf16_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, ctx->stream>>>(n, d_in, d_out, 1);
+  else cast_f32_bf16_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, d_in, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in, float* d_out) {
+  GAIB_CHECK(ctx && ((d_in && d_out) || n == 0), "gaib_cast_bf16_f32: NULL argument");
+  GAIB_CHECK(n >= 0, "gaib_cast_bf16_f32: n < 0");
+  if (n == 0) return GAIB_OK;
+  GAIB_CHECK((const void*)d_in != (const void*)d_out, "gaib_cast_bf16_f32: in and out must not alias");
+  const int vec = ((((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0);
+  ProfScope ps(ctx, "cast_bf16_f32", 6.0 * (double)n);
+  if (vec) cast_bf16_f32_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, ctx->stream>>>(n, d_in, d_out, 1);
+  else cast_bf16_f32_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, d_in, d_out);
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

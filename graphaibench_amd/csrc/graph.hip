@@ -321,11 +321,12 @@ int gaib_graph_ensure_inv_deg(gaib_ctx* ctx, gaib_graph* g) {
 int gaib_graph_ensure_w_gcn(gaib_ctx* ctx, gaib_graph* g) {
   if (g->w_gcn) return GAIB_OK;
   GAIB_NOT_WHILE_CAPTURING(ctx, "building the graph's GCN edge weights");
+  // (checked before the allocation: a refused call must not leave an unfilled weight array that a later call would take)
+  GAIB_CHECK(g->nc == g->nv || g->col_vdata,
+             "rectangular graph: call gaib_graph_set_vertex_norm before GAIB_W_GCN");
   if (!g->vdata) GAIB_TRY(gaib_graph_compute_vertex_data(ctx, g));
   GAIB_HIP(hipMalloc(&g->w_gcn, sizeof(float) * (size_t)(g->ne > 0 ? g->ne : 1)));
   g->dev_bytes += sizeof(float) * g->ne;
-  GAIB_CHECK(g->nc == g->nv || g->col_vdata,
-             "rectangular graph: call gaib_graph_set_vertex_norm before GAIB_W_GCN");
   edge_weight_kernel<1><<<grid1d(g->nv, 4), 256, 0, ctx->stream>>>(
       g->nv, g->rowptr, g->colidx, g->vdata, g->col_vdata ? g->col_vdata : g->vdata, g->w_gcn);
   GAIB_LAUNCH_CHECK();
@@ -335,11 +336,11 @@ int gaib_graph_ensure_w_gcn(gaib_ctx* ctx, gaib_graph* g) {
 int gaib_graph_ensure_w_mean_t(gaib_ctx* ctx, gaib_graph* g) {
   if (g->w_mean_t) return GAIB_OK;
   GAIB_NOT_WHILE_CAPTURING(ctx, "building the graph's transpose-mean edge weights");
+  GAIB_CHECK(g->nc == g->nv || g->col_inv_deg,
+             "rectangular graph: call gaib_graph_set_vertex_norm before GAIB_W_MEAN_T");
   GAIB_TRY(gaib_graph_ensure_inv_deg(ctx, g));
   GAIB_HIP(hipMalloc(&g->w_mean_t, sizeof(float) * (size_t)(g->ne > 0 ? g->ne : 1)));
   g->dev_bytes += sizeof(float) * g->ne;
-  GAIB_CHECK(g->nc == g->nv || g->col_inv_deg,
-             "rectangular graph: call gaib_graph_set_vertex_norm before GAIB_W_MEAN_T");
   gather_by_col_kernel<<<grid1d(g->ne, 256), 256, 0, ctx->stream>>>(
       g->ne, g->colidx, g->col_inv_deg ? g->col_inv_deg : g->inv_deg, g->w_mean_t);
   GAIB_LAUNCH_CHECK();

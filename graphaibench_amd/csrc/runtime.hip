@@ -64,6 +64,8 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_addr_mode = 0;
   c->spmm_gather_mode = 0;
   c->spmm_hot_bytes = 3 << 20;
+  c->spmm_bf16_layout = 0;
+  c->agg_bf16 = 0;
   c->sgemm_variant = 0;
   if (const char* e = getenv("GAIB_SGEMM_VARIANT")) c->sgemm_variant = atoi(e);  // (A/B of a whole trainer run: 61 = without sgemm_skinny.hip)
   c->gat_fast = 1;
@@ -520,6 +522,8 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_fuse_cus")) *h_value = ctx->spmm_fuse_cus;
   else if (!strcmp(key, "spmm_flat_ring")) *h_value = ctx->spmm_flat_ring;
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
+  else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
+  else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
   else {
     gaib_set_error("gaib_get_option: no readable option '%s'", key);
     return GAIB_ERR_INVALID;
@@ -559,6 +563,13 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
     ctx->spmm_gather_mode = (int)value;
   else if (!strcmp(key, "spmm_hot_bytes"))
     ctx->spmm_hot_bytes = (int)value;
+  else if (!strcmp(key, "spmm_bf16_layout")) {
+    GAIB_CHECK(value == 0 || value == 4 || value == 8, "spmm_bf16_layout must be 0, 4 or 8");
+    ctx->spmm_bf16_layout = (int)value;
+  } else if (!strcmp(key, "agg_bf16")) {
+    GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
+    ctx->agg_bf16 = (int)value;
+  }
   else if (!strcmp(key, "sgemm_variant"))
     ctx->sgemm_variant = (int)value;
   else if (!strcmp(key, "gat_fast"))

@@ -38,7 +38,8 @@ namespace {
 // HT > 0 (WMODE 3, heads == HT in {4, 8, 16}): the chunk's [64][HT] weight block is read once, one edge per lane
 // (HT/4 16-byte loads), parked in the wave's LDS slice with a row stride of HT + 1 floats and picked up per (edge, head)
 // from there: 2 + 2 wave instructions per chunk instead of one 4-byte global load per lane and edge.
-template <int G, int WMODE, int HT = 0>
+// E = uint16_t: the table holds bf16 bits (a lane's 4 elements are one 8-B load, widened exactly); sums as for fp32.
+template <int G, int WMODE, int HT = 0, typename E = float>
 __global__ __launch_bounds__(256) void spmm_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row,
                                                          const uint32_t* chunk_ebase, const uint32_t* chunk_start,
                                                          SpmmArgs a, float* partial) {
@@ -85,7 +86,10 @@ __global__ __launch_bounds__(256) void spmm_chunk_kernel(int64_t n_chunks, const
     for (int u = 0; u < U; ++u) {
       const int ei = gbase + j + u;  // edge of the chunk this group handles now
       const uint32_t cj = (uint32_t)__shfl((int)cl, ei, 64);
-      x[u] = *reinterpret_cast<const f32x4_t*>(a.in + (int64_t)cj * a.ld + coff);
+      if constexpr (sizeof(E) == 2)
+        x[u] = load_elems<4, E>(reinterpret_cast<const char*>(a.in) + ((int64_t)cj * a.ld + coff) * 2);
+      else
+        x[u] = *reinterpret_cast<const f32x4_t*>(a.in + (int64_t)cj * a.ld + coff);
       if constexpr (HT > 0) w[u] = wd[ei * WS + head];
       else if constexpr (MH) w[u] = ei < n ? load_edge_w<WMODE>(a, eb + ei, head) : 0.f;
       else w[u] = __shfl(wl, ei, 64);
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256) void spmm_chunk_reduce_kernel(SpmmArgs a, cons
   *reinterpret_cast<f32x4_t*>(o) = s;
 }
 
-template <int WMODE>
+template <int WMODE, typename E = float>
 int launch_chunked(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a) {
   GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
   GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (size_t)g->n_chunks * a.ncols + 256));
@@ -155,10 +159,11 @@ int launch_chunked(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a) {
   {
     // col + gathered row + the edge's weights; a partial row per chunk written (and read again by the reduction)
     const double wb = WMODE == 0 ? 0.0 : (WMODE >= 3 ? 4.0 * a.heads : 4.0);
-    ProfScope ps(ctx, "spmm_chunk", (double)g->ne * (4.0 * a.ncols + 4.0 + wb) + (double)g->n_chunks * 4.0 * a.ncols,
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_chunk" : "spmm_chunk",
+                 (double)g->ne * ((double)sizeof(E) * a.ncols + 4.0 + wb) + (double)g->n_chunks * 4.0 * a.ncols,
                  2.0 * (double)g->ne * a.ncols);
 #define GAIB_CHUNK(GG) \
-  spmm_chunk_kernel<GG, WMODE><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, a, partial)
+  spmm_chunk_kernel<GG, WMODE, 0, E><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, a, partial)
 #define GAIB_CHUNK_H(GG, HH) \
   spmm_chunk_kernel<GG, 3, HH><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, a, partial)
     const bool w16 = WMODE == 3 && (((uintptr_t)a.ew) & 15) == 0;
@@ -207,11 +212,28 @@ inline double lines_strided(int bytes, int stride) {
 
 }  // namespace
 
+// Rows whose byte length is not a multiple of 64 straddle more 128-B lines than they fill (a 188-B row of the
+// 47-class output layer touches 2.44 lines on average, 2 when rows start on 64-B boundaries), and the gather time
+// follows the lines touched: products, D = 47: 5.28 ms, D = 48: 4.04 ms.  Where re-striding saves more than 10 %
+// of the lines, the input table is copied once into rows of whole 64-B pieces (0.9 GB of streaming traffic against
+// 40 GB of gathers at products / 47) and gathered from there; output rows keep the caller's stride.
+// Returns the padded row stride in floats, 0 where the fp32 table is gathered as it is.
+static int64_t pad_stride_floats(const gaib_ctx* ctx, const gaib_graph* g, int len, bool part) {
+  const int bytes = len * 4, stride = (bytes + 63) & ~63;
+  // (not inside a side-stream section: the copy buffer belongs to the main stream's calls)
+  if (ctx->spmm_pad && !part && !ctx->forked && len > 16 && stride != bytes && g->ne > 4 * g->nc &&
+      lines_strided(bytes, stride) < 0.9 * lines_packed(bytes))
+    return stride / 4;
+  return 0;
+}
+
 // fills the launch arguments shared by every aggregation path; *wmode = kernel weight mode
 // d_in2 / n_first: column ids >= n_first index the second table d_in2 (row id - n_first) -- NULL: one table
+// bf16: d_in holds bf16 bits (gaib_spmm_bf16): gathered as it is (no re-strided copy, no cold-column flags), and the
+// buffer-descriptor path is chosen by the table's bf16 byte size
 static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                       const float* d_in, float* d_out, int flags, int heads, SpmmArgs* pa, int* wmode,
-                      const float* d_in2 = nullptr, int64_t n_first = 0) {
+                      const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false) {
   SpmmArgs& a = *pa;
   const bool part = g->row_map != nullptr || d_in2 != nullptr;  // a row class of a partition (spmm_part.hip)
   GAIB_CHECK(!d_in2 || (n_first >= 0 && n_first <= g->nc), "gaib_spmm: n_first (%lld) outside the %lld columns",
@@ -244,23 +266,17 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   a.in2 = d_in2;
   a.n_first = d_in2 ? (uint32_t)n_first : 0xffffffffu;
   a.in2_bytes = 0;
-  if (!part && ctx->spmm_gather_mode == 3 && g->nc == g->nv && !g->col_vdata) {
+  if (!part && !bf16 && ctx->spmm_gather_mode == 3 && g->nc == g->nv && !g->col_vdata) {
     GAIB_TRY(gaib_graph_ensure_hot_flags(ctx, g, len));
     a.col_flagged = g->colidx_flagged;
   }
   a.ldo = len;
-  // Rows whose byte length is not a multiple of 64 straddle more 128-B lines than they fill (a 188-B row of the
-  // 47-class output layer touches 2.44 lines on average, 2 when rows start on 64-B boundaries), and the gather time
-  // follows the lines touched: products, D = 47: 5.28 ms, D = 48: 4.04 ms.  Where re-striding saves more than 10 %
-  // of the lines, the input table is copied once into rows of whole 64-B pieces (0.9 GB of streaming traffic against
-  // 40 GB of gathers at products / 47) and gathered from there; output rows keep the caller's stride.
+  // odd-width tables: gathered from a copy re-strided to whole 64-B pieces where that saves lines (pad_stride_floats)
   {
-    const int bytes = len * 4, stride = (bytes + 63) & ~63;
-    // (not inside a side-stream section: the copy buffer belongs to the main stream's calls)
-    if (ctx->spmm_pad && !part && !ctx->forked && len > 16 && stride != bytes && g->ne > 4 * g->nc &&
-        lines_strided(bytes, stride) < 0.9 * lines_packed(bytes)) {
-      const int lp = stride / 4;
-      GAIB_TRY(gaib_pad_reserve(ctx, (size_t)g->nc * (size_t)stride));
+    const int64_t lp_pad = bf16 ? 0 : pad_stride_floats(ctx, g, len, part);
+    if (lp_pad > 0) {
+      const int lp = (int)lp_pad;
+      GAIB_TRY(gaib_pad_reserve(ctx, (size_t)g->nc * (size_t)lp * 4));
       const int64_t n4 = g->nc * (int64_t)(lp / 4);
       const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n4, 256), (int64_t)ctx->num_cus * 16);
       pad_rows_kernel<<<grid, 256, 0, ctx->stream>>>(n4, len, lp / 4, d_in, reinterpret_cast<f32x4_t*>(ctx->pad));
@@ -269,8 +285,8 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
       a.ld = lp;
     }
   }
-  // feature table = nc rows of a.ld floats; the 32-bit buffer path needs it below 4 GB
-  const int64_t table_bytes = (d_in2 ? n_first : g->nc) * a.ld * 4;
+  // feature table = nc rows of a.ld elements (4 B, or 2 B in bf16); the 32-bit buffer path needs it below 4 GB
+  const int64_t table_bytes = (d_in2 ? n_first : g->nc) * a.ld * (bf16 ? 2 : 4);
   a.in_bytes = table_bytes < ((int64_t)1 << 32) ? (uint32_t)table_bytes : 0u;
   if (d_in2) {
     const int64_t t2 = (g->nc - n_first) * a.ld * 4;
@@ -599,4 +615,110 @@ extern "C" int gaib_spmm_mh(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const
   GAIB_CHECK(heads == 1 || weight_kind == GAIB_W_EDGE || weight_kind == GAIB_W_EDGE_T,
              "gaib_spmm_mh: per-head weights need GAIB_W_EDGE or GAIB_W_EDGE_T");
   return spmm_impl(ctx, g, weight_kind, d_edge_w, len, d_in, d_out, flags, heads);
+}
+
+// ---- bf16 feature tables ------------------------------------------------------------------------------------------------
+// out[i,:] (+)= sum_e w_e * widen(in[col_e,:]) with in in bf16 (raw bits), out in fp32.  The kernels are the fp32 ones with
+// a bf16 gather (RowGather<.., E = uint16_t>): the same weights, the same CSR order with separate multiply and add, the same
+// row classes (heavy threshold, 16-wave split, LDS combine in wave order) and the same choice of the ordered-chunk form for
+// dense graphs -- so the result is bit-identical to gaib_spmm_ex on the table widened to fp32.  Only the lane layout
+// differs: a row needs half the bytes, so a lane takes twice the elements for the same load width.
+namespace {
+
+template <int WMODE>
+int dispatch_bf16(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a0, int len) {
+  typedef uint16_t bf16_t;
+  // widest vector the row length and base pointers allow: VEC elements = 2 VEC bytes per gather, 4 VEC bytes per store
+  const uintptr_t ai = (uintptr_t)a0.in, ao = (uintptr_t)a0.out;
+  int vmax = 1;
+  for (int v = 8; v > 1; v >>= 1)
+    if (len % v == 0 && (ai & (2 * v - 1)) == 0 && (ao & ((v >= 4 ? 16 : 4 * v) - 1)) == 0) {
+      vmax = v;
+      break;
+    }
+  // option spmm_bf16_layout (A/B of the lane layout; LEDGER): 0 = one row per wave, the narrowest lane that covers a row in
+  // one pass (128 columns: 4-B lanes); 4 / 8 = sub-wave rows of 4 / 8 elements per lane (128 columns: 2 / 4 rows per wave)
+  const int layout = ctx->spmm_bf16_layout;
+  if ((layout == 4 || layout == 8) && vmax >= layout && (len + layout - 1) / layout <= 32) {
+    const int lanes = (len + layout - 1) / layout;
+    if (layout == 8) {
+      if (lanes <= 1) return launch_sub<8, 1, WMODE, bf16_t>(ctx, g, a0);
+      if (lanes <= 2) return launch_sub<8, 2, WMODE, bf16_t>(ctx, g, a0);
+      if (lanes <= 4) return launch_sub<8, 4, WMODE, bf16_t>(ctx, g, a0);
+      if (lanes <= 8) return launch_sub<8, 8, WMODE, bf16_t>(ctx, g, a0);
+      if (lanes <= 16) return launch_sub<8, 16, WMODE, bf16_t>(ctx, g, a0);
+      return launch_sub<8, 32, WMODE, bf16_t>(ctx, g, a0);
+    }
+    if (lanes <= 1) return launch_sub<4, 1, WMODE, bf16_t>(ctx, g, a0);
+    if (lanes <= 2) return launch_sub<4, 2, WMODE, bf16_t>(ctx, g, a0);
+    if (lanes <= 4) return launch_sub<4, 4, WMODE, bf16_t>(ctx, g, a0);
+    if (lanes <= 8) return launch_sub<4, 8, WMODE, bf16_t>(ctx, g, a0);
+    if (lanes <= 16) return launch_sub<4, 16, WMODE, bf16_t>(ctx, g, a0);
+    return launch_sub<4, 32, WMODE, bf16_t>(ctx, g, a0);
+  }
+  int vec = vmax;
+  for (int v = 1; v < vmax; v <<= 1)
+    if ((len + v - 1) / v <= 64) {
+      vec = v;
+      break;
+    }
+  // one launch covers up to 256 lanes of <= 2 elements, 128 of 4 or 64 of 8 (as in fp32, 16 accumulators per lane next to
+  // the gathers spill); wider rows in column slabs, each walking the edge list again
+  const int slab = vec >= 4 ? 512 : 256 * vec;
+  for (int c0 = 0; c0 < len; c0 += slab) {
+    SpmmArgs a = a0;
+    a.in = reinterpret_cast<const float*>(reinterpret_cast<const bf16_t*>(a0.in) + c0);
+    a.out = a0.out + c0;
+    if (a.in_bytes) a.in_bytes -= (uint32_t)(2 * c0);
+    a.ncols = (len - c0 < slab) ? (len - c0) : slab;
+    const int lanes = (a.ncols + vec - 1) / vec;
+    const int ct = lanes <= 64 ? 1 : (lanes <= 128 ? 2 : 4);
+    int rc;
+    if (vec == 8) rc = launch_w64<8, 1, WMODE, bf16_t>(ctx, g, a);
+    else if (vec == 4) rc = ct == 1 ? launch_w64<4, 1, WMODE, bf16_t>(ctx, g, a) : launch_w64<4, 2, WMODE, bf16_t>(ctx, g, a);
+    else if (vec == 2) rc = ct == 1 ? launch_w64<2, 1, WMODE, bf16_t>(ctx, g, a)
+                                    : (ct == 2 ? launch_w64<2, 2, WMODE, bf16_t>(ctx, g, a) : launch_w64<2, 4, WMODE, bf16_t>(ctx, g, a));
+    else rc = ct == 1 ? launch_w64<1, 1, WMODE, bf16_t>(ctx, g, a)
+                      : (ct == 2 ? launch_w64<1, 2, WMODE, bf16_t>(ctx, g, a) : launch_w64<1, 4, WMODE, bf16_t>(ctx, g, a));
+    if (rc != GAIB_OK) return rc;
+  }
+  return GAIB_OK;
+}
+
+}  // namespace
+
+extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
+                              const uint16_t* d_in, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_bf16: NULL ctx/graph");
+  GAIB_CHECK(len >= 0, "gaib_spmm_bf16: len < 0");
+  GAIB_CHECK((flags & ~(GAIB_ACCUMULATE | GAIB_RELU)) == 0, "gaib_spmm_bf16: unsupported flags %d", flags);
+  GAIB_CHECK(ctx->device == g->device, "gaib_spmm_bf16: graph lives on device %d, ctx on %d", g->device, ctx->device);
+  if (g->row_map) {
+    gaib_set_error("gaib_spmm_bf16: a row class of a partition (graph with a row map) is not supported: fp32 tables only");
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (len == 0 || g->nv == 0) return GAIB_OK;
+  GAIB_CHECK(d_in && d_out, "gaib_spmm_bf16: NULL feature pointer");
+  GAIB_CHECK((const void*)d_in != (const void*)d_out, "gaib_spmm_bf16: in and out must not alias");
+  SpmmArgs a;
+  int wmode = 0;
+  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len, reinterpret_cast<const float*>(d_in), d_out, flags, 1, &a, &wmode,
+                      nullptr, 0, true));
+  // the fp32 path's choice of the ordered-chunk form, made on what IT would see (the row stride of its possibly re-strided
+  // table; 16-B aligned rows) -- the same graph and len take the same summation order
+  const int64_t ld32 = pad_stride_floats(ctx, g, len, false) > 0 ? pad_stride_floats(ctx, g, len, false) : len;
+  const bool chunk_shape = len % 4 == 0 && len <= 256 && g->ne > 0 && (((uintptr_t)d_in & 7) == 0) &&
+                           (((uintptr_t)d_out & 15) == 0);
+  if (chunk_shape && (ctx->spmm_chunked == 1 || (ctx->spmm_chunked < 0 && chunk_rule(ctx, g, ld32)))) {
+    switch (wmode) {
+      case 0: return launch_chunked<0, uint16_t>(ctx, g, a);
+      case 1: return launch_chunked<1, uint16_t>(ctx, g, a);
+      default: return launch_chunked<2, uint16_t>(ctx, g, a);
+    }
+  }
+  switch (wmode) {
+    case 0: return dispatch_bf16<0>(ctx, g, a, len);
+    case 1: return dispatch_bf16<1>(ctx, g, a, len);
+    default: return dispatch_bf16<2>(ctx, g, a, len);
+  }
 }

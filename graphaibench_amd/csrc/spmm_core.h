@@ -49,6 +49,7 @@ template <int VEC> struct VecT;
 template <> struct VecT<1> { typedef float type; };
 template <> struct VecT<2> { typedef float type __attribute__((ext_vector_type(2))); };
 template <> struct VecT<4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct VecT<8> { typedef float type __attribute__((ext_vector_type(8))); };  // (bf16 tables: one 16-B gather)
 
 template <int VEC>
 __device__ __forceinline__ typename VecT<VEC>::type vzero() {
@@ -114,6 +115,38 @@ __device__ __forceinline__ float load_edge_w(const SpmmArgs& a, int64_t e, int h
 typedef unsigned u2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u4_t __attribute__((ext_vector_type(4)));
 
+// bf16 tables (E = uint16_t: raw bf16 bits): VEC elements arrive in VEC / 2 dwords and are widened exactly (bits << 16);
+// everything after the gather -- weights, sums, order, the fp32 output -- is the fp32 kernels' own.
+__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+template <int VEC> struct Bf16Raw;  // the packed words of VEC bf16 elements
+template <> struct Bf16Raw<1> { typedef unsigned short type; };
+template <> struct Bf16Raw<2> { typedef unsigned type; };
+template <> struct Bf16Raw<4> { typedef u2_t type; };
+template <> struct Bf16Raw<8> { typedef u4_t type; };
+template <int VEC>
+__device__ __forceinline__ typename VecT<VEC>::type widen_bf16(typename Bf16Raw<VEC>::type r) {
+  typename VecT<VEC>::type v;
+  if constexpr (VEC == 1) v = __uint_as_float((unsigned)r << 16);
+  else if constexpr (VEC == 2) {
+    v[0] = bf16_lo(r);
+    v[1] = bf16_hi(r);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC / 2; ++i) {
+      v[2 * i] = bf16_lo(r[i]);
+      v[2 * i + 1] = bf16_hi(r[i]);
+    }
+  }
+  return v;
+}
+// VEC elements of type E at p (global address) as VEC floats
+template <int VEC, typename E>
+__device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
+  if constexpr (sizeof(E) == 4) return *reinterpret_cast<const typename VecT<VEC>::type*>(p);
+  else return widen_bf16<VEC>(*reinterpret_cast<const typename Bf16Raw<VEC>::type*>(p));
+}
+
 // One feature-row gather.  BUF: `buffer_load_dwordxN v, voff, s[rsrc], soff offen` -- the row
 // base (col * row bytes) is a 32-bit SGPR offset against one descriptor for the whole table,
 // so a gather in flight costs only its VEC destination VGPRs (no 64-bit VGPR address pair).
@@ -123,16 +156,19 @@ typedef unsigned u4_t __attribute__((ext_vector_type(4)));
 // set by gaib_graph_ensure_hot_flags), so the few thousand hub rows keep their place in the 4 MB L2.
 // PART: two tables -- column ids below n_first index `in`, the others `in2` (a rank's own rows and its halo table, which
 // live in different allocations); the choice is a scalar select on the (wave-uniform) column id.
-template <int VEC, int GM, bool PART = false>
+// E: element type of the table -- float, or uint16_t for a bf16 table (a.in then points at bf16 bits, a.ld counts
+// elements, a.in_bytes is the bf16 size; voff is a byte offset into such a row).
+template <int VEC, int GM, bool PART = false, typename E = float>
 struct RowGather {
   static constexpr bool BUF = GM != 0;
+  static_assert(!PART || sizeof(E) == 4, "two-table gathers: fp32 tables only");
   __amdgpu_buffer_rsrc_t rsrc, rsrc2;
   const char *inb, *inb2;  // inb2 is biased by -n_first rows: row base = inb2 + col * ldb
   int64_t ldb;
   uint32_t n_first;
   __device__ __forceinline__ RowGather(const SpmmArgs& a) {
     inb = reinterpret_cast<const char*>(a.in);
-    ldb = a.ld * 4;
+    ldb = a.ld * (int64_t)sizeof(E);
     if constexpr (BUF) rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, (int)a.in_bytes, 0x00020000);
     if constexpr (PART) {
       n_first = a.in2 ? a.n_first : 0xffffffffu;
@@ -162,7 +198,8 @@ struct RowGather {
       return load_buf<0>(cj, voff);
     } else {
       const char* rowp = inb + (int64_t)cj * ldb;  // scalar base
-      return *reinterpret_cast<const vec_t*>(rowp + voff);
+      if constexpr (sizeof(E) == 2) return load_elems<VEC, E>(rowp + voff);
+      else return *reinterpret_cast<const vec_t*>(rowp + voff);
     }
   }
   template <int AUX>
@@ -172,7 +209,12 @@ struct RowGather {
   template <int AUX>
   __device__ __forceinline__ typename VecT<VEC>::type load_rsrc(__amdgpu_buffer_rsrc_t rsrc, int soff, uint32_t voff) const {
     typedef typename VecT<VEC>::type vec_t;
-    if constexpr (VEC == 1) {
+    if constexpr (sizeof(E) == 2) {  // bf16: half the bytes per gather (b16 / b32 / b64 / b128 for 1 / 2 / 4 / 8 elements)
+      if constexpr (VEC == 1) return widen_bf16<1>(__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)voff, soff, AUX));
+      else if constexpr (VEC == 2) return widen_bf16<2>(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX));
+      else if constexpr (VEC == 4) return widen_bf16<4>(__builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX));
+      else return widen_bf16<8>(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, soff, AUX));
+    } else if constexpr (VEC == 1) {
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX));
     } else if constexpr (VEC == 2) {
       u2_t r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX);
@@ -198,14 +240,15 @@ struct RowGather {
 // hipcc branch on EXEC and drain vmcnt after each one); what they accumulate is never stored.
 // PRE: the column ids (and weights) of the row's FIRST chunk were requested by the caller ahead of time (c_first / w_first,
 // lane l = edge eb + l, 0 past the row's end) -- the fused kernel asks for row r + 1's while row r's gathers are in flight.
-template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, bool PRE = false>
+template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, bool PRE = false, typename E = float>
 __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int64_t eb, int64_t ee,
                                                 int64_t chunk_stride, float roww,
                                                 const uint32_t (&voff)[CT],
                                                 typename VecT<VEC>::type (&acc)[CT], uint32_t c_first = 0u,
                                                 float w_first = 0.f) {
   typedef typename VecT<VEC>::type vec_t;
-  const RowGather<VEC, BUF, PART> gather(a);
+  static_assert(sizeof(E) == 4 || WMODE < 3, "bf16 tables: single-head weights");
+  const RowGather<VEC, BUF, PART, E> gather(a);
   vec_t x[U][CT];  // gather destinations; the tail's piece p lives in x[p .. 2p-1]
   constexpr bool MH = WMODE >= 3;  // multi-head: every lane fetches the weight of ITS head itself
   int hd[CT];

@@ -11,7 +11,8 @@
 namespace {
 
 // ---- light rows, one wave per row ------------------------------------------------------
-template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false>
+// E: element type of the gathered table (float, or uint16_t = bf16 bits; see RowGather)
+template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, typename E = float>
 __global__ __launch_bounds__(256) void spmm_w64_kernel(SpmmArgs a) {
   typedef typename VecT<VEC>::type vec_t;
   const int lane = threadIdx.x & 63;
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(256) void spmm_w64_kernel(SpmmArgs a) {
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     colok[ct] = (lane + ct * 64) * VEC < a.ncols;
-    voff[ct] = colok[ct] ? (uint32_t)((lane + ct * 64) * VEC * 4) : 0u;
+    voff[ct] = colok[ct] ? (uint32_t)((lane + ct * 64) * VEC * (int)sizeof(E)) : 0u;
     acc[ct] = vzero<VEC>();
   }
   const float roww = (WMODE == 0) ? a.rw[row] : 0.f;
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void spmm_w64_kernel(SpmmArgs a) {
     for (int ct = 0; ct < CT; ++ct)
       if (colok[ct]) acc[ct] = *reinterpret_cast<const vec_t*>(o + ct * 64 * VEC);
   }
-  wave_accumulate<VEC, CT, WMODE, U, BUF, PART>(a, lane, e0, e1, 64, roww, voff, acc);
+  wave_accumulate<VEC, CT, WMODE, U, BUF, PART, false, E>(a, lane, e0, e1, 64, roww, voff, acc);
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
     if (colok[ct]) *reinterpret_cast<vec_t*>(o + ct * 64 * VEC) = a.relu ? vrelu<VEC>(acc[ct]) : acc[ct];
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void spmm_w64_kernel(SpmmArgs a) {
 
 // ---- heavy rows, one 1024-thread workgroup per row ------------------------------------
 constexpr int HEAVY_WAVES = 16;
-template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false>
+template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, typename E = float>
 __global__ __launch_bounds__(HEAVY_WAVES * 64) void spmm_heavy_kernel(SpmmArgs a) {
   typedef typename VecT<VEC>::type vec_t;
   extern __shared__ __attribute__((aligned(16))) float red[];  // [HEAVY_WAVES][CT*64*VEC]
@@ -60,12 +61,12 @@ __global__ __launch_bounds__(HEAVY_WAVES * 64) void spmm_heavy_kernel(SpmmArgs a
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     const bool ok = (lane + ct * 64) * VEC < a.ncols;
-    voff[ct] = ok ? (uint32_t)((lane + ct * 64) * VEC * 4) : 0u;
+    voff[ct] = ok ? (uint32_t)((lane + ct * 64) * VEC * (int)sizeof(E)) : 0u;
     acc[ct] = vzero<VEC>();
   }
   const float roww = (WMODE == 0) ? a.rw[row] : 0.f;
-  wave_accumulate<VEC, CT, WMODE, U, BUF, PART>(a, lane, e0 + (int64_t)wave * 64, e1,
-                                           (int64_t)HEAVY_WAVES * 64, roww, voff, acc);
+  wave_accumulate<VEC, CT, WMODE, U, BUF, PART, false, E>(a, lane, e0 + (int64_t)wave * 64, e1,
+                                                          (int64_t)HEAVY_WAVES * 64, roww, voff, acc);
   constexpr int W = CT * 64 * VEC;
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(HEAVY_WAVES * 64) void spmm_heavy_kernel(SpmmArgs a
 }
 
 // ---- light rows, narrow features: 64/G rows per wave ----------------------------------
-template <int VEC, int G, int WMODE>
+template <int VEC, int G, int WMODE, typename E = float>
 __global__ __launch_bounds__(256) void spmm_sub_kernel(SpmmArgs a) {
   typedef typename VecT<VEC>::type vec_t;
   constexpr int RPW = 64 / G;
@@ -104,6 +105,7 @@ __global__ __launch_bounds__(256) void spmm_sub_kernel(SpmmArgs a) {
   const float roww = (WMODE == 0 && active) ? a.rw[row] : 0.f;
   const int head = (WMODE >= 3 && colok) ? (sl * VEC) / a.dh : 0;
   const float* inl = a.in + sl * VEC;
+  const char* inl_e = reinterpret_cast<const char*>(a.in) + sl * VEC * (int)sizeof(E);  // (E = bf16)
   for (int64_t e = e0; e < e1; e += U) {
     // every lane of the group reads the same colidx/weight address (hardware broadcast)
     uint32_t cj[U];
@@ -118,7 +120,10 @@ __global__ __launch_bounds__(256) void spmm_sub_kernel(SpmmArgs a) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const bool ok = e + u < e1;
-      x[u] = (ok && colok) ? *reinterpret_cast<const vec_t*>(inl + (int64_t)cj[u] * a.ld) : vzero<VEC>();
+      if constexpr (sizeof(E) == 2)
+        x[u] = (ok && colok) ? load_elems<VEC, E>(inl_e + (int64_t)cj[u] * a.ld * 2) : vzero<VEC>();
+      else
+        x[u] = (ok && colok) ? *reinterpret_cast<const vec_t*>(inl + (int64_t)cj[u] * a.ld) : vzero<VEC>();
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -128,21 +133,23 @@ __global__ __launch_bounds__(256) void spmm_sub_kernel(SpmmArgs a) {
 }
 
 // ---- dispatch --------------------------------------------------------------------------
-template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false>
+template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, typename E = float>
 int launch_w64_u(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
+  constexpr double EB = sizeof(E);  // bytes per gathered element
   // heavy rows first (few, long): their tail hides under the light kernel's start
   if (g->n_heavy > 0) {
     SpmmArgs h = a;
     h.row_list = g->heavy_rows;
     h.row_order = g->heavy_rows + g->n_heavy;
     size_t lds = sizeof(float) * HEAVY_WAVES * CT * 64 * VEC;
-    ProfScope ps(ctx, "spmm_heavy", gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4,
-                                                         a.accumulate ? 2 : 1), 2.0 * g->heavy_edges * a.ncols, a.ncols);
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_heavy" : "spmm_heavy",
+                 gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, EB),
+                 2.0 * g->heavy_edges * a.ncols, a.ncols);
     // (a 1024-thread workgroup leaves a wave 128 VGPRs: the multi-head edge-weight modes -- a weight per head and edge next to
     // the gathers -- keep half as many rows in flight there, or they spill 52-61 registers; 16 waves per row hide the rest)
     constexpr int UH = (WMODE >= 3 && U * CT * VEC > 16) ? (U / 2 > 4 ? U / 2 : 4) : U;
-    spmm_heavy_kernel<VEC, CT, WMODE, UH, BUF, PART><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds,
-                                                      ctx->stream>>>(h);
+    spmm_heavy_kernel<VEC, CT, WMODE, UH, BUF, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds,
+                                                         ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
   a.nblocks = (int)cdiv64(a.n_rows, 4);
@@ -158,15 +165,15 @@ int launch_w64_u(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   if (grid > 0) {
     // (row classes of a partition are timed under keys of their own: interior / owned-column pass, halo-column pass, one pass)
     const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_l = (double)a.n_rows - (double)g->n_heavy;
-    ProfScope ps(ctx, !PART ? "spmm_light" : (a.in2 ? "part_light_2t" : (a.accumulate ? "part_light_acc" : "part_light")),
-                 gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1), 2.0 * e_l * a.ncols, a.ncols);
-    spmm_w64_kernel<VEC, CT, WMODE, U, BUF, PART><<<dim3(grid), 256, 0, ctx->stream>>>(a);
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_light" : (!PART ? "spmm_light" : (a.in2 ? "part_light_2t" : (a.accumulate ? "part_light_acc" : "part_light"))),
+                 gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, EB), 2.0 * e_l * a.ncols, a.ncols);
+    spmm_w64_kernel<VEC, CT, WMODE, U, BUF, PART, E><<<dim3(grid), 256, 0, ctx->stream>>>(a);
     GAIB_LAUNCH_CHECK();
   }
   return GAIB_OK;
 }
 
-template <int VEC, int CT, int WMODE>
+template <int VEC, int CT, int WMODE, typename E = float>
 int launch_w64(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   // gathers in flight per wave: sized so the destination registers stay <= 32 VGPRs
   constexpr int U = (VEC * CT >= 8) ? 4 : (VEC * CT >= 4 ? 8 : 16);
@@ -182,32 +189,34 @@ int launch_w64(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   if constexpr (U > 8) {
     if (ctx->spmm_unroll == 8) {
       switch (gm) {
-        case 0: return launch_w64_u<VEC, CT, WMODE, 8, 0>(ctx, g, a);
-        case 2: return launch_w64_u<VEC, CT, WMODE, 8, 2>(ctx, g, a);
-        case 3: return launch_w64_u<VEC, CT, WMODE, 8, 3>(ctx, g, a);
-        default: return launch_w64_u<VEC, CT, WMODE, 8, 1>(ctx, g, a);
+        case 0: return launch_w64_u<VEC, CT, WMODE, 8, 0, false, E>(ctx, g, a);
+        case 2: return launch_w64_u<VEC, CT, WMODE, 8, 2, false, E>(ctx, g, a);
+        case 3: return launch_w64_u<VEC, CT, WMODE, 8, 3, false, E>(ctx, g, a);
+        default: return launch_w64_u<VEC, CT, WMODE, 8, 1, false, E>(ctx, g, a);
       }
     }
   }
   switch (gm) {
-    case 0: return launch_w64_u<VEC, CT, WMODE, U, 0>(ctx, g, a);
-    case 2: return launch_w64_u<VEC, CT, WMODE, U, 2>(ctx, g, a);
-    case 3: return launch_w64_u<VEC, CT, WMODE, U, 3>(ctx, g, a);
-    default: return launch_w64_u<VEC, CT, WMODE, U, 1>(ctx, g, a);
+    case 0: return launch_w64_u<VEC, CT, WMODE, U, 0, false, E>(ctx, g, a);
+    case 2: return launch_w64_u<VEC, CT, WMODE, U, 2, false, E>(ctx, g, a);
+    case 3: return launch_w64_u<VEC, CT, WMODE, U, 3, false, E>(ctx, g, a);
+    default: return launch_w64_u<VEC, CT, WMODE, U, 1, false, E>(ctx, g, a);
   }
 }
 
-template <int VEC, int G, int WMODE>
+template <int VEC, int G, int WMODE, typename E = float>
 int launch_sub(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   if (g->n_heavy > 0) {
     SpmmArgs h = a;
     h.row_list = g->heavy_rows;
     h.row_order = g->heavy_rows + g->n_heavy;
     size_t lds = sizeof(float) * HEAVY_WAVES * 64 * VEC;
-    ProfScope ps(ctx, "spmm_heavy", gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4,
-                                                         a.accumulate ? 2 : 1), 2.0 * g->heavy_edges * a.ncols, a.ncols);
-    spmm_heavy_kernel<VEC, 1, WMODE, 8, 0><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds,
-                                                 ctx->stream>>>(h);
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_heavy" : "spmm_heavy",
+                 gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1,
+                                     (double)sizeof(E)), 2.0 * g->heavy_edges * a.ncols, a.ncols);
+    constexpr int UH = VEC >= 8 ? 4 : 8;  // (8 elements per lane: 8 rows in flight spilled 33-55 registers)
+    spmm_heavy_kernel<VEC, 1, WMODE, UH, 0, false, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds,
+                                                         ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
   constexpr int RPW = 64 / G;
@@ -219,8 +228,10 @@ int launch_sub(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   }
   if (grid > 0) {
     const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_l = (double)a.n_rows - (double)g->n_heavy;
-    ProfScope ps(ctx, "spmm_sub", gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1), 2.0 * e_l * a.ncols, a.ncols);
-    spmm_sub_kernel<VEC, G, WMODE><<<dim3(grid), 256, 0, ctx->stream>>>(a);
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_sub" : "spmm_sub",
+                 gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, (double)sizeof(E)), 2.0 * e_l * a.ncols,
+                 a.ncols);
+    spmm_sub_kernel<VEC, G, WMODE, E><<<dim3(grid), 256, 0, ctx->stream>>>(a);
     GAIB_LAUNCH_CHECK();
   }
   return GAIB_OK;

@@ -14,6 +14,48 @@ static gaib_graph* dev(Graph& g) {
   return g.device_graph();
 }
 
+// ---- bf16 feature tables (option agg_bf16) ------------------------------------------------------------------------------
+bool aggregator::bf16_tables() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "agg_bf16", &v));
+  return v != 0;
+}
+// One process-wide scratch.  A buffer that has to grow is kept, not freed: a recorded epoch (gaib_exec) may still name it.
+static uint16_t* g_bf16_tab = nullptr;
+static size_t g_bf16_cap = 0;
+static gaib_ctx* g_bf16_ctx = nullptr;
+static std::vector<uint16_t*> g_bf16_retired;
+static uint16_t* bf16_table(size_t elems) {
+  if (g_bf16_ctx != C()) {  // a new process context (gpu_context::set): start a buffer on its device
+    if (g_bf16_tab) g_bf16_retired.push_back(g_bf16_tab);
+    g_bf16_tab = nullptr;
+    g_bf16_cap = 0;
+    g_bf16_ctx = C();
+  }
+  if (elems > g_bf16_cap) {
+    if (g_bf16_tab) g_bf16_retired.push_back(g_bf16_tab);
+    g_bf16_tab = nullptr;
+    g_bf16_cap = 0;
+    // (inside a capture gaib_malloc refuses: the run has to reserve the scratch before it records)
+    GAIB_OR_DIE(gaib_malloc(C(), elems * sizeof(uint16_t), (void**)&g_bf16_tab));
+    g_bf16_cap = elems;
+  }
+  return g_bf16_tab;
+}
+
+// the table of `rows` x `len` floats at `in` as bf16 bits in the scratch
+static const uint16_t* to_bf16(size_t rows, int len, const float* in) {
+  const size_t n = rows * (size_t)len;
+  uint16_t* t = bf16_table(n);
+  GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)n, in, t));
+  return t;
+}
+static void no_bf16_halo(Graph& g) {
+  if (!g.has_halo()) return;
+  fprintf(stderr, "GPU error: agg_bf16 (GAIB_AGG_DTYPE=bf16) covers whole graphs only; this graph has a halo (partitioned run)\n");
+  exit(EXIT_FAILURE);
+}
+
 // The halo-column half of a partitioned aggregation over `whole` (the mode's halo-column graph): in one pass after the whole
 // exchange -- last(whole, table) --, or, where the exchange travels in K > 1 time slices (gaib_halo_set_pieces), piece by piece
 // as the slices land: plain(piece k, table) in accumulate mode for every piece but the last non-empty one, which takes last()
@@ -41,6 +83,12 @@ static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last la
 static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* out, bool relu = false, bool count = true) {
   if (count) count_edges(g);
   const int act = relu ? GAIB_RELU : 0;
+  if (aggregator::bf16_tables()) {
+    no_bf16_halo(g);
+    gaib_graph* dg = dev(g);
+    GAIB_OR_DIE(gaib_spmm_bf16(C(), dg, kind, NULL, len, to_bf16((size_t)gaib_graph_nc(dg), len, in), out, act));
+    return;
+  }
   if (!g.has_halo()) {
     GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, out, act));
     return;
@@ -81,6 +129,17 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
                                        const float* rows2, const float* W2) {
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
+  if (bf16_tables()) {
+    // bf16 table: the aggregation gathers from it, the product(s) follow over all rows (no bf16 form of the fused kernel)
+    no_bf16_halo(g);
+    gaib_graph* dg = dev(g);
+    const int act = relu ? GAIB_RELU : 0;
+    GAIB_OR_DIE(gaib_spmm_bf16(C(), dg, kind, NULL, len, to_bf16((size_t)gaib_graph_nc(dg), len, in), agg, 0));
+    GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, agg, W, rows2 ? 0 : act, out));
+    if (rows2)
+      GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, rows2, W2, GAIB_ACCUMULATE | act, out));
+    return;
+  }
   const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
   auto fused = [&](gaib_graph* dg, const float* src, int fl) {
     if (rows2)

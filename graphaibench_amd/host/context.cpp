@@ -48,6 +48,16 @@ void gpu_context::set(int device, void* hip_stream) {
       pos = end + 1;
     }
   }
+  // the precision of the aggregations' feature tables (GCN / SAGE): fp32 (default) or bf16 -- a user-facing switch, so that
+  // a driver linked against the layer library gets bf16 tables without code changes
+  if (const char* d = getenv("GAIB_AGG_DTYPE")) {
+    const std::string dt(d);
+    if (dt != "fp32" && dt != "bf16") {
+      fprintf(stderr, "GAIB_AGG_DTYPE=%s: expected fp32 or bf16\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "agg_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_AGG_DTYPE)");
+  }
 }
 
 gaib_ctx* gpu_context::get() {

@@ -199,6 +199,15 @@ struct Trainer {
     if (subg_size > 0 || ARCH == gnn_arch::GAT) use_l2norm = use_dense = true;
     if (subg_size > 0) inductive = 1;  // net.cpp:160
     init_comm();
+    // the aggregations' feature tables: fp32, or bf16 with GAIB_AGG_DTYPE=bf16 (context option agg_bf16; GCN / SAGE only)
+    const bool bf16 = aggregator::bf16_tables();
+    if (root())
+      std::cout << "aggregation tables: " << (bf16 ? (ARCH == gnn_arch::GAT ? "fp32 (bf16 asked; GAT gathers fp32)" : "bf16") : "fp32")
+                << "\n";
+    if (bf16 && world > 1) {
+      std::cerr << "GAIB_AGG_DTYPE=bf16 runs on one GPU only (a partitioned run gathers fp32 tables)\n";
+      exit(EXIT_FAILURE);
+    }
     if (world > 1 && (subg_size > 0 || inductive)) {
       std::cerr << "subgraph sampling / inductive training run on one GPU only\n";
       exit(EXIT_FAILURE);

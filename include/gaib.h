@@ -106,6 +106,11 @@ int gaib_fill_f32(gaib_ctx* ctx, int64_t n, float value, float* d_x);
 /* x <- alpha * x  (scale, math_functions.cpp:336-356 / scal_gpu; the partitioned trainer rescales the loss gradient
  * from 1/(local range) to 1/(global range), softmax_loss_layer.cpp:31) */
 int gaib_scale_f32(gaib_ctx* ctx, int64_t n, float alpha, float* d_x);
+/* bf16 feature tables: raw bf16 bits in uint16_t.  f32 -> bf16 rounds to nearest, ties to even (torch's .to(torch.bfloat16)):
+ * subnormals kept, finite values past the largest bf16 round to +-inf; a NaN stays a quiet NaN of the same sign (upper half
+ * of its bits, quiet bit set).  bf16 -> f32 is exact (bits << 16).  in and out must not alias. */
+int gaib_cast_f32_bf16(gaib_ctx* ctx, int64_t n, const float* d_in, uint16_t* d_out);
+int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in, float* d_out);
 
 /* ---- graph: LearningGraph's device half (include/gnn/lgraph.h:20-277) ------------------
  * gaib_graph_create  = alloc_on_device + copy_to_gpu (src/gnn/lgraph.cu:51-92).
@@ -205,6 +210,16 @@ int gaib_spmm_acc(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_
                                   * under RCCL with > 1 rank, 0 on the peer-to-peer pull); at most num_cus - 64 */
 int gaib_spmm_ex(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                  const float* d_in, float* d_out, int flags);
+/* gaib_spmm_ex over a bf16 table: d_in is [nc x len] bf16 bits (row-major), d_out fp32 [nv x len], flags as for gaib_spmm_ex.
+ * Every gathered element is widened exactly and the sums are gaib_spmm_ex's (same weights, CSR order, separate multiply and
+ * add, same heavy-row split and fixed combine order, same ordered-chunk rule), so the result is BIT-IDENTICAL to gaib_spmm_ex
+ * on the table widened to fp32 (gaib_cast_bf16_f32) -- for d_in 8-B aligned and d_out 16-B aligned (otherwise a dense
+ * graph that gaib_spmm_ex aggregates by ordered chunks is aggregated row by row: deterministic, the CSR-order sum).
+ * Single-head weights (GAIB_W_GCN / _MEAN / _MEAN_T / _EDGE / _EDGE_T); square and rectangular graphs.  A graph with a row
+ * map (a row class of a partition, gaib_graph_split_classes): GAIB_ERR_UNSUPPORTED.  A table of >= 4 GB in bf16 is gathered
+ * with 64-bit addresses. */
+int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, const uint16_t* d_in,
+                   float* d_out, int flags);
 /* multi-head attention weights: d_edge_w is [ne][heads]; column c uses head c / (len/heads).
  * weight_kind must be GAIB_W_EDGE or GAIB_W_EDGE_T when heads > 1. */
 int gaib_spmm_mh(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int heads,
@@ -635,11 +650,15 @@ int gaib_graph_stats(gaib_ctx* ctx, gaib_graph* g, int64_t* h_n_heavy, int64_t* 
 int gaib_probe_stream_copy(gaib_ctx* ctx, size_t bytes, int iters, double* h_gbs);
 int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int bidir, double* h_gbs);
 
-/* ---- tuning knobs (benchmarks only; defaults are what ships) ---- */
+/* ---- tuning knobs (benchmarks only; defaults are what ships) ----
+ * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
+ * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16; GAT ignores it, a partitioned
+ * graph refuses it); "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 = sub-wave rows of
+ * 4 / 8 elements per lane.  Both readable with gaib_get_option. */
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
- * "spmm_fuse_cus", "spmm_flat_ring", "num_cus" */
+ * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -10,6 +10,11 @@
 class aggregator {
  public:
   aggregator() : n(0), length(0), fuse_relu(false) {}
+  // extension: bf16 feature tables (context option "agg_bf16" = 1, or GAIB_AGG_DTYPE=bf16): the GCN / SAGE aggregations
+  // cast their table into a bf16 scratch and gather from there (gaib_spmm_bf16; fp32 sums and output).  The scratch is
+  // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
+  // epoch 0 eagerly).  GAT ignores the option; a partitioned graph (halo) refuses it.
+  static bool bf16_tables();
   void set_vlen(int vlen) { length = vlen; }
   // extension: the next aggregate() call clamps its output at 0 (the layer's relu_gpu fused
   // into the aggregation's store); cleared by that call
