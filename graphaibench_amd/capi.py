@@ -76,6 +76,8 @@ SIGNATURES = {
     "gaib_spmm_gemm2": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_mh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i]),
     "gaib_spmm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "gaib_spmm_gemm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "gaib_spmm_gemm2_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_graph_split_classes": (_i, [_vp, _vp, _vp, _pp, _pp, _pp, _pp, C.POINTER(_i64), C.POINTER(_i64), _i]),
     "gaib_graph_split_pieces": (_i, [_vp, _vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _pp]),
     "gaib_graph_set_row_map": (_i, [_vp, _vp, _vp, _i64]),
@@ -527,6 +529,27 @@ class Context:
             return out
         _check(self.lib.gaib_spmm_gemm(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),
                                        1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm")
+        return out
+
+    def spmm_gemm_bf16(self, g: "Graph", kind: int, x, agg, W, out, transW: bool = False, relu: bool = False,
+                       agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None):
+        """gaib_spmm_gemm_bf16 / gaib_spmm_gemm2_bf16: spmm_gemm with x a [nc x len_in] torch.bfloat16 table; agg, W, rows2, W2
+        and out fp32.  The bits of spmm_gemm on the widened table."""
+        import torch
+
+        assert x.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
+        assert x.dtype == torch.bfloat16 and agg.dtype == torch.float32 and out.dtype == torch.float32
+        len_in, len_out = agg.shape[1], out.shape[1]
+        assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))
+        flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0)
+        if rows2 is not None:
+            assert rows2.is_contiguous() and W2.is_contiguous() and W2.shape == W.shape and rows2.shape[1] == len_in
+            _check(self.lib.gaib_spmm_gemm2_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),
+                                                 1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags),
+                   "gaib_spmm_gemm2_bf16")
+            return out
+        _check(self.lib.gaib_spmm_gemm_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),
+                                            1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm_bf16")
         return out
 
     def spmm_2t(self, g: "Graph", kind: int, x, x2, n_first: int, out, edge_w=None, accumulate: bool = False,

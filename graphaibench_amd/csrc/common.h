@@ -46,6 +46,7 @@ void gaib_set_error(const char* fmt, ...);
 
 
 #define GAIB_FLAT_RING_DEFAULT 1  // spmm_flat_ring's default (see spmm_kernels.h RING)
+#define GAIB_BF16_FUSE_U 32       // gathers in flight per wave in the row forms of the bf16 fused aggregation (launch_fused)
 
 struct gaib_ctx {
   int device;
@@ -86,7 +87,8 @@ struct gaib_ctx {
   int spmm_gather_mode;      // 0/1 default cache policy, 2 = nt gathers, 3 = nt for cold columns only
   int spmm_hot_bytes;        // L2 budget for the hot rows of gather mode 3
   int spmm_bf16_layout;      // gaib_spmm_bf16's lane layout: 0 = one row per wave (auto lane width), 4 / 8 = sub-wave rows of 4 / 8 elements per lane
-  int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16)
+  int spmm_bf16_fuse_u;      // benchmark only: gathers in flight of the bf16 fused kernel's headline variant, 0 = default (GAIB_BF16_FUSE_U), 16 / 32
+  int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16, gaib_spmm_gemm_bf16)
   int sgemm_variant;         // 0 = auto
   int gat_fast;              // reserved
   int gat_chunk_colsum;      // GAT backward column sums by ordered chunks: -1 = dense graphs, 0 never, 1 always

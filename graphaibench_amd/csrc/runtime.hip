@@ -65,6 +65,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_gather_mode = 0;
   c->spmm_hot_bytes = 3 << 20;
   c->spmm_bf16_layout = 0;
+  c->spmm_bf16_fuse_u = 0;
   c->agg_bf16 = 0;
   c->sgemm_variant = 0;
   if (const char* e = getenv("GAIB_SGEMM_VARIANT")) c->sgemm_variant = atoi(e);  // (A/B of a whole trainer run: 61 = without sgemm_skinny.hip)
@@ -524,6 +525,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
   else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
+  else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
   else {
     gaib_set_error("gaib_get_option: no readable option '%s'", key);
     return GAIB_ERR_INVALID;
@@ -566,6 +568,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   else if (!strcmp(key, "spmm_bf16_layout")) {
     GAIB_CHECK(value == 0 || value == 4 || value == 8, "spmm_bf16_layout must be 0, 4 or 8");
     ctx->spmm_bf16_layout = (int)value;
+  } else if (!strcmp(key, "spmm_bf16_fuse_u")) {
+    GAIB_CHECK(value == 0 || value == 16 || value == 32, "spmm_bf16_fuse_u must be 0 (default), 16 or 32");
+    ctx->spmm_bf16_fuse_u = (int)value;
   } else if (!strcmp(key, "agg_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->agg_bf16 = (int)value;

@@ -340,6 +340,9 @@ static bool chunk_rule(gaib_ctx* ctx, gaib_graph* g, int64_t ld) {
 int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len);
 int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
                          int vec, int wmode);
+// ... and so do the fused kernels over a bf16 table: spmm_gemm_bf16.hip
+int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
+                         int vec, int wmode);
 
 static int spmm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                      const float* d_in, float* d_out, int flags, int heads = 1, const float* d_in2 = nullptr,
@@ -420,10 +423,14 @@ extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in
   return ctx && fuse_shape_ok(ctx, weight_kind, len_in, len_out, dual != 0) ? 1 : 0;
 }
 
+// bf16: d_in holds bf16 bits (gaib_spmm_gemm_bf16; whole graphs, checked by the caller).  Every test below is made on what the
+// fp32 call would see for the same table widened -- the widened table sits at "twice the address" (a bf16 table aligned to 8 B
+// stands for an fp32 one aligned to 16), sizes and the chunk rule count fp32 bytes -- so both take the same route, and each route
+// runs with the bf16 gather: no fp32 copy of the table anywhere.
 static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                           const float* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                           const float* d_W2, int len_out, float* d_out, int flags, const float* d_in2 = nullptr,
-                          int64_t n_first = 0) {
+                          int64_t n_first = 0, bool bf16 = false) {
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm: NULL ctx/graph");
   GAIB_CHECK(len_in >= 0 && len_out >= 0, "gaib_spmm_gemm: negative length");
   GAIB_CHECK(ctx->device == g->device, "gaib_spmm_gemm: graph lives on device %d, ctx on %d", g->device,
@@ -437,7 +444,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
              "gaib_spmm_gemm: buffers must not alias");
   const bool dual = d_rows2 != nullptr;
   const bool part = g->row_map != nullptr || d_in2 != nullptr;
-  const uintptr_t al = (uintptr_t)d_in | (uintptr_t)d_agg | (uintptr_t)d_in2;
+  const uintptr_t al = (bf16 ? (uintptr_t)d_in << 1 : (uintptr_t)d_in) | (uintptr_t)d_agg | (uintptr_t)d_in2;
   // the weight matrices [len_out x (len_in+4)] and 16 row strips must fit the CU's 160 KB of LDS;
   // 65..128 columns need 8-byte lanes
   const int kpad = len_in <= 64 ? 64 : 128;
@@ -457,7 +464,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   // accumulating GEMM below runs over rows [0, nv) of rows2 / out; it gets GAIB_ERR_UNSUPPORTED further down)
   if (!part && shape_ok && dual && fuse_strip_rows(kpad, len_out, true) == 0 && fuse_strip_rows(kpad, len_out, false) != 0) {
     GAIB_TRY(spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out,
-                            flags & ~GAIB_RELU));
+                            flags & ~GAIB_RELU, nullptr, 0, bf16));
     return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2,
                          GAIB_ACCUMULATE | ((flags & GAIB_RELU) ? GAIB_RELU : 0), d_out);
   }
@@ -484,7 +491,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   if (kslab) {
     SpmmArgs a0;
     int wmode = 0;
-    GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode));
+    GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode, nullptr, 0, bf16));
     const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;
     const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * len_in + 255) & ~(size_t)255;
     GAIB_TRY(gaib_ws_reserve(ctx, wt_bytes + hv_bytes + 256));
@@ -500,11 +507,12 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
     }
     for (int k0 = 0; k0 < len_in; k0 += 128) {
       SpmmArgs a = a0;
-      a.in = a0.in + k0;
+      // (bf16: the slab offset and in_bytes count bf16 elements)
+      a.in = bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0) : a0.in + k0;
       a.ncols = len_in - k0 < 128 ? len_in - k0 : 128;
       a.accumulate = 0;
       a.out = (flags & GAIB_AGG_SCRATCH) ? nullptr : d_agg + k0;
-      if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * 4);
+      if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * (bf16 ? 2 : 4));
       FuseArgs f;
       f.wt = wk + k0;
       f.wt2 = nullptr;
@@ -522,7 +530,8 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
       f.heavy_agg = hv + k0;
       f.heavy_rows = g->heavy_rows;
       f.n_heavy = (int)g->n_heavy;
-      GAIB_TRY(wmode == 0 ? (launch_fused<2, 0>(ctx, g, a, f, hv + k0)) : (launch_fused<2, 1>(ctx, g, a, f, hv + k0)));
+      if (bf16) GAIB_TRY(gaib_spmm_fused_bf16(ctx, g, &a, &f, hv + k0, 2, wmode));
+      else GAIB_TRY(wmode == 0 ? (launch_fused<2, 0>(ctx, g, a, f, hv + k0)) : (launch_fused<2, 1>(ctx, g, a, f, hv + k0)));
     }
     if (dual)
       return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2,
@@ -531,14 +540,15 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   }
   if (!fusable) {
     const int act = (flags & GAIB_RELU) ? GAIB_RELU : 0;
-    GAIB_TRY(spmm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, flags & GAIB_ACCUMULATE));
+    if (bf16) GAIB_TRY(gaib_spmm_bf16(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const uint16_t*>(d_in), d_agg, flags & GAIB_ACCUMULATE));
+    else GAIB_TRY(spmm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, flags & GAIB_ACCUMULATE));
     GAIB_TRY(gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_agg, d_W, dual ? 0 : act, d_out));
     if (dual) return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2, GAIB_ACCUMULATE | act, d_out);
     return GAIB_OK;
   }
   SpmmArgs a;
   int wmode = 0;
-  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first));
+  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first, bf16));
   a.accumulate = 0;  // (the fused kernel takes the partial sums through f.agg_in)
   if (flags & GAIB_AGG_SCRATCH) a.out = nullptr;  // the caller does not read agg: skip its store
   // scratch: op(W) (and op(W2)) k-contiguous + the heavy rows' aggregates + the tile counter
@@ -578,6 +588,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   f.heavy_rows = g->heavy_rows;
   f.n_heavy = (int)g->n_heavy;
   if (part) return gaib_spmm_part_fused(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
+  if (bf16) return gaib_spmm_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
   if (len_in <= 64) {
     return wmode == 0 ? launch_fused<1, 0>(ctx, g, a, f, hv) : launch_fused<1, 1>(ctx, g, a, f, hv);
   }
@@ -721,4 +732,36 @@ extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, con
     case 1: return dispatch_bf16<1>(ctx, g, a, len);
     default: return dispatch_bf16<2>(ctx, g, a, len);
   }
+}
+
+// agg = A.widen(in) ; out = act(agg . op(W) [+ rows2 . op(W2)]) with `in` in bf16 (raw bits), everything else fp32: the route
+// gaib_spmm_gemm(2) takes on the widened table, run with the bf16 gather -- d_agg (unless scratch) and d_out bit-identical to
+// that call, for d_in aligned to 8 B and d_agg to 16.
+static int spmm_gemm_bf16_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                                const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_gemm_bf16: NULL ctx/graph");
+  GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm_bf16: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which "
+                                                "aggregate fp32 tables");
+  if (g->row_map) {
+    gaib_set_error("gaib_spmm_gemm_bf16: a row class of a partition (graph with a row map) is not supported: fp32 tables only");
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2,
+                        d_W2, len_out, d_out, flags, nullptr, 0, true);
+}
+
+extern "C" int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                   const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
+                                   int flags) {
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out,
+                              flags);
+}
+
+extern "C" int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                    const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                                    const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_bf16: NULL second operand");
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out,
+                              flags);
 }

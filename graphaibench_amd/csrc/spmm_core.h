@@ -1,6 +1,7 @@
-// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_gemm.hip):
+// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_part.hip, spmm_gemm_bf16.hip):
 // launch arguments, the feature-row gather and the per-wave edge loop.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -176,7 +177,16 @@ struct RowGather {
       if constexpr (BUF) rsrc2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.in2, 0, (int)a.in2_bytes, 0x00020000);
     }
   }
-  __device__ __forceinline__ typename VecT<VEC>::type load(uint32_t cj, uint32_t voff) const {
+  // What a gather leaves in registers until it is consumed: the fp32 vector itself, or the packed words of VEC bf16 elements
+  // (half the registers).  load_raw() requests, widen() -- exact, bits << 16 -- belongs at the point of use: widened at the load,
+  // the shifts sit between the loads of a batch and every gather in flight holds fp32-sized registers.
+  typedef typename std::conditional<sizeof(E) == 2, typename Bf16Raw<VEC>::type, typename VecT<VEC>::type>::type raw_t;
+  static __device__ __forceinline__ typename VecT<VEC>::type widen(const raw_t& r) {
+    if constexpr (sizeof(E) == 2) return widen_bf16<VEC>(r);
+    else return r;
+  }
+  __device__ __forceinline__ typename VecT<VEC>::type load(uint32_t cj, uint32_t voff) const { return widen(load_raw(cj, voff)); }
+  __device__ __forceinline__ raw_t load_raw(uint32_t cj, uint32_t voff) const {
     typedef typename VecT<VEC>::type vec_t;
     if constexpr (PART) {
       static_assert(GM == 0 || GM == 1, "two-table gathers: plain buffer or global loads");
@@ -198,22 +208,22 @@ struct RowGather {
       return load_buf<0>(cj, voff);
     } else {
       const char* rowp = inb + (int64_t)cj * ldb;  // scalar base
-      if constexpr (sizeof(E) == 2) return load_elems<VEC, E>(rowp + voff);
+      if constexpr (sizeof(E) == 2) return *reinterpret_cast<const raw_t*>(rowp + voff);
       else return *reinterpret_cast<const vec_t*>(rowp + voff);
     }
   }
   template <int AUX>
-  __device__ __forceinline__ typename VecT<VEC>::type load_buf(uint32_t cj, uint32_t voff) const {
+  __device__ __forceinline__ raw_t load_buf(uint32_t cj, uint32_t voff) const {
     return load_rsrc<AUX>(rsrc, (int)(cj * (uint32_t)ldb), voff);
   }
   template <int AUX>
-  __device__ __forceinline__ typename VecT<VEC>::type load_rsrc(__amdgpu_buffer_rsrc_t rsrc, int soff, uint32_t voff) const {
+  __device__ __forceinline__ raw_t load_rsrc(__amdgpu_buffer_rsrc_t rsrc, int soff, uint32_t voff) const {
     typedef typename VecT<VEC>::type vec_t;
     if constexpr (sizeof(E) == 2) {  // bf16: half the bytes per gather (b16 / b32 / b64 / b128 for 1 / 2 / 4 / 8 elements)
-      if constexpr (VEC == 1) return widen_bf16<1>(__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)voff, soff, AUX));
-      else if constexpr (VEC == 2) return widen_bf16<2>(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX));
-      else if constexpr (VEC == 4) return widen_bf16<4>(__builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX));
-      else return widen_bf16<8>(__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, soff, AUX));
+      if constexpr (VEC == 1) return __builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)voff, soff, AUX);
+      else if constexpr (VEC == 2) return __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX);
+      else if constexpr (VEC == 4) return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX);
+      else return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, soff, AUX);
     } else if constexpr (VEC == 1) {
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX));
     } else if constexpr (VEC == 2) {
@@ -246,10 +256,10 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
                                                 const uint32_t (&voff)[CT],
                                                 typename VecT<VEC>::type (&acc)[CT], uint32_t c_first = 0u,
                                                 float w_first = 0.f) {
-  typedef typename VecT<VEC>::type vec_t;
   static_assert(sizeof(E) == 4 || WMODE < 3, "bf16 tables: single-head weights");
-  const RowGather<VEC, BUF, PART, E> gather(a);
-  vec_t x[U][CT];  // gather destinations; the tail's piece p lives in x[p .. 2p-1]
+  typedef RowGather<VEC, BUF, PART, E> gather_t;
+  const gather_t gather(a);
+  typename gather_t::raw_t x[U][CT];  // gather destinations (bf16: packed words, widened where consumed); the tail's piece p lives in x[p .. 2p-1]
   constexpr bool MH = WMODE >= 3;  // multi-head: every lane fetches the weight of ITS head itself
   int hd[CT];
   float wv[MH ? U : 1][CT];
@@ -275,7 +285,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
         const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)c, j + u);
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-          x[u][ct] = gather.load(cj, voff[ct]);
+          x[u][ct] = gather.load_raw(cj, voff[ct]);
           if constexpr (MH) wv[u][ct] = load_edge_w<WMODE>(a, base + j + u, hd[ct]);
         }
       }
@@ -289,7 +299,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
         for (int ct = 0; ct < CT; ++ct) {
           float wsel = wj;
           if constexpr (MH) wsel = wv[u][ct];
-          vacc<VEC>(acc[ct], wsel, x[u][ct]);
+          vacc<VEC>(acc[ct], wsel, gather_t::widen(x[u][ct]));
         }
       }
     }
@@ -305,7 +315,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
           for (int u = 0; u < p; ++u) {
             const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)c, jj + u);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) x[p + u][ct] = gather.load(cj, voff[ct]);
+            for (int ct = 0; ct < CT; ++ct) x[p + u][ct] = gather.load_raw(cj, voff[ct]);
           }
           jj += p;
         }
@@ -323,7 +333,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
               // (the tail is short: its per-head weights are fetched at the point of use)
               float wh = wj;
               if constexpr (MH) wh = load_edge_w<WMODE>(a, base + jj + u, hd[ct]);
-              vacc<VEC>(acc[ct], wh, x[p + u][ct]);
+              vacc<VEC>(acc[ct], wh, gather_t::widen(x[p + u][ct]));
             }
           }
           jj += p;

@@ -388,10 +388,14 @@ constexpr int FUSE_WAVES = 16;
 // AFFINE: the XCD-affine tile supply is compiled in.  A template flag, not a run-time test: with both supplies in one loop the
 // global-counter form -- the headline's, a random vertex order -- ran 0.5 % slower than before the affine supply existed
 // (7.597 -> 7.635 ms per launch, bisected to that change on one box: scripts/drift_ab.sh, profiles/r04/drift_*.jsonl).
+// E: element type of the gathered table (float, or uint16_t = bf16 bits; see RowGather).  Only the gather differs: a gather in
+// flight is held as the packed words it arrived in and widened where it is consumed, so U bf16 gathers cost the registers of
+// U / 2 fp32 ones.  Partial sums, parked strips, op(W), the product and every store are fp32 whatever E is.
 template <int VEC, int WMODE, int U, int GM, int STRIP, bool DUAL, bool FLAT = false, bool YACC = false, bool PART = false,
-          bool RING = false, bool AFFINE = false, bool PREF = false>
+          bool RING = false, bool AFFINE = false, bool PREF = false, typename E = float>
 __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, FuseArgs f) {
   typedef typename VecT<VEC>::type vec_t;
+  typedef RowGather<VEC, GM, PART, E> gather_t;
   constexpr int K = 64 * VEC;  // padded inner dimension; a.ncols (<= K) columns are real
   constexpr int KQ = K / 4;
   constexpr int LDT = K + 4;
@@ -417,7 +421,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
   // between the gathered rows (measured: the halo-column half 3.79 -> 3.60 ms per step, the headline kernel unchanged at
   // 7.54-7.55 ms; product rows stored the same way change nothing either way)
   auto store_row = [&](vec_t* p, const vec_t& v) { __builtin_nontemporal_store(v, p); };
-  const uint32_t voff[1] = {colok ? (uint32_t)(lane * VEC * 4) : 0u};
+  const uint32_t voff[1] = {colok ? (uint32_t)(lane * VEC * (int)sizeof(E)) : 0u};
   const int ntiles = (a.n_rows + FUSE_ROWS - 1) / FUSE_ROWS;
   // FLAT: tiles are cheap (a few edges per row), and one atomic per tile on one address becomes the floor (153 k
   // atomics = 0.4 ms at 2.4 M rows).  Guided chunks instead: a wave takes (tiles left) / (4 x waves) tiles at a time,
@@ -536,7 +540,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
             return ((int64_t)__builtin_amdgcn_readlane(rp_hi, rr) << 32) | (uint32_t)__builtin_amdgcn_readlane(rp_lo, rr);
           };
           const int64_t e_lo = rp_at(rbase), e_hi = rp_at(rbase + HALF);
-          const RowGather<VEC, GM, PART> gather(a);
+          const gather_t gather(a);
           float* trow_w = tile + lane * VEC;  // this lane's columns of strip row 0
           // RING: ids and weights of the strip's first (and second) 64 edges, lane l holds edge 64 q + l
           const int total = (int)(e_hi - e_lo);  // (a strip without heavy rows: at most HALF x heavy_thr edges)
@@ -586,11 +590,11 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
             }
           };
           if constexpr (RING) {
-            vec_t x[U];
+            typename gather_t::raw_t x[U];
             if (total > 0) {
 #pragma unroll
               for (int u = 0; u < U; ++u)  // (edges past the strip's end read row 0 of the table: never consumed)
-                x[u] = gather.load((uint32_t)__builtin_amdgcn_readlane((int)c_cur, u), voff[0]);
+                x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c_cur, u), voff[0]);
             }
             for (int k = 0; k < total; k += U) {
               const int kc = k & 63;
@@ -605,18 +609,18 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                   while (e_lo + k + u == row_end) flush();
-                  vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), x[u]);
-                  x[u] = gather.load((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
+                  vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), gather_t::widen(x[u]));
+                  x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
                 }
               } else {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                   if (k + u < total) {
                     while (e_lo + k + u == row_end) flush();
-                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), x[u]);
+                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), gather_t::widen(x[u]));
                   }
                   if (k + u + U < total)
-                    x[u] = gather.load((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
+                    x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
                 }
               }
             }
@@ -630,17 +634,17 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
               c = a.col[base + lane];
               if constexpr (WMODE == 1 || WMODE == 2) w = load_edge_w<WMODE>(a, base + lane);
             }
-            vec_t x[U];
+            typename gather_t::raw_t x[U];
             int j = 0;
             for (; j + U <= n; j += U) {
 #pragma unroll
               for (int u = 0; u < U; ++u)
-                x[u] = gather.load((uint32_t)__builtin_amdgcn_readlane((int)c, j + u), voff[0]);
+                x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c, j + u), voff[0]);
               __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
               for (int u = 0; u < U; ++u) {
                 while (base + j + u == row_end) flush();
-                vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, j + u), x[u]);
+                vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, j + u), gather_t::widen(x[u]));
               }
             }
             const int rest = n - j;
@@ -651,7 +655,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
                 if (rest & p) {
 #pragma unroll
                   for (int u = 0; u < p; ++u)
-                    x[p + u] = gather.load((uint32_t)__builtin_amdgcn_readlane((int)c, jj + u), voff[0]);
+                    x[p + u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c, jj + u), voff[0]);
                   jj += p;
                 }
               }
@@ -663,7 +667,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
 #pragma unroll
                   for (int u = 0; u < p; ++u) {
                     while (base + jj + u == row_end) flush();
-                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, jj + u), x[p + u]);
+                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, jj + u), gather_t::widen(x[p + u]));
                   }
                   jj += p;
                 }
@@ -707,7 +711,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
             }
           } else {
             const float roww = (WMODE == 0) ? a.rw[row] : 0.f;
-            wave_accumulate<VEC, 1, WMODE, U, GM, PART, PRE>(a, lane, e0, e1, 64, roww, voff, acc, c_now, w_now);
+            wave_accumulate<VEC, 1, WMODE, U, GM, PART, PRE, E>(a, lane, e0, e1, 64, roww, voff, acc, c_now, w_now);
           }
           if (a.out && colok) store_row(reinterpret_cast<vec_t*>(a.out + orow(rr) * a.ldo + lane * VEC), acc[0]);
         }
@@ -881,9 +885,18 @@ inline int fuse_strip_rows(int kpad, int n_out, bool dual) {
   return fuse_lds_bytes(kpad, n_out, dual, 2) <= 160 * 1024 ? 2 : 0;
 }
 
-template <int VEC, int WMODE, bool PART = false>
+// E = uint16_t (whole graphs only): a.in points at bf16 bits, a.ld counts elements, a.in_bytes is the bf16 size.  Gathers in flight
+// per wave: a bf16 gather is held packed (half the registers of an fp32 one), so the row forms keep GAIB_BF16_FUSE_U of them where
+// fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  The XCD-affine tile supply is not compiled in for bf16 (it would
+// triple this set of instantiations for the planted-locality case alone; the supply changes no row's sum): global counter.
+template <int VEC, int WMODE, bool PART = false, typename E = float>
 int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
-  constexpr int U = 16;
+  constexpr bool BF = sizeof(E) == 2;
+  static_assert(!BF || !PART, "bf16 tables: whole graphs only");
+  constexpr int U = 16;                               // the heavy kernel's, and the fp32 row forms'
+  constexpr int UROW = BF ? GAIB_BF16_FUSE_U : U;     // row forms
+  constexpr int UFLAT = BF ? 16 : 8;                  // edge-stream forms
+  constexpr double EB = sizeof(E);
   constexpr int K = 64 * VEC;
   // buffer loads need every table below 4 GB
   const bool buf = a.in_bytes != 0 && ctx->spmm_addr_mode != 2 && (!PART || !a.in2 || a.in2_bytes != 0);
@@ -896,13 +909,14 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
     h.relu = 0;
     h.accumulate = 0;
     size_t lds = sizeof(float) * HEAVY_WAVES * 64 * VEC;
-    ProfScope ps(ctx, "spmm_heavy", gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1),
+    ProfScope ps(ctx, BF ? "spmm_bf16_heavy" : "spmm_heavy",
+                 gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1, EB),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
-    if (buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
-    else spmm_heavy_kernel<VEC, 1, WMODE, U, 0, PART><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    if (buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    else spmm_heavy_kernel<VEC, 1, WMODE, U, 0, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
-  if constexpr (PART) f.tile_xcd = 0;
+  if constexpr (PART || BF) f.tile_xcd = 0;
   const bool dual = f.wt2 != nullptr;
   const int strip = fuse_strip_rows(K, f.n_out, dual);  // 8, 2 or 0 (does not fit: the caller checked)
   const size_t lds = fuse_lds_bytes(K, f.n_out, dual, strip);
@@ -916,21 +930,21 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   // SURVEY 8(d) for the aggregation part (the heavy rows' edges are the heavy kernel's) + what the riding product moves: the
   // aggregate rows stored (unless scratch) or continued (agg_in), y written (read too on a later K-slab), the second row operand
   const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_all = (double)a.n_rows;
-  const double fused_bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (dual ? 1 : 0)) +
+  const double fused_bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (dual ? 1 : 0), EB) +
                              r_all * 4.0 * f.n_out * (f.y_accum ? 2 : 1);
   const double fused_flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (dual ? 2 : 1);
-  ProfScope ps(ctx, !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused")), fused_bytes,
+  ProfScope ps(ctx, BF ? "spmm_gemm_bf16_fused" : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused")), fused_bytes,
                fused_flops, a.ncols);
   // more than 64 KB of dynamic LDS has to be asked for
   // (the edge-stream form keeps 8 gathers in flight, not 16: with 16 the operand fragments of the dense product
   // spill and are reloaded inside the MFMA loop)
 #define GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, AFF, PRE)                                              \
   do {                                                                                                                \
-    constexpr int UU = FLAT ? 8 : U;                                                                                  \
+    constexpr int UU = FLAT ? UFLAT : UROW;                                                                           \
     GAIB_HIP(hipFuncSetAttribute(                                                                                     \
-        (const void*)spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE>,             \
+        (const void*)spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE, E>,          \
         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                     \
-    spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE>                               \
+    spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE, E>                            \
         <<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);                                                    \
   } while (0)
 #define GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, AFF)                                                   \
@@ -945,7 +959,7 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   // (row classes of a partition are rectangular graphs: their numbering is never measured as local, no affine variants)
 #define GAIB_FUSED_LAUNCH_R(GM, STRIP, DUAL, FLAT, YACC, RING)                                                        \
   do {                                                                                                                \
-    if constexpr (!PART) {                                                                                            \
+    if constexpr (!PART && !BF) {                                                                                     \
       if (f.tile_xcd) GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, true);                                   \
       else GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, false);                                             \
     } else {                                                                                                          \
@@ -959,7 +973,21 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   const bool flat = !dual && strip == 8 && !f.y_accum &&
                     (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * (int64_t)a.n_rows));
   const bool ring = flat && ctx->spmm_flat_ring != 0;  // the edge stream as a software pipeline (see RING)
-  if (f.y_accum) {  // the second K-slab of a 129..256-column aggregation (VEC == 2 only; never dual or flat; not on row classes)
+  // option spmm_bf16_fuse_u (benchmark only): the other depth of the A/B, on the headline variant alone -- bf16 row form,
+  // 8-row strip, buffer addressing, 8-B lanes
+  bool launched = false;
+  if constexpr (BF && VEC == 2) {
+    constexpr int UALT = UROW == 32 ? 16 : 32;
+    if (ctx->spmm_bf16_fuse_u == UALT && buf && !dual && strip == 8 && !flat && !f.y_accum) {
+      GAIB_HIP(hipFuncSetAttribute((const void*)spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>
+          <<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+      launched = true;
+    }
+  }
+  if (launched) {
+  } else if (f.y_accum) {  // the second K-slab of a 129..256-column aggregation (VEC == 2 only; never dual or flat; not on row classes)
     if constexpr (VEC == 2 && !PART) {
       if (buf) {
         if (strip == 2) GAIB_FUSED_LAUNCH_Y(1, 2, false, false, true);

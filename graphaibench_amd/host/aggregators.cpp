@@ -130,14 +130,15 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
   if (bf16_tables()) {
-    // bf16 table: the aggregation gathers from it, the product(s) follow over all rows (no bf16 form of the fused kernel)
+    // bf16 table: the fused kernel gathers from it -- the route (and the bits) of the fp32 branch below on the rounded table
     no_bf16_halo(g);
     gaib_graph* dg = dev(g);
-    const int act = relu ? GAIB_RELU : 0;
-    GAIB_OR_DIE(gaib_spmm_bf16(C(), dg, kind, NULL, len, to_bf16((size_t)gaib_graph_nc(dg), len, in), agg, 0));
-    GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, agg, W, rows2 ? 0 : act, out));
+    const int fl = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
+    const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(dg), len, in);
     if (rows2)
-      GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, rows2, W2, GAIB_ACCUMULATE | act, out));
+      GAIB_OR_DIE(gaib_spmm_gemm2_bf16(C(), dg, kind, NULL, len, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
+    else
+      GAIB_OR_DIE(gaib_spmm_gemm_bf16(C(), dg, kind, NULL, len, tab, agg, W, transW ? 1 : 0, len_out, out, fl));
     return;
   }
   const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);

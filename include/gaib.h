@@ -419,6 +419,23 @@ int gaib_spmm_gemm2(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* 
                     int len_in, const float* d_in, float* d_agg, const float* d_W, int transW,
                     const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags);
 
+/* gaib_spmm_gemm / gaib_spmm_gemm2 over a bf16 table: d_in is [nc x len_in] bf16 bits (row-major, as gaib_spmm_bf16);
+ * d_agg, d_W, d_rows2, d_W2 and d_out are fp32.  flags: GAIB_RELU, GAIB_AGG_SCRATCH, GAIB_ACCUMULATE.
+ * d_agg (unless GAIB_AGG_SCRATCH) and d_out are BIT-IDENTICAL to gaib_spmm_gemm(2) called with the same arguments and options
+ * on the table widened to fp32 (gaib_cast_bf16_f32), for d_in 8-B aligned and d_agg 16-B aligned: the call takes the route
+ * the fp32 call would take on that table -- the fused kernel, two 128-column K-slabs, the neighbour product fused and the self
+ * term as an accumulating GEMM, ordered chunks + gaib_sgemm_ex on a dense graph, gaib_spmm_bf16 + gaib_sgemm_ex on a shape that
+ * does not fuse or with "spmm_fuse" = 0 -- and runs it with a bf16 gather (half the gathered bytes; widened exactly in
+ * registers, no fp32 copy of the table).  Partial sums, op(W), the product and all stores are fp32.
+ * A graph with a row map (a row class of a partition): GAIB_ERR_UNSUPPORTED; GAIB_OVERLAPS_TRANSFER: GAIB_ERR_INVALID
+ * (partitions aggregate fp32 tables).  A table of >= 4 GB in bf16 is gathered with 64-bit addresses. */
+int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                        const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
+                        int flags);
+int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                         const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                         const float* d_W2, int len_out, float* d_out, int flags);
+
 /* ---- dense update: matmul -> sgemm_gpu -> cublasSgemm (math_functions.cu:321-343) --------
  * row-major C[M x N] = op(A)[M x K] . op(B)[K x N]  (+ C if accum).  fp32 MFMA. */
 int gaib_sgemm(gaib_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K,
@@ -652,13 +669,15 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
 
 /* ---- tuning knobs (benchmarks only; defaults are what ships) ----
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
- * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16; GAT ignores it, a partitioned
- * graph refuses it); "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 = sub-wave rows of
- * 4 / 8 elements per lane.  Both readable with gaib_get_option. */
+ * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16 / gaib_spmm_gemm_bf16; GAT ignores
+ * it, a partitioned graph refuses it); "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
+ * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
+ * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
+ * kernel (row form, 8-row strip, buffer addressing, 65..128 columns): 0 = what ships, 16 / 32 = that depth.  Same bits. */
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
- * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout" */
+ * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

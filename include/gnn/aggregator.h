@@ -11,7 +11,7 @@ class aggregator {
  public:
   aggregator() : n(0), length(0), fuse_relu(false) {}
   // extension: bf16 feature tables (context option "agg_bf16" = 1, or GAIB_AGG_DTYPE=bf16): the GCN / SAGE aggregations
-  // cast their table into a bf16 scratch and gather from there (gaib_spmm_bf16; fp32 sums and output).  The scratch is
+  // cast their table into a bf16 scratch and gather from there (gaib_spmm_bf16, gaib_spmm_gemm_bf16 where the product rides along; fp32 sums and output).  The scratch is
   // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
   // epoch 0 eagerly).  GAT ignores the option; a partitioned graph (halo) refuses it.
   static bool bf16_tables();

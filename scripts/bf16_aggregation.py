@@ -6,6 +6,17 @@ SAGE 128 layer step (forward + backward + update) with the context option agg_bf
 2 B per gathered bf16 element.  Writes one JSON record (default profiles/bf16/bf16_aggregation.json).
 
     python scripts/bf16_aggregation.py [--scale 1.0] [--iters 5] [--out PATH]
+
+--fused: the fused aggregation + product over a bf16 table instead (default record profiles/bf16/bf16_fused.json).  After a
+bit check against gaib_spmm_gemm on the widened table, the legs of one group are timed INTERLEAVED -- one call of every leg per
+round, --iters rounds (at least 20) after warm-up -- so that box and clock state are shared; median, min and max per leg and
+the stream-copy rate before and after.  Groups: the call alone at 128 -> 128 and 256 -> 256 with the aggregate kept and as
+scratch (gaib_spmm_gemm_bf16 | the two-kernel route gaib_spmm_bf16 + gaib_sgemm_ex, which is that entry point under
+spmm_fuse = 0 | fp32 gaib_spmm_gemm), the gathers in flight of the headline variant (spmm_bf16_fuse_u = 16 | 32), and the GCN
+and SAGE layer steps at 128 and 256 (fp32 | bf16 tables | bf16 tables under spmm_fuse = 0: the route before the fused kernel
+had a bf16 form).
+
+    python scripts/bf16_aggregation.py --fused [--scale 1.0] [--iters 20] [--out PATH]
 """
 import argparse
 import json
@@ -34,12 +45,134 @@ def timeit(fn, iters, warmup=2):
     return ts[len(ts) // 2]
 
 
+def interleaved(legs, iters, warmup=3):
+    """legs: {name: (setup, fn)} -- setup() (options; not timed) then fn() between an event pair, one leg after the other,
+    `iters` rounds.  Returns {name: dict(median_ms, min_ms, max_ms, n)}."""
+    for setup, fn in legs.values():
+        setup()
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    evs = {k: [] for k in legs}
+    for _ in range(iters):
+        for k, (setup, fn) in legs.items():
+            setup()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            evs[k].append((a, b))
+    torch.cuda.synchronize()
+    res = {}
+    for k, pairs in evs.items():
+        ts = sorted(a.elapsed_time(b) for a, b in pairs)
+        res[k] = dict(median_ms=ts[len(ts) // 2], min_ms=ts[0], max_ms=ts[-1], n=len(ts))
+    return res
+
+
+def fused_main(args):
+    iters = max(args.iters, 20)
+    ctx = L.init(0)
+    sg = synth.make("ogbn-products", device="cuda", scale=args.scale)
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    ctx.sync()
+    nv, ne = g.nv, g.ne
+    copy0 = ctx.probe_stream_copy()
+    rec = dict(graph="ogbn-products synth", nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=copy0, calls=[], fuse_u=[], layers=[])
+    print(f"nv={nv} ne={ne} stream copy {copy0:.0f} GB/s", flush=True)
+
+    def opts(**kw):
+        def setup():
+            for k, v in kw.items():
+                ctx.set_option(k, v)
+        return setup
+
+    try:
+        for d in (128, 256):
+            x = torch.randn(nv, d, device="cuda")
+            xb = ctx.cast_f32_bf16(x)
+            xw = ctx.cast_bf16_f32(xb)
+            W = torch.randn(d, d, device="cuda") * 0.1
+            agg, out = torch.empty(nv, d, device="cuda"), torch.empty(nv, d, device="cuda")
+            agg_r, out_r = torch.empty(nv, d, device="cuda"), torch.empty(nv, d, device="cuda")
+            ctx.spmm_gemm(g, capi.W_GCN, xw, agg_r, W, out_r)
+            ctx.spmm_gemm_bf16(g, capi.W_GCN, xb, agg, W, out)
+            torch.cuda.synchronize()
+            same = torch.equal(out.view(torch.int32), out_r.view(torch.int32)) and torch.equal(agg.view(torch.int32), agg_r.view(torch.int32))
+            assert same, f"fused bf16 call differs from the fp32 call on the widened table at {d}"
+            del xw, agg_r, out_r
+            torch.cuda.empty_cache()
+            on, off = opts(spmm_fuse=1, spmm_bf16_fuse_u=0), opts(spmm_fuse=0, spmm_bf16_fuse_u=0)
+            legs = {}
+            for keep in (True, False):
+                kw = dict(agg_scratch=not keep)
+                tag = "keep" if keep else "scratch"
+                legs[f"bf16_fused_{tag}"] = (on, lambda kw=kw: ctx.spmm_gemm_bf16(g, capi.W_GCN, xb, agg, W, out, **kw))
+                legs[f"bf16_two_kernel_{tag}"] = (off, lambda kw=kw: ctx.spmm_gemm_bf16(g, capi.W_GCN, xb, agg, W, out, **kw))
+                legs[f"fp32_fused_{tag}"] = (on, lambda kw=kw: ctx.spmm_gemm(g, capi.W_GCN, x, agg, W, out, **kw))
+            r = dict(d=d, kind="W_GCN", bit_identical=True, legs=interleaved(legs, iters))
+            print(json.dumps(r), flush=True)
+            rec["calls"].append(r)
+            if d == 128:  # gathers in flight of the headline variant (row form, 8-row strip, buffer addressing, 8-B lanes)
+                for kind, kname in ((capi.W_MEAN, "W_MEAN"), (capi.W_GCN, "W_GCN")):
+                    legs = {f"u{u}": (opts(spmm_fuse=1, spmm_bf16_fuse_u=u),
+                                      lambda kind=kind: ctx.spmm_gemm_bf16(g, kind, xb, agg, W, out)) for u in (16, 32)}
+                    r = dict(d=d, kind=kname, legs=interleaved(legs, iters))
+                    print(json.dumps(r), flush=True)
+                    rec["fuse_u"].append(r)
+            del x, xb, W, agg, out
+            torch.cuda.empty_cache()
+
+        ctx.set_option("spmm_bf16_fuse_u", 0)
+        lg = L.LGraph.adopt(g)
+        for d in (128, 256):
+            for kind, name in ((L.GCN, "gcn"), (L.SAGE, "sage")):
+                layer = L.Layer(kind, 1, nv, d, d, lg, True)
+                layer.write(L.FEAT_IN, torch.randn(nv, d, device="cuda"))
+                gin = torch.randn(nv, d, device="cuda")
+                out, gout = torch.empty(nv, d, device="cuda"), torch.empty(nv, d, device="cuda")
+                opt = L.adam(0.01)
+                layer.write(L.GRAD_IN, gin)
+
+                def step():
+                    layer.forward(out)
+                    layer.backward(out, gout)
+                    layer.update_weight(opt)
+
+                legs = dict(fp32=(opts(agg_bf16=0, spmm_fuse=1), step), bf16_fused=(opts(agg_bf16=1, spmm_fuse=1), step),
+                            bf16_two_kernel=(opts(agg_bf16=1, spmm_fuse=0), step))
+                r = dict(layer=f"{name}_{d}_{d}", legs=interleaved(legs, iters))
+                b, f = r["legs"]["bf16_two_kernel"], r["legs"]["bf16_fused"]
+                r["gate_fused_below_baseline_by_more_than_its_spread"] = bool(b["median_ms"] - f["median_ms"] > b["max_ms"] - b["min_ms"])
+                print(json.dumps(r), flush=True)
+                rec["layers"].append(r)
+                L.adam_free(opt)
+                layer.close()
+                del gin, out, gout
+                torch.cuda.empty_cache()
+    finally:
+        for k, v in dict(agg_bf16=0, spmm_fuse=1, spmm_bf16_fuse_u=0).items():
+            ctx.set_option(k, v)
+    rec["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    out_path = Path(args.out) if args.out else ROOT / "profiles" / "bf16" / "bf16_fused.json"
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(rec, indent=1) + "\n")
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "bf16" / "bf16_aggregation.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--fused", action="store_true", help="the fused aggregation + product over a bf16 table (see above)")
     args = ap.parse_args()
+    if args.fused:
+        return fused_main(args)
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / "bf16" / "bf16_aggregation.json")
     ctx = L.init(0)  # the layer library's context: the layer steps below run on it too
     sg = synth.make("ogbn-products", device="cuda", scale=args.scale)
     g0 = ctx.graph(sg.rowptr, sg.colidx)
