@@ -54,6 +54,8 @@ SIGNATURES = {
     "gaib_scale_f32": (_i, [_vp, _i64, _f, _vp]),
     "gaib_cast_f32_bf16": (_i, [_vp, _i64, _vp, _vp]),
     "gaib_cast_bf16_f32": (_i, [_vp, _i64, _vp, _vp]),
+    "gaib_pack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
+    "gaib_unpack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "gaib_graph_create": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_create_rect": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_destroy": (_i, [_vp]),
@@ -76,6 +78,9 @@ SIGNATURES = {
     "gaib_spmm_gemm2": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_mh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i]),
     "gaib_spmm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "gaib_spmm_gemm_zs_route": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gaib_spmm_gemm_zs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "gaib_spmm_gemm2_zs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_gemm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "gaib_spmm_gemm2_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_graph_split_classes": (_i, [_vp, _vp, _vp, _pp, _pp, _pp, _pp, C.POINTER(_i64), C.POINTER(_i64), _i]),
@@ -551,6 +556,51 @@ class Context:
         _check(self.lib.gaib_spmm_gemm_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),
                                             1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm_bf16")
         return out
+
+    # ---- zero-suppressed tables (int32 tensors of [rows x 96] hold the packed rows) -----------
+    def pack_zs(self, x, out=None, overflow=None):
+        """gaib_pack_zs: x fp32 [rows x 128] -> [rows x 96] int32 (384-B rows); overflow: a 1-element int32 tensor the number
+        of over-capacity rows is added to"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+        if out is None:
+            out = torch.empty((x.shape[0], 96), dtype=torch.int32, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.int32 and out.numel() == x.shape[0] * 96
+        _check(self.lib.gaib_pack_zs(self.h, x.shape[0], x.shape[1], _ptr(x), _ptr(out), _ptr(overflow)), "gaib_pack_zs")
+        return out
+
+    def unpack_zs(self, zs, dense, out=None):
+        """gaib_unpack_zs: the inverse of pack_zs (dense: the table the image was made from, read for over-capacity rows)"""
+        import torch
+
+        assert zs.is_contiguous() and dense.is_contiguous() and dense.dtype == torch.float32
+        if out is None:
+            out = torch.empty_like(dense)
+        _check(self.lib.gaib_unpack_zs(self.h, dense.shape[0], dense.shape[1], _ptr(zs), _ptr(dense), _ptr(out)), "gaib_unpack_zs")
+        return out
+
+    def spmm_gemm_zs(self, g: "Graph", kind: int, x, zs, agg, W, out, transW: bool = False, relu: bool = False,
+                     agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None) -> bool:
+        """gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs: spmm_gemm gathering from zs = pack_zs(x).  False when the call has no packed
+        gather (GAIB_ERR_UNSUPPORTED, nothing touched): use spmm_gemm."""
+        assert x.is_contiguous() and zs.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
+        len_in, len_out = agg.shape[1], out.shape[1]
+        assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))
+        flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0)
+        if rows2 is not None:
+            assert rows2.is_contiguous() and W2.is_contiguous() and W2.shape == W.shape and rows2.shape[1] == len_in
+            rc = self.lib.gaib_spmm_gemm2_zs(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(zs), _ptr(agg), _ptr(W),
+                                             1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags)
+            what = "gaib_spmm_gemm2_zs"
+        else:
+            rc = self.lib.gaib_spmm_gemm_zs(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(zs), _ptr(agg), _ptr(W),
+                                            1 if transW else 0, len_out, _ptr(out), flags)
+            what = "gaib_spmm_gemm_zs"
+        if rc == -5:
+            return False
+        _check(rc, what)
+        return True
 
     def spmm_2t(self, g: "Graph", kind: int, x, x2, n_first: int, out, edge_w=None, accumulate: bool = False,
                 relu: bool = False):

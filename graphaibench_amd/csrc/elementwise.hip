@@ -7,6 +7,7 @@
 // masked_accuracy_single / l2norm / d_l2norm (src/utilities/math_functions.cu:12-14,
 // 114-146, 158-196, 242-268, 516-564, 749-761, 886-942) and adam::update_gpu
 // (src/utilities/optimizer.cu:5-36).
+#include <algorithm>
 #include "common.h"
 
 namespace {
@@ -555,6 +556,80 @@ __global__ __launch_bounds__(256) void cast_bf16_f32_kernel(int64_t n, const uin
   }
 }
 
+// ---- zero-suppressed tables (the gather side is RowGather<.., zs_t>, spmm_core.h) -----------------------------------------
+// A row of 128 floats -> 96 dwords on a 128-B boundary: M0 (bit l: column 2l holds anything but bit pattern 0), M1 (column 2l + 1),
+// then pairs: dword 4 + 2k is the k-th kept value of the even columns, dword 5 + 2k the k-th of the odd columns (as bits, in lane
+// order); the rest of the row is 0.  Only bit pattern 0x00000000 is suppressed (-0.0, NaN, inf and subnormals are values), so
+// unpacking reproduces the table bit for bit.  A row with more than ZS_CAP values in either half keeps its masks only: its
+// consumer reads the dense row.
+// One wave per row: one 8-B load per lane, two ballots, mbcnt positions; the row is put together in the wave's 384 B of LDS
+// (a wave's LDS operations complete in order) and leaves as one coalesced non-temporal store of three whole lines.
+constexpr int ZS_ROW_DW = 96;
+constexpr int ZS_CAP = 46;
+typedef unsigned zs_u2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256) void pack_zs_kernel(int64_t rows, const float* __restrict__ in, unsigned* __restrict__ out,
+                                                       unsigned* __restrict__ overflow) {
+  __shared__ __attribute__((aligned(16))) unsigned buf[4][ZS_ROW_DW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned* w = buf[wave];
+  unsigned over = 0;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
+    const zs_u2 x = __builtin_nontemporal_load(reinterpret_cast<const zs_u2*>(in + r * 128) + lane);
+    const bool b0 = x[0] != 0u, b1 = x[1] != 0u;
+    const unsigned long long m0 = __ballot(b0), m1 = __ballot(b1);
+    const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1);
+    const bool fits = n0 <= ZS_CAP && n1 <= ZS_CAP;  // wave-uniform
+    if (lane < ZS_ROW_DW / 2) {
+      zs_u2 z = {0u, 0u};
+      if (lane == 0) z = zs_u2{(unsigned)m0, (unsigned)(m0 >> 32)};
+      if (lane == 1) z = zs_u2{(unsigned)m1, (unsigned)(m1 >> 32)};
+      *reinterpret_cast<zs_u2*>(w + 2 * lane) = z;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (fits) {
+      const unsigned k0 = __builtin_amdgcn_mbcnt_hi((unsigned)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0, 0u));
+      const unsigned k1 = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u));
+      if (b0) w[4 + 2 * k0] = x[0];
+      if (b1) w[5 + 2 * k1] = x[1];
+    } else {
+      ++over;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < ZS_ROW_DW / 2) {
+      const zs_u2 o = *reinterpret_cast<const zs_u2*>(w + 2 * lane);
+      __builtin_nontemporal_store(o, reinterpret_cast<zs_u2*>(out + r * ZS_ROW_DW) + lane);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  if (overflow && over > 0 && lane == 0) atomicAdd(overflow, over);  // (a vector atomic, once per wave)
+}
+
+// (tests and tools: not on any hot path)
+__global__ __launch_bounds__(256) void unpack_zs_kernel(int64_t rows, const unsigned* __restrict__ zs, const float* __restrict__ dense,
+                                                         float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) unsigned buf[4][ZS_ROW_DW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned* w = buf[wave];
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
+    if (lane < ZS_ROW_DW / 2) *reinterpret_cast<zs_u2*>(w + 2 * lane) = reinterpret_cast<const zs_u2*>(zs + r * ZS_ROW_DW)[lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const unsigned long long m0 = ((unsigned long long)w[1] << 32) | w[0], m1 = ((unsigned long long)w[3] << 32) | w[2];
+    const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1);
+    zs_u2 v;
+    if (n0 > ZS_CAP || n1 > ZS_CAP) {
+      v = reinterpret_cast<const zs_u2*>(dense + r * 128)[lane];
+    } else {
+      const unsigned p0 = 4u + 2u * (unsigned)__builtin_popcountll(m0 & ((1ull << lane) - 1ull));
+      const unsigned p1 = 5u + 2u * (unsigned)__builtin_popcountll(m1 & ((1ull << lane) - 1ull));
+      v[0] = ((m0 >> lane) & 1ull) ? w[p0 < (unsigned)ZS_ROW_DW ? p0 : 0u] : 0u;
+      v[1] = ((m1 >> lane) & 1ull) ? w[p1 < (unsigned)ZS_ROW_DW ? p1 : 0u] : 0u;
+    }
+    reinterpret_cast<zs_u2*>(out + r * 128)[lane] = v;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+}
+
 }  // namespace
 
 extern "C" int gaib_fill_f32(gaib_ctx* ctx, int64_t n, float value, float* d_x) {
@@ -595,6 +670,39 @@ extern "C" int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in
   ProfScope ps(ctx, "cast_bf16_f32", 6.0 * (double)n);
   if (vec) cast_bf16_f32_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, ctx->stream>>>(n, d_in, d_out, 1);
   else cast_bf16_f32_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, d_in, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_pack_zs(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, void* d_zs, uint32_t* d_overflow) {
+  GAIB_CHECK(ctx && ((d_in && d_zs) || rows == 0), "gaib_pack_zs: NULL argument");
+  GAIB_CHECK(rows >= 0, "gaib_pack_zs: rows < 0");
+  if (len != 128) {
+    gaib_set_error("gaib_pack_zs: rows of %d columns (the zero-suppressed format holds rows of 128)", len);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return GAIB_OK;
+  GAIB_CHECK(((uintptr_t)d_in & 7) == 0 && ((uintptr_t)d_zs & 127) == 0, "gaib_pack_zs: the table must sit on an 8-B, the image on a 128-B boundary");
+  GAIB_CHECK((const void*)d_in != (const void*)d_zs, "gaib_pack_zs: in and out must not alias");
+  ProfScope ps(ctx, "pack_zs", (512.0 + 384.0) * (double)rows);
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(rows, 4), (int64_t)ctx->num_cus * 32);
+  pack_zs_kernel<<<grid, 256, 0, ctx->stream>>>(rows, d_in, static_cast<unsigned*>(d_zs), d_overflow);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_unpack_zs(gaib_ctx* ctx, int64_t rows, int len, const void* d_zs, const float* d_dense, float* d_out) {
+  GAIB_CHECK(ctx && ((d_zs && d_dense && d_out) || rows == 0), "gaib_unpack_zs: NULL argument");
+  GAIB_CHECK(rows >= 0, "gaib_unpack_zs: rows < 0");
+  if (len != 128) {
+    gaib_set_error("gaib_unpack_zs: rows of %d columns (the zero-suppressed format holds rows of 128)", len);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return GAIB_OK;
+  GAIB_CHECK((((uintptr_t)d_dense | (uintptr_t)d_out | (uintptr_t)d_zs) & 7) == 0, "gaib_unpack_zs: tables must sit on 8-B boundaries");
+  GAIB_CHECK(d_dense != d_out, "gaib_unpack_zs: dense and out must not alias");
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(rows, 4), (int64_t)ctx->num_cus * 32);
+  unpack_zs_kernel<<<grid, 256, 0, ctx->stream>>>(rows, static_cast<const unsigned*>(d_zs), d_dense, d_out);
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

@@ -67,6 +67,8 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_bf16_layout = 0;
   c->spmm_bf16_fuse_u = 0;
   c->agg_bf16 = 0;
+  c->agg_zs = 1;
+  c->agg_zs_paused = 0;
   c->sgemm_variant = 0;
   if (const char* e = getenv("GAIB_SGEMM_VARIANT")) c->sgemm_variant = atoi(e);  // (A/B of a whole trainer run: 61 = without sgemm_skinny.hip)
   c->gat_fast = 1;
@@ -524,6 +526,9 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_flat_ring")) *h_value = ctx->spmm_flat_ring;
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
+  else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
+  else if (!strcmp(key, "capturing")) *h_value = ctx->capturing;  // a recording is open (gaib_capture_begin)
+  else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
   else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
   else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
   else {
@@ -574,6 +579,12 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "agg_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->agg_bf16 = (int)value;
+  } else if (!strcmp(key, "agg_zs")) {
+    GAIB_CHECK(value == 0 || value == 1, "agg_zs must be 0 (dense gradient tables) or 1 (zero-suppressed)");
+    ctx->agg_zs = (int)value;
+  } else if (!strcmp(key, "agg_zs_paused")) {
+    GAIB_CHECK(value == 0 || value == 1, "agg_zs_paused must be 0 or 1");
+    ctx->agg_zs_paused = (int)value;
   }
   else if (!strcmp(key, "sgemm_variant"))
     ctx->sgemm_variant = (int)value;

@@ -343,6 +343,9 @@ int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_ar
 // ... and so do the fused kernels over a bf16 table: spmm_gemm_bf16.hip
 int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
                          int vec, int wmode);
+// ... and over a zero-suppressed table: spmm_gemm_zs.hip
+int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
+                       int wmode);
 
 static int spmm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                      const float* d_in, float* d_out, int flags, int heads = 1, const float* d_in2 = nullptr,
@@ -427,10 +430,13 @@ extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in
 // fp32 call would see for the same table widened -- the widened table sits at "twice the address" (a bf16 table aligned to 8 B
 // stands for an fp32 one aligned to 16), sizes and the chunk rule count fp32 bytes -- so both take the same route, and each route
 // runs with the bf16 gather: no fp32 copy of the table anywhere.
+// d_zs: the zero-suppressed image of d_in (gaib_pack_zs; gaib_spmm_gemm_zs).  Only the one-launch fused route over a whole graph
+// has such a gather (128 columns, buffer addressing, row forms): every other route is GAIB_ERR_UNSUPPORTED, decided on the dense
+// sizes before anything is launched.
 static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                           const float* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                           const float* d_W2, int len_out, float* d_out, int flags, const float* d_in2 = nullptr,
-                          int64_t n_first = 0, bool bf16 = false) {
+                          int64_t n_first = 0, bool bf16 = false, const void* d_zs = nullptr, bool zs_query = false) {
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm: NULL ctx/graph");
   GAIB_CHECK(len_in >= 0 && len_out >= 0, "gaib_spmm_gemm: negative length");
   GAIB_CHECK(ctx->device == g->device, "gaib_spmm_gemm: graph lives on device %d, ctx on %d", g->device,
@@ -458,6 +464,24 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
                         g->nv >= 1 &&
                         (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN ||
                          weight_kind == GAIB_W_MEAN_T || weight_kind == GAIB_W_EDGE);
+  if (d_zs) {
+    const int strip = shape_ok ? fuse_strip_rows(kpad, len_out, dual) : 0;
+    const int64_t dense_bytes = g->nc * (int64_t)len_in * 4;
+    bool ok = !part && len_in == 128 && strip == (dual ? 2 : 8) && dense_bytes < ((int64_t)1 << 32) && ctx->spmm_addr_mode != 2 &&
+              ((uintptr_t)d_zs & 127) == 0;
+    // the variants the dense call would pick for this graph and have no packed form (launch_fused's own predicates): the edge
+    // stream on short rows (20-34 % faster than the row form at 3-5 edges per row), the XCD-affine tile supply on a numbering
+    // with locality.  The caller gathers dense there.
+    if (ok && !dual && (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv))) ok = false;
+    if (ok && tile_xcd_arg(ctx, g) != 0) ok = false;
+    if (!ok) {
+      gaib_set_error("gaib_spmm_gemm_zs: no zero-suppressed gather for this call (whole graph, 128 columns, the one-launch fused route "
+                     "in its row form -- 8-row strip or two products, no edge stream, global tile counter --, table below 4 GB, "
+                     "buffer addressing, image on a 128-B boundary)");
+      return GAIB_ERR_UNSUPPORTED;
+    }
+    if (zs_query) return GAIB_OK;
+  }
   // two products whose matrices do not fit LDS together (SAGE's 100 -> 256 input layer): the neighbour product still
   // rides on the aggregation, the self term follows as an accumulating GEMM that also applies the activation
   // (whole graphs only: a row class of a partition -- row map, second feature table -- cannot take this route, the
@@ -589,6 +613,14 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   f.n_heavy = (int)g->n_heavy;
   if (part) return gaib_spmm_part_fused(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
   if (bf16) return gaib_spmm_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
+  if (d_zs) {  // gather from the packed rows; the dense table stays behind them for over-capacity rows
+    a.in2 = a.in;
+    a.in2_bytes = a.in_bytes;
+    a.in = static_cast<const float*>(d_zs);
+    a.ld = GAIB_ZS_ROW_BYTES / 4;
+    a.in_bytes = (uint32_t)(g->nc * (int64_t)GAIB_ZS_ROW_BYTES);
+    return gaib_spmm_fused_zs(ctx, g, &a, &f, hv, wmode);
+  }
   if (len_in <= 64) {
     return wmode == 0 ? launch_fused<1, 0>(ctx, g, a, f, hv) : launch_fused<1, 1>(ctx, g, a, f, hv);
   }
@@ -608,6 +640,36 @@ extern "C" int gaib_spmm_gemm2(gaib_ctx* ctx, gaib_graph* g, int weight_kind, co
   GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2: NULL second operand");
   return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out,
                         d_out, flags);
+}
+
+// Would gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs (d_rows2 != NULL) take this call?  GAIB_OK or GAIB_ERR_UNSUPPORTED from the route
+// information alone: nothing is launched, nothing is read through the pointers -- a caller asks BEFORE it packs.
+extern "C" int gaib_spmm_gemm_zs_route(gaib_ctx* ctx, gaib_graph* g, int weight_kind, int len_in, const float* d_in, const void* d_zs,
+                                       float* d_agg, const float* d_rows2, int len_out, float* d_out) {
+  GAIB_CHECK(d_zs, "gaib_spmm_gemm_zs_route: NULL packed table");
+  return spmm_gemm_impl(ctx, g, weight_kind, nullptr, len_in, d_in, d_agg, d_in, 1, d_rows2, d_rows2 ? d_in : nullptr, len_out, d_out,
+                        0, nullptr, 0, false, d_zs, true);
+}
+
+// agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]) gathering from the zero-suppressed image d_zs of d_in (gaib_pack_zs):
+// three lines per gathered row instead of four, d_agg (unless scratch) and d_out bit-identical to gaib_spmm_gemm(2) on d_in.
+extern "C" int gaib_spmm_gemm_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                 const float* d_in, const void* d_zs, float* d_agg, const float* d_W, int transW, int len_out,
+                                 float* d_out, int flags) {
+  GAIB_CHECK(d_zs, "gaib_spmm_gemm_zs: NULL packed table");
+  GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm_zs: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which gather dense tables");
+  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out, flags,
+                        nullptr, 0, false, d_zs);
+}
+
+extern "C" int gaib_spmm_gemm2_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                  const float* d_in, const void* d_zs, float* d_agg, const float* d_W, int transW,
+                                  const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(d_zs, "gaib_spmm_gemm2_zs: NULL packed table");
+  GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_zs: NULL second operand");
+  GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm2_zs: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which gather dense tables");
+  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags,
+                        nullptr, 0, false, d_zs);
 }
 
 extern "C" int gaib_spmm_gemm_2t(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,

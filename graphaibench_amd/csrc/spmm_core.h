@@ -148,6 +148,16 @@ __device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
   else return widen_bf16<VEC>(*reinterpret_cast<const typename Bf16Raw<VEC>::type*>(p));
 }
 
+// Zero-suppressed tables (E = zs_t; gaib_pack_zs, elementwise.hip): a row of 128 floats is 384 B on a 128-B boundary --
+//   dwords 0-1  M0: bit l set when column 2l holds anything but bit pattern 0        dwords 2-3  M1: the same for column 2l + 1
+//   dword 4 + 2k  the k-th kept value of the even columns (M0, in lane order)        dword 5 + 2k  the k-th of the odd columns (M1)
+// i.e. the 8-B load of lane 2 + k holds the k-th value of either half, which is what lets the gather find a lane's two values
+// with ONE cross-lane read each and no choice between a lane's two dwords (see widen_zs).  Either half holds up to GAIB_ZS_CAP
+// values; a row with more in one half keeps only its masks there and is read from the dense table.  Unpacking reproduces every bit.
+struct zs_t { uint32_t bits; };
+constexpr int GAIB_ZS_ROW_BYTES = 384;
+constexpr int GAIB_ZS_CAP = 46;
+
 // One feature-row gather.  BUF: `buffer_load_dwordxN v, voff, s[rsrc], soff offen` -- the row
 // base (col * row bytes) is a 32-bit SGPR offset against one descriptor for the whole table,
 // so a gather in flight costs only its VEC destination VGPRs (no 64-bit VGPR address pair).
@@ -158,11 +168,15 @@ __device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
 // PART: two tables -- column ids below n_first index `in`, the others `in2` (a rank's own rows and its halo table, which
 // live in different allocations); the choice is a scalar select on the (wave-uniform) column id.
 // E: element type of the table -- float, or uint16_t for a bf16 table (a.in then points at bf16 bits, a.ld counts
-// elements, a.in_bytes is the bf16 size; voff is a byte offset into such a row).
+// elements, a.in_bytes is the bf16 size; voff is a byte offset into such a row); or zs_t for a zero-suppressed table (a.in
+// then points at the packed rows, a.ld = 96, a.in_bytes is the packed size, and a.in2 / a.in2_bytes name the dense table the
+// packed one was made from; voff is the lane's byte offset into the DENSE row, 8 * lane).
 template <int VEC, int GM, bool PART = false, typename E = float>
 struct RowGather {
   static constexpr bool BUF = GM != 0;
-  static_assert(!PART || sizeof(E) == 4, "two-table gathers: fp32 tables only");
+  static constexpr bool ZS = std::is_same<E, zs_t>::value;
+  static_assert(!PART || (sizeof(E) == 4 && !ZS), "two-table gathers: fp32 tables only");
+  static_assert(!ZS || (VEC == 2 && GM == 1), "zero-suppressed tables: 8-byte lanes (128 columns), buffer addressing");
   __amdgpu_buffer_rsrc_t rsrc, rsrc2;
   const char *inb, *inb2;  // inb2 is biased by -n_first rows: row base = inb2 + col * ldb
   int64_t ldb;
@@ -176,14 +190,49 @@ struct RowGather {
       inb2 = reinterpret_cast<const char*>(a.in2) - (int64_t)a.n_first * ldb;
       if constexpr (BUF) rsrc2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.in2, 0, (int)a.in2_bytes, 0x00020000);
     }
+    if constexpr (ZS) rsrc2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.in2, 0, (int)a.in2_bytes, 0x00020000);  // the dense table
   }
   // What a gather leaves in registers until it is consumed: the fp32 vector itself, or the packed words of VEC bf16 elements
   // (half the registers).  load_raw() requests, widen() -- exact, bits << 16 -- belongs at the point of use: widened at the load,
   // the shifts sit between the loads of a batch and every gather in flight holds fp32-sized registers.
-  typedef typename std::conditional<sizeof(E) == 2, typename Bf16Raw<VEC>::type, typename VecT<VEC>::type>::type raw_t;
+  // A zero-suppressed gather is held as the two dwords the lane asked for (lanes 0 .. 47 cover the 384-B row).
+  typedef typename std::conditional<ZS, u2_t, typename std::conditional<sizeof(E) == 2, typename Bf16Raw<VEC>::type,
+                                                                           typename VecT<VEC>::type>::type>::type raw_t;
   static __device__ __forceinline__ typename VecT<VEC>::type widen(const raw_t& r) {
+    static_assert(!ZS, "zero-suppressed tables are expanded by widen_zs");
     if constexpr (sizeof(E) == 2) return widen_bf16<VEC>(r);
     else return r;
+  }
+  // Expansion of one zero-suppressed row where it is consumed.  Control flow is wave-uniform here and every lane is live: the masks
+  // come from lanes 0 and 1; a lane's even column is component 0 of lane 2 + (set bits of M0 below the lane), its odd column
+  // component 1 of lane 2 + (set bits of M1 below the lane) -- one ds_bpermute each (no LDS is allocated); suppressed columns are
+  // +0.0 by a select with the mask itself as its lane mask.  Per row: 4 readlane, 4 mbcnt, 2 shifts, 2 selects next to the dense
+  // loop's 2 multiplies and 2 adds.  A row with more than GAIB_ZS_CAP values in a half (wave-uniform test on the popcounts) holds
+  // only its masks: it is read from the dense table, 512 B per row, and waited for.
+  // (cvec / idx: the wave's column ids and the lane that holds this row's -- read only on the over-capacity path)
+  __device__ __forceinline__ typename VecT<VEC>::type widen_zs(const raw_t& r, uint32_t cvec, int idx, uint32_t voff) const {
+    typedef unsigned long long u64;
+    const u64 m0 = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 0);
+    const u64 m1 = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 1) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 1);
+    typename VecT<VEC>::type v;
+    if (__builtin_expect(__builtin_popcountll(m0) > GAIB_ZS_CAP || __builtin_popcountll(m1) > GAIB_ZS_CAP, 0)) {
+      const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cvec, idx);
+      const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * 512u), 0);
+      v[0] = __uint_as_float(d[0]);
+      v[1] = __uint_as_float(d[1]);
+      return v;
+    }
+    const uint32_t l0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 2u));
+    const uint32_t l1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 2u));
+    const uint32_t x0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l0 << 2), (int)r[0]);
+    const uint32_t x1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l1 << 2), (int)r[1]);
+    // the zero fill, written out: from `(m >> lane) & 1` the compiler builds a 64-bit shift, two ands and a 64-bit compare per value
+    uint32_t k0, k1;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k0) : "v"(x0), "s"(m0));
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k1) : "v"(x1), "s"(m1));
+    v[0] = __uint_as_float(k0);
+    v[1] = __uint_as_float(k1);
+    return v;
   }
   __device__ __forceinline__ typename VecT<VEC>::type load(uint32_t cj, uint32_t voff) const { return widen(load_raw(cj, voff)); }
   __device__ __forceinline__ raw_t load_raw(uint32_t cj, uint32_t voff) const {
@@ -204,6 +253,10 @@ struct RowGather {
       return load_buf<0>(c, voff);
     } else if constexpr (GM == 2) {
       return load_buf<2>(cj, voff);
+    } else if constexpr (ZS) {
+      // lanes 48 .. 63 ask for offset 0 as out-of-range lanes do: exactly the row's three lines, whatever its header says
+      return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(voff < (uint32_t)GAIB_ZS_ROW_BYTES ? voff : 0u),
+                                                  (int)(cj * (uint32_t)GAIB_ZS_ROW_BYTES), 0);
     } else if constexpr (GM == 1) {
       return load_buf<0>(cj, voff);
     } else {
@@ -256,7 +309,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
                                                 const uint32_t (&voff)[CT],
                                                 typename VecT<VEC>::type (&acc)[CT], uint32_t c_first = 0u,
                                                 float w_first = 0.f) {
-  static_assert(sizeof(E) == 4 || WMODE < 3, "bf16 tables: single-head weights");
+  static_assert((sizeof(E) == 4 && !std::is_same<E, zs_t>::value) || WMODE < 3, "bf16 and zero-suppressed tables: single-head weights");
   typedef RowGather<VEC, BUF, PART, E> gather_t;
   const gather_t gather(a);
   typename gather_t::raw_t x[U][CT];  // gather destinations (bf16: packed words, widened where consumed); the tail's piece p lives in x[p .. 2p-1]
@@ -299,7 +352,10 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
         for (int ct = 0; ct < CT; ++ct) {
           float wsel = wj;
           if constexpr (MH) wsel = wv[u][ct];
-          vacc<VEC>(acc[ct], wsel, gather_t::widen(x[u][ct]));
+          if constexpr (gather_t::ZS)
+            vacc<VEC>(acc[ct], wsel, gather.widen_zs(x[u][ct], c, j + u, voff[ct]));
+          else
+            vacc<VEC>(acc[ct], wsel, gather_t::widen(x[u][ct]));
         }
       }
     }
@@ -333,7 +389,10 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
               // (the tail is short: its per-head weights are fetched at the point of use)
               float wh = wj;
               if constexpr (MH) wh = load_edge_w<WMODE>(a, base + jj + u, hd[ct]);
-              vacc<VEC>(acc[ct], wh, gather_t::widen(x[p + u][ct]));
+              if constexpr (gather_t::ZS)
+                vacc<VEC>(acc[ct], wh, gather.widen_zs(x[p + u][ct], c, jj + u, voff[ct]));
+              else
+                vacc<VEC>(acc[ct], wh, gather_t::widen(x[p + u][ct]));
             }
           }
           jj += p;

@@ -1,0 +1,70 @@
+// spmm_gemm_zs.hip -- the fused aggregation + dense product of spmm_kernels.h (spmm_gemm_kernel, spmm_heavy_kernel)
+// instantiated for zero-suppressed feature tables (E = zs_t, spmm_core.h; packed by gaib_pack_zs), whole graphs only:
+//   agg[i,:] = sum_e w_e * unpack(zs[col_e,:]) ;  y[i,:] = act(agg[i,:] . op(W) [+ rows2[i,:] . op(W2)])
+// A relu-masked gradient is about half +0.0: packed, a row of 128 floats is three 128-B lines instead of four, and the
+// aggregation's time follows the lines a gathered row touches.  Only the gather differs from the fp32 instantiations of spmm.hip:
+// a row in flight is the two dwords a lane asked for, expanded with cross-lane permutes where it is consumed (RowGather::widen_zs);
+// suppressed columns enter as +0.0, so every product w * x and every addition of the fp32 kernels is still made, in the same
+// order: agg and y are bit-identical to gaib_spmm_gemm(2) on the dense table.
+// Row forms only (8-row strip, or the 2-row strip with two products), per-row and per-edge weights, buffer addressing; the
+// edge-stream forms, the XCD-affine tile supply, K-slabs, partitions and 64-bit addressing have no packed gather: where the dense
+// call would take one of them (short rows, a numbering with locality), spmm_gemm_impl (spmm.hip) refuses and the caller gathers
+// dense.
+// No reference counterpart (the reference aggregates dense fp32 tables: include/gnn/graph_operations.h:8-178).
+#include "spmm_kernels.h"
+
+namespace {
+
+template <int WMODE>
+int launch_fused_zs(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
+  constexpr int U = 16;
+  constexpr int K = 128;
+  if (g->n_heavy > 0) {
+    SpmmArgs h = a;
+    h.row_list = g->heavy_rows;
+    h.row_order = g->heavy_rows + g->n_heavy;
+    h.out = heavy_scratch;
+    h.compact = 1;
+    h.relu = 0;
+    h.accumulate = 0;
+    const size_t lds = sizeof(float) * HEAVY_WAVES * K;
+    // (bytes and flops are priced on the dense formula under the dense keys: a work rate in dense bytes)
+    ProfScope ps(ctx, "spmm_heavy", gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1),
+                 2.0 * g->heavy_edges * a.ncols, a.ncols);
+    spmm_heavy_kernel<2, 1, WMODE, U, 1, false, zs_t><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    GAIB_LAUNCH_CHECK();
+  }
+  f.tile_xcd = 0;
+  const bool dual = f.wt2 != nullptr;
+  const int strip = dual ? 2 : 8;  // (checked by spmm_gemm_impl)
+  const size_t lds = fuse_lds_bytes(K, f.n_out, dual, strip);
+  const int64_t ntiles = cdiv64(a.n_rows, FUSE_ROWS);
+  const int cus = ctx->spmm_fuse_cus > 0 ? ctx->spmm_fuse_cus : ctx->num_cus;
+  const unsigned grid = (unsigned)std::min<int64_t>(cus, cdiv64(ntiles, FUSE_WAVES));
+  GAIB_HIP(hipMemsetAsync(f.tile_counter, 0, 8 * sizeof(int), ctx->stream));
+  const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_all = (double)a.n_rows;
+  const double fused_bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (dual ? 1 : 0)) +
+                             r_all * 4.0 * f.n_out;
+  const double fused_flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (dual ? 2 : 1);
+  ProfScope ps(ctx, "spmm_gemm_fused", fused_bytes, fused_flops, a.ncols);
+  if (dual) {
+    auto kern = spmm_gemm_kernel<2, WMODE, U, 1, 2, true, false, false, false, false, false, false, zs_t>;
+    GAIB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    kern<<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+  } else {
+    auto kern = spmm_gemm_kernel<2, WMODE, U, 1, 8, false, false, false, false, false, false, false, zs_t>;
+    GAIB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    kern<<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+  }
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+}  // namespace
+
+int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
+                       int wmode) {
+  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
+  const FuseArgs& f = *static_cast<const FuseArgs*>(fuse_args);
+  return wmode == 0 ? launch_fused_zs<0>(ctx, g, a, f, heavy_scratch) : launch_fused_zs<1>(ctx, g, a, f, heavy_scratch);
+}

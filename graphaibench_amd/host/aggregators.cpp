@@ -56,6 +56,101 @@ static void no_bf16_halo(Graph& g) {
   exit(EXIT_FAILURE);
 }
 
+// ---- zero-suppressed gradient tables (option agg_zs) ---------------------------------------------------------------------
+// Where the packed launch set (pack + heavy + fused) stops beating the dense one: the share of rows over capacity from which
+// the layers gather dense.  An over-capacity row costs a dense 512-B gather that the wave waits for on top of its packed one.
+// scripts/zs_aggregation.py sweeps the kept share of the gradient from 40 to 90 % on the products-shaped graph
+// (profiles/zs/zs_aggregation.json): packed wins by 0.32 ms at 50 % kept (0.02 % of the rows over capacity), by 0.10 ms at 60 %
+// (3.5 %), loses 3.8 ms at 70 % (55 %) -- about 6.3 ms per unit share, so the two sets cross at 5 % of the rows.
+static const double ZS_GUARD_SHARE = 0.05;
+static const unsigned ZS_PROBE_EVERY = 8;
+// Two products (SAGE's backward: the self term rides along, the 2-row-strip kernel at 128 VGPRs with 8-9 spilled): the packed
+// kernels exist and are bit-identical (gaib_spmm_gemm2_zs), but the layers take them only once they are MEASURED faster than the
+// dense call on the SAGE step -- until then SAGE gathers dense (LEDGER 10.3).
+static const bool ZS_TWO_PRODUCTS = false;
+bool aggregator::zs_tables() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs", &v));
+  return v != 0;
+}
+bool aggregator::zs_paused() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs_paused", &v));
+  return v != 0;
+}
+// The guard's state is kept PER GATHERED TABLE (the layer's grad_in buffer): in a model, the count one layer's pack left behind
+// says nothing about the next layer's gradient.  Each table has its own device counter and pinned host word.
+static const int ZS_SLOTS = 16;  // tables watched at a time (a deeper model shares slots round robin: counts then mix)
+struct ZsWatch {
+  const float* table = nullptr;
+  size_t counted_rows = 0;  // rows of the pack the slot's count belongs to (0: no pack yet)
+  bool paused = false;
+  unsigned since_probe = 0;
+};
+static struct {
+  gaib_ctx* ctx = nullptr;
+  void* tab = nullptr;  // [cap_rows x 384 B]
+  size_t cap_rows = 0;
+  uint32_t* d_over = nullptr;           // [ZS_SLOTS] the packs' counts of over-capacity rows ...
+  volatile uint32_t* h_over = nullptr;  // [ZS_SLOTS] ... read back into pinned memory behind every pack
+  ZsWatch watch[ZS_SLOTS];
+  int n_watch = 0, next_evict = 0;
+  std::vector<void*> retired;  // (a recorded epoch may still name a buffer that had to grow)
+} g_zs;
+static void* zs_table(size_t rows) {
+  if (g_zs.ctx != C()) {  // a new process context: start over on its device (the old context's buffers went with it)
+    if (g_zs.h_over) GAIB_OR_DIE(gaib_host_free(C(), const_cast<uint32_t*>(g_zs.h_over)));
+    g_zs.retired.clear();
+    g_zs.tab = nullptr;
+    g_zs.cap_rows = 0;
+    g_zs.ctx = C();
+    g_zs.n_watch = g_zs.next_evict = 0;
+    GAIB_OR_DIE(gaib_malloc(C(), sizeof(uint32_t) * ZS_SLOTS, (void**)&g_zs.d_over));
+    void* h = nullptr;
+    GAIB_OR_DIE(gaib_host_alloc(C(), sizeof(uint32_t) * ZS_SLOTS, &h));
+    g_zs.h_over = static_cast<volatile uint32_t*>(h);
+    for (int i = 0; i < ZS_SLOTS; i++) g_zs.h_over[i] = 0;
+  }
+  if (rows > g_zs.cap_rows) {
+    if (g_zs.tab) g_zs.retired.push_back(g_zs.tab);
+    g_zs.tab = nullptr;
+    g_zs.cap_rows = 0;
+    // (inside a capture gaib_malloc refuses: the run has to reserve the scratch before it records)
+    GAIB_OR_DIE(gaib_malloc(C(), rows * (size_t)384, &g_zs.tab));
+    g_zs.cap_rows = rows;
+  }
+  return g_zs.tab;
+}
+static int zs_slot(const float* table) {
+  for (int i = 0; i < g_zs.n_watch; i++)
+    if (g_zs.watch[i].table == table) return i;
+  int i;
+  if (g_zs.n_watch < ZS_SLOTS) i = g_zs.n_watch++;
+  else i = g_zs.next_evict++ % ZS_SLOTS;
+  g_zs.watch[i] = ZsWatch();
+  g_zs.watch[i].table = table;
+  return i;
+}
+// pack `rows` x 128 floats at `in` into the scratch; the count of over-capacity rows follows into the slot's pinned word
+static const void* zs_pack(int slot, size_t rows, const float* in) {
+  void* t = zs_table(rows);
+  GAIB_OR_DIE(gaib_fill_f32(C(), 1, 0.f, reinterpret_cast<float*>(g_zs.d_over + slot)));
+  GAIB_OR_DIE(gaib_pack_zs(C(), (int64_t)rows, 128, in, t, g_zs.d_over + slot));
+  GAIB_OR_DIE(gaib_memcpy_d2h_async(C(), const_cast<uint32_t*>(g_zs.h_over + slot), g_zs.d_over + slot, sizeof(uint32_t)));
+  g_zs.watch[slot].counted_rows = rows;
+  return t;
+}
+// ("agg_zs_paused" reads 1 while ANY watched table is gathered dense by the guard)
+static void zs_set_paused(int slot, bool p) {
+  ZsWatch& w = g_zs.watch[slot];
+  if (p == w.paused) return;
+  w.paused = p;
+  w.since_probe = 0;
+  bool any = false;
+  for (int i = 0; i < g_zs.n_watch; i++) any = any || g_zs.watch[i].paused;
+  GAIB_OR_DIE(gaib_set_option(C(), "agg_zs_paused", any ? 1 : 0));
+}
+
 // The halo-column half of a partitioned aggregation over `whole` (the mode's halo-column graph): in one pass after the whole
 // exchange -- last(whole, table) --, or, where the exchange travels in K > 1 time slices (gaib_halo_set_pieces), piece by piece
 // as the slices land: plain(piece k, table) in accumulate mode for every piece but the last non-empty one, which takes last()
@@ -126,7 +221,7 @@ static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* 
 
 void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float* in, float* agg, bool keep_agg,
                                        const float* W, bool transW, int len_out, float* out, bool relu,
-                                       const float* rows2, const float* W2) {
+                                       const float* rows2, const float* W2, bool relu_masked) {
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
   if (bf16_tables()) {
@@ -195,6 +290,40 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
               [&](gaib_graph* gh, const float* halo) { fused(gh, halo, flags | GAIB_ACCUMULATE); });
     return;
   }
+  if (relu_masked && len == 128 && (!rows2 || ZS_TWO_PRODUCTS) && zs_tables()) {
+    gaib_graph* dg = dev(g);
+    const size_t rows = (size_t)gaib_graph_nc(dg);
+    int64_t capturing = 0;
+    GAIB_OR_DIE(gaib_get_option(C(), "capturing", &capturing));
+    if (g_zs.ctx != C()) zs_table(0);
+    // is there a packed route for this call?  Asked from the route information alone, before anything is packed or allocated (a
+    // graph of short rows, a numbering with locality, a dense graph the ordered chunks take, a table of 4 GB: the dense call's
+    // variants).  The query reads nothing through the image pointer: any 128-B aligned address stands for it.
+    int route = gaib_spmm_gemm_zs_route(C(), dg, kind, len, in, g_zs.d_over, agg, rows2, len_out, out);
+    if (route != GAIB_OK && route != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(route);
+    if (route == GAIB_OK && rows > g_zs.cap_rows) {
+      if (capturing) route = GAIB_ERR_UNSUPPORTED;  // (a recording that would have to grow the scratch: dense)
+      else zs_table(rows);
+    }
+    if (route == GAIB_OK) {
+      const int slot = zs_slot(in);
+      ZsWatch& w = g_zs.watch[slot];
+      // the guard looks at the count this table's last finished pack left behind (no synchronisation: a past step's value)
+      if (w.counted_rows > 0) zs_set_paused(slot, (double)g_zs.h_over[slot] > ZS_GUARD_SHARE * (double)w.counted_rows);
+      if (w.paused) {
+        // a look at the count every ZS_PROBE_EVERY-th call -- never inside a recording: a recorded epoch of a paused table
+        // gathers dense and packs nothing, whatever the call count was when it was recorded
+        if (!capturing && ++w.since_probe % ZS_PROBE_EVERY == 0) zs_pack(slot, rows, in);
+      } else {
+        const void* tab = zs_pack(slot, rows, in);
+        if (rows2)
+          GAIB_OR_DIE(gaib_spmm_gemm2_zs(C(), dg, kind, NULL, len, in, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, flags));
+        else
+          GAIB_OR_DIE(gaib_spmm_gemm_zs(C(), dg, kind, NULL, len, in, tab, agg, W, transW ? 1 : 0, len_out, out, flags));
+        return;
+      }
+    }
+  }
   fused(dev(g), in, flags);
 }
 
@@ -204,8 +333,8 @@ void GCN_Aggregator::aggregate_matmul(int len, Graph& g, const float* in, float*
   aggregate_then_matmul(GAIB_W_GCN, len, g, in, agg, keep_agg, W, transW, len_out, out, relu);
 }
 void GCN_Aggregator::d_aggregate_matmul(int len, Graph& g, const float* grad_in, float* agg, bool keep_agg,
-                                        const float* W, bool transW, int len_out, float* out) {
-  aggregate_then_matmul(GAIB_W_GCN, len, g, grad_in, agg, keep_agg, W, transW, len_out, out, false);
+                                        const float* W, bool transW, int len_out, float* out, bool relu_masked) {
+  aggregate_then_matmul(GAIB_W_GCN, len, g, grad_in, agg, keep_agg, W, transW, len_out, out, false, NULL, NULL, relu_masked);
 }
 void SAGE_Aggregator::aggregate_matmul(int len, Graph& g, const float* in, float* agg, bool keep_agg,
                                        const float* W, bool transW, int len_out, float* out, bool relu,
@@ -214,9 +343,9 @@ void SAGE_Aggregator::aggregate_matmul(int len, Graph& g, const float* in, float
 }
 void SAGE_Aggregator::d_aggregate_matmul(int len, Graph& g, const float* grad_in, float* agg, bool keep_agg,
                                          const float* W, bool transW, int len_out, float* out,
-                                         const float* rows_self, const float* W_self) {
+                                         const float* rows_self, const float* W_self, bool relu_masked) {
   aggregate_then_matmul(GAIB_W_MEAN_T, len, g, grad_in, agg, keep_agg, W, transW, len_out, out, false, rows_self,
-                        W_self);
+                        W_self, relu_masked);
 }
 void GCN_Aggregator::init(int l, int nv, int, float, float) {
   length = l;

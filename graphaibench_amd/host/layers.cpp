@@ -142,7 +142,8 @@ void GCN_layer::backward(float* feat_out, float* grad_out) {
       if (y == z) {
         // A.(g.W^T) == (A.g).W^T: at equal widths the aggregation goes first and carries the product
         // (the reference order would cost a separate GEMM pass; same result up to summation order)
-        aggr.d_aggregate_matmul(z, *graph, grad_in, d_in_temp, false, d_W_neigh, true, y, grad_out);
+        // (a relu layer's gradient is about half +0.0 now: the aggregation may gather it zero-suppressed, aggregator::zs_tables)
+        aggr.d_aggregate_matmul(z, *graph, grad_in, d_in_temp, false, d_W_neigh, true, y, grad_out, is_act);
       } else {
         matmul(x, y, z, grad_in, d_W_neigh, d_in_temp, false, true);
         aggr.d_aggregate(y, *graph, NULL, d_in_temp, grad_out);
@@ -201,7 +202,7 @@ void SAGE_layer::backward(float* feat_out, float* grad_out) {
     matmul(y, z, x, d_in_temp1, grad_in, d_W_neigh_grad, true, false);
     if (level_ > 0) {
       if (y == z) {  // (M^T g).W^T instead of M^T (g.W^T): the products ride on the aggregation
-        aggr.d_aggregate_matmul(z, *graph, grad_in, d_in_temp, false, d_W_neigh, true, y, grad_out, grad_in, d_W_self);
+        aggr.d_aggregate_matmul(z, *graph, grad_in, d_in_temp, false, d_W_neigh, true, y, grad_out, grad_in, d_W_self, is_act);
       } else {
         matmul(x, y, z, grad_in, d_W_neigh, d_in_temp, false, true);
         aggr.d_aggregate(y, *graph, NULL, d_in_temp, grad_out);

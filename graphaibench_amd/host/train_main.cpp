@@ -204,6 +204,8 @@ struct Trainer {
     if (root())
       std::cout << "aggregation tables: " << (bf16 ? (ARCH == gnn_arch::GAT ? "fp32 (bf16 asked; GAT gathers fp32)" : "bf16") : "fp32")
                 << "\n";
+    if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root())
+      std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
     if (bf16 && world > 1) {
       std::cerr << "GAIB_AGG_DTYPE=bf16 runs on one GPU only (a partitioned run gathers fp32 tables)\n";
       exit(EXIT_FAILURE);

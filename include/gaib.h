@@ -112,6 +112,17 @@ int gaib_scale_f32(gaib_ctx* ctx, int64_t n, float alpha, float* d_x);
 int gaib_cast_f32_bf16(gaib_ctx* ctx, int64_t n, const float* d_in, uint16_t* d_out);
 int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in, float* d_out);
 
+/* Zero-suppressed tables ("zs"): a row of 128 floats as 384 bytes on a 128-byte boundary -- two 64-bit masks (M0: bit l set when
+ * column 2l holds anything but bit pattern 0x00000000; M1: the same for column 2l + 1), then pairs of fp32 bit patterns: dword
+ * 4 + 2k is the k-th kept value of the even columns, dword 5 + 2k the k-th of the odd columns; the rest of the row is 0.  -0.0,
+ * NaN, inf and subnormals are kept, so unpacking reproduces every bit.  Either half holds up to 46 values: a row with more in
+ * one half keeps only its masks and is read from the dense table, which stays valid.
+ * gaib_pack_zs: d_in [rows x 128] fp32 (8-B aligned) -> d_zs [rows x 384 B] (128-B aligned); d_overflow (may be NULL): a device
+ * word the number of over-capacity rows is ADDED to.  gaib_unpack_zs: the inverse, d_dense being the table the image was made
+ * from (read for over-capacity rows only).  len != 128: GAIB_ERR_UNSUPPORTED. */
+int gaib_pack_zs(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, void* d_zs, uint32_t* d_overflow);
+int gaib_unpack_zs(gaib_ctx* ctx, int64_t rows, int len, const void* d_zs, const float* d_dense, float* d_out);
+
 /* ---- graph: LearningGraph's device half (include/gnn/lgraph.h:20-277) ------------------
  * gaib_graph_create  = alloc_on_device + copy_to_gpu (src/gnn/lgraph.cu:51-92).
  *   rowptr: nv+1 entries of `rowptr_bits` (32: index_t as LearningGraph holds it; 64: as
@@ -429,6 +440,25 @@ int gaib_spmm_gemm2(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* 
  * registers, no fp32 copy of the table).  Partial sums, op(W), the product and all stores are fp32.
  * A graph with a row map (a row class of a partition): GAIB_ERR_UNSUPPORTED; GAIB_OVERLAPS_TRANSFER: GAIB_ERR_INVALID
  * (partitions aggregate fp32 tables).  A table of >= 4 GB in bf16 is gathered with 64-bit addresses. */
+/* gaib_spmm_gemm / gaib_spmm_gemm2 gathering from the zero-suppressed image d_zs of d_in (gaib_pack_zs over the same g->nc rows):
+ * three 128-byte lines per gathered row instead of four.  Masked columns enter every row sum as w * (+0.0), in the order of the
+ * dense call: d_agg (unless GAIB_AGG_SCRATCH) and d_out are bit-identical to gaib_spmm_gemm(2) on d_in, which stays the source of
+ * over-capacity rows.  Covers the one-launch fused route of a whole graph: len_in == 128, GCN / MEAN / MEAN_T / single-head EDGE
+ * weights, op(W) in LDS beside 8-row strips (one product) or two products that fit LDS together, a table below 4 GB, "spmm_addr_mode" != 2,
+ * and a graph the dense call runs in its row form off the global tile counter (not the edge stream of short rows -- fewer than 12
+ * edges per row, or "spmm_flat" = 1 --, not the XCD-affine supply of a numbering with locality).  Anything
+ * else -- another width, a graph with a row map, a dense graph the ordered chunks would take, "spmm_fuse" = 0 -- returns
+ * GAIB_ERR_UNSUPPORTED before anything is launched: call the dense function. */
+/* gaib_spmm_gemm_zs_route: would the packed call (two products when d_rows2 != NULL) be taken?  GAIB_OK or GAIB_ERR_UNSUPPORTED
+ * from the route information alone -- nothing is launched or read: ask before packing. */
+int gaib_spmm_gemm_zs_route(gaib_ctx* ctx, gaib_graph* g, int weight_kind, int len_in, const float* d_in, const void* d_zs,
+                            float* d_agg, const float* d_rows2, int len_out, float* d_out);
+int gaib_spmm_gemm_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, const float* d_in,
+                      const void* d_zs, float* d_agg, const float* d_W, int transW, int len_out, float* d_out, int flags);
+int gaib_spmm_gemm2_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, const float* d_in,
+                       const void* d_zs, float* d_agg, const float* d_W, int transW, const float* d_rows2, const float* d_W2,
+                       int len_out, float* d_out, int flags);
+
 int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                         const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
                         int flags);
@@ -668,6 +698,11 @@ int gaib_probe_stream_copy(gaib_ctx* ctx, size_t bytes, int iters, double* h_gbs
 int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int bidir, double* h_gbs);
 
 /* ---- tuning knobs (benchmarks only; defaults are what ships) ----
+ * "agg_zs" (default 1): 1 = the layer library's GCN backward pass gathers a relu-masked gradient of 128 columns from its
+ * zero-suppressed image (gaib_pack_zs + gaib_spmm_gemm_zs: three lines per gathered row instead of four, the same bits); off
+ * under "agg_bf16", on a partitioned graph, at other widths, on graphs without a packed route (gaib_spmm_gemm_zs_route), and for
+ * SAGE's two-product backward until that form is measured faster than the dense one.  "agg_zs_paused" (readable; written by that library): 1 while
+ * its guard gathers dense because too many rows of the gradient are over the packed row's capacity.
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
  * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16 / gaib_spmm_gemm_bf16; GAT ignores
  * it, a partitioned graph refuses it); "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
@@ -677,7 +712,8 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
- * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u" */
+ * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
+ * "agg_zs", "agg_zs_paused", "capturing" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

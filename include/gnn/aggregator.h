@@ -15,6 +15,15 @@ class aggregator {
   // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
   // epoch 0 eagerly).  GAT ignores the option; a partitioned graph (halo) refuses it.
   static bool bf16_tables();
+  // extension: zero-suppressed gradient tables (context option "agg_zs", default 1).  The backward aggregation of a layer with
+  // a relu gathers a table that is about half +0.0 (the d_relu has just masked it): aggregate_then_matmul packs such a table
+  // of 128 columns into a process-wide scratch (gaib_pack_zs) and gathers from there (gaib_spmm_gemm_zs: the same bits).  The
+  // scratch is allocated on first use, outside a capture, like the bf16 one.  Guard: the pack counts the rows over capacity
+  // into a pinned host word that is read WITHOUT synchronising (a past step's value); above ZS_GUARD_SHARE of the rows the
+  // aggregation gathers dense, packing every ZS_PROBE_EVERY-th call only to look at the count again (never inside a recording).
+  // The guard's state is kept per gathered table.  Calls with a second product (SAGE) gather dense for now (ZS_TWO_PRODUCTS).
+  static bool zs_tables();
+  static bool zs_paused();
   void set_vlen(int vlen) { length = vlen; }
   // extension: the next aggregate() call clamps its output at 0 (the layer's relu_gpu fused
   // into the aggregation's store); cleared by that call
@@ -30,9 +39,10 @@ class aggregator {
   // lets the kernel skip the store of agg (still needs the buffer).  On a partitioned graph (halo exchange)
   // it runs as aggregation + matmul.
   // rows2 / W2 (both or neither): + rows2 . op(W2) in the same store (the self term of a SAGE layer)
+  // relu_masked: `in` is a gradient the layer's d_relu has masked (see zs_tables)
   void aggregate_then_matmul(int kind, int len, Graph& g, const float* in, float* agg, bool keep_agg,
                              const float* W, bool transW, int len_out, float* out, bool relu,
-                             const float* rows2 = NULL, const float* W2 = NULL);
+                             const float* rows2 = NULL, const float* W2 = NULL, bool relu_masked = false);
 
   int n;
   int length;  // feature vector length
@@ -49,7 +59,7 @@ class GCN_Aggregator : public aggregator {
   void aggregate_matmul(int len, Graph& g, const float* in, float* agg, bool keep_agg, const float* W,
                         bool transW, int len_out, float* out, bool relu);
   void d_aggregate_matmul(int len, Graph& g, const float* grad_in, float* agg, bool keep_agg, const float* W,
-                          bool transW, int len_out, float* out);
+                          bool transW, int len_out, float* out, bool relu_masked = false);
 };
 
 // forward: mean over neighbours (1/deg(i)); backward: its transpose (1/deg(col_e))
@@ -64,7 +74,7 @@ class SAGE_Aggregator : public aggregator {
                         const float* W_self = NULL);
   void d_aggregate_matmul(int len, Graph& g, const float* grad_in, float* agg, bool keep_agg, const float* W,
                           bool transW, int len_out, float* out, const float* rows_self = NULL,
-                          const float* W_self = NULL);
+                          const float* W_self = NULL, bool relu_masked = false);
 };
 
 // single-head attention: p = softmax_row(leaky_relu_0.2(a_l.h_i + a_r.h_j)); out = P h.

@@ -176,6 +176,36 @@ def wide_row_aggregation(res):
     return out
 
 
+def zs_lines(res):
+    """The packed backward launch set of a relu layer: gaib_pack_zs alone, and pack + heavy + fused
+    (gaib_pack_zs + gaib_spmm_gemm_zs) on the products shape with half of the gradient kept, GCN weights, transW, the aggregate
+    as scratch -- the call GCN's backward makes (scripts/zs_aggregation.py times the same pair against the dense set)."""
+    ctx = capi.Context(0)
+    sg = synth.make("ogbn-products", device="cuda")
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    del sg
+    nv = g.nv
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.randn(nv, 128, device="cuda", generator=gen)
+    x = torch.where(torch.rand(nv, 128, device="cuda", generator=gen) < 0.5, x, torch.zeros_like(x))
+    W = torch.randn(128, 128, device="cuda", generator=gen) * 0.1
+    agg, out = torch.empty(nv, 128, device="cuda"), torch.empty(nv, 128, device="cuda")
+    zs = torch.empty(nv, 96, dtype=torch.int32, device="cuda")
+
+    def packed_set():
+        ctx.pack_zs(x, zs)
+        assert ctx.spmm_gemm_zs(g, capi.W_GCN, x, zs, agg, W, out, transW=True, agg_scratch=True)
+
+    res["pack_zs 2.45M x 128, half kept"] = ev_time(lambda: ctx.pack_zs(x, zs))
+    res["packed backward launch set (pack + heavy + fused), products shape, half kept"] = ev_time(packed_set)
+    del x, W, agg, out, zs
+    g.close()
+    ctx.close()
+    torch.cuda.empty_cache()
+
+
 def cora_epoch_ms():
     data = Path("/tmp/gaib_data_pg")
     subprocess.run([sys.executable, str(ROOT / "scripts" / "make_synth_dataset.py"), "cora", str(data)], check=True,
@@ -251,6 +281,7 @@ def main():
     res["GCN 128->47 layer step, products shape"] = layer_step(L.GCN, "ogbn-products", 128, 47, True)
     res["GAT 64->64 8 heads layer step, reddit shape"] = layer_step(L.GAT, "reddit", 64, 64, True, heads=8)
     gat_fused_vs_staged(res)
+    zs_lines(res)
     wide_tbs = wide_row_aggregation(res)
     res["cora GCN 2-layer epoch (trainer, recorded epochs)"] = cora_epoch_ms()
     k_ms, copy_gbs, norm = dominant_kernel_normalised()
