@@ -89,6 +89,8 @@ SIGNATURES = {
     "gaib_graph_row_map": (_vp, [_vp]),
     "gaib_spmm_2t": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _i]),
     "gaib_spmm_gemm_2t": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    "gaib_spmm_part_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _i]),
+    "gaib_spmm_gemm_part_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_gemm_fusable": (_i, [_vp, _i, _i, _i, _i]),
     "gaib_gat_scores_mh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_sddmm_mh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -170,6 +172,9 @@ SIGNATURES = {
     "gaib_halo_piece_slice": (_i, [_i64, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
     "gaib_halo_piece_ranges": (_i, [_vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i)]),
     "gaib_halo_exchange_wait_piece": (_i, [_vp, _i, _pp]),
+    "gaib_halo_exchange_begin_bf16": (_i, [_vp, _i, _vp]),
+    "gaib_halo_exchange_end_bf16": (_i, [_vp, _pp]),
+    "gaib_halo_exchange_wait_piece_bf16": (_i, [_vp, _i, _pp]),
     "gaib_halo_reduce": (_i, [_vp, _i, _vp, _vp]),
     "gaib_probe_stream_copy": (_i, [_vp, C.c_size_t, _i, C.POINTER(C.c_double)]),
     "gaib_probe_peer_copy": (_i, [_i, _i, C.c_size_t, _i, _i, C.POINTER(C.c_double)]),
@@ -290,6 +295,20 @@ class Halo:
     def wait_piece(self, piece: int) -> int:
         p = C.c_void_p()
         _check(self.lib.gaib_halo_exchange_wait_piece(self.h, piece, C.byref(p)), "gaib_halo_exchange_wait_piece")
+        return p.value or 0
+
+    def begin_bf16(self, rows, length: int):
+        """gaib_halo_exchange_begin_bf16: rows a torch.bfloat16 [n_own x length] matrix"""
+        _check(self.lib.gaib_halo_exchange_begin_bf16(self.h, length, _ptr(rows)), "gaib_halo_exchange_begin_bf16")
+
+    def end_bf16(self) -> int:
+        p = C.c_void_p()
+        _check(self.lib.gaib_halo_exchange_end_bf16(self.h, C.byref(p)), "gaib_halo_exchange_end_bf16")
+        return p.value or 0
+
+    def wait_piece_bf16(self, piece: int) -> int:
+        p = C.c_void_p()
+        _check(self.lib.gaib_halo_exchange_wait_piece_bf16(self.h, piece, C.byref(p)), "gaib_halo_exchange_wait_piece_bf16")
         return p.value or 0
 
     def reduce(self, halo_rows, rows, length: int):
@@ -620,6 +639,34 @@ class Context:
         _check(self.lib.gaib_spmm_gemm_2t(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(x2), n_first, _ptr(agg),
                                           _ptr(W), 1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags),
                "gaib_spmm_gemm_2t")
+        return out
+
+    def spmm_part_bf16(self, g: "Graph", kind: int, x, x2, n_first: int, out, edge_w=None, accumulate: bool = False,
+                       relu: bool = False):
+        """gaib_spmm_part_bf16: spmm (x2 None) / spmm_2t with torch.bfloat16 tables, on graphs with or without a row map; the
+        bits of the fp32 call on the widened tables"""
+        import torch
+
+        assert x.is_contiguous() and out.is_contiguous() and x.dtype == torch.bfloat16 and out.dtype == torch.float32
+        assert x2 is None or (x2.is_contiguous() and x2.dtype == torch.bfloat16)
+        flags = (1 if accumulate else 0) | (2 if relu else 0)
+        _check(self.lib.gaib_spmm_part_bf16(self.h, g.h, kind, _ptr(edge_w), x.shape[1], _ptr(x), _ptr(x2), n_first, _ptr(out),
+                                            flags), "gaib_spmm_part_bf16")
+        return out
+
+    def spmm_gemm_part_bf16(self, g: "Graph", kind: int, x, x2, n_first: int, agg, W, out, transW: bool = False,
+                            relu: bool = False, agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None,
+                            W2=None, overlaps_transfer: bool = False):
+        """gaib_spmm_gemm_part_bf16: spmm_gemm_2t with torch.bfloat16 tables (x2 may be None); agg, W, rows2, W2 and out fp32"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.bfloat16 and (x2 is None or (x2.is_contiguous() and x2.dtype == torch.bfloat16))
+        assert agg.dtype == torch.float32 and out.dtype == torch.float32
+        len_in, len_out = agg.shape[1], out.shape[1]
+        flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0) | (8 if overlaps_transfer else 0)
+        _check(self.lib.gaib_spmm_gemm_part_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(x2), n_first, _ptr(agg),
+                                                 _ptr(W), 1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags),
+               "gaib_spmm_gemm_part_bf16")
         return out
 
     def spmm_gemm_fusable(self, kind: int, len_in: int, len_out: int, dual: bool = False) -> bool:

@@ -135,6 +135,11 @@ struct ShmSlot {  // one rank's published send buffer of one halo plan
   int32_t pad3;
   int64_t chunk_rows_t;
   hipIpcMemHandle_t handle_tx[GAIB_IPC_MAX_CHUNKS - 1];
+  // what the owner's current exchange carries: bytes per row and per element (4: fp32 rows, 2: bf16 rows) -- the puller's must be
+  // the same (a rank with bf16 tables next to a rank without them would pull rows of the wrong length)
+  int64_t row_bytes;
+  int32_t elem_bytes;
+  int32_t pad4;
 };
 struct ShmSeg {
   std::atomic<uint32_t> magic;
@@ -269,7 +274,8 @@ struct gaib_halo {
   // test_ipc_halo_buffers_regrow_between_exchange_and_reduce[3] when plan creation began to allocate scratch of its own).
   // gaib_halo_destroy closes every mapping on every rank, passes a barrier, and only then frees.
   std::vector<void*> retired;  // (growable: a full list must never push a possibly-mapped buffer back into the pool early)
-  int pending_len;
+  int pending_len;   // fp32 words per row of the exchange in flight (0: none); a bf16 row of len elements is len / 2 words
+  int pending_elem;  // 4: begun with gaib_halo_exchange_begin, 2: with gaib_halo_exchange_begin_bf16
   struct Peer {
     uint64_t gen;
     void* base;
@@ -942,7 +948,9 @@ extern "C" int gaib_halo_piece_ranges(const gaib_halo* h, int piece, int cap, in
 // 1. pack the owned rows the peers asked for (compute stream), 2. start moving them.  Every rank calls it for every
 // exchange (also one that neither sends nor receives).  Returns at once on RCCL; on IPC after the peers' packs are
 // done and this rank's pulls are enqueued.
-extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_rows) {
+// (elem_bytes: what the caller's rows hold -- 4, or 2 for bf16 rows of 2 len elements, which travel as the len fp32 words they are
+// byte for byte: the pack, the chunks, the direct sends, the pieces and the pulls below only ever see row bytes)
+static int halo_exchange_begin_impl(gaib_halo* h, int len, const float* d_rows, int elem_bytes) {
   GAIB_CHECK(h && len >= 1, "gaib_halo_exchange_begin: bad argument");
   GAIB_CHECK(h->pending_len == 0, "gaib_halo_exchange_begin: the previous exchange was not ended");
   gaib_comm* c = h->c;
@@ -1010,6 +1018,7 @@ extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_ro
   }
   h->bytes_sent += (int64_t)row_bytes * n_send;
   h->pending_len = len;
+  h->pending_elem = elem_bytes;
   GAIB_HIP(hipEventRecord(c->ev_ready, ctx->stream));
   if (c->transport == GAIB_COMM_RCCL) {
     GAIB_HIP(hipStreamWaitEvent(c->cstream, c->ev_ready, 0));
@@ -1075,6 +1084,8 @@ extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_ro
     h->pub_chunk_rows = chunk_rows;
   }
   mine->n_pieces = h->n_pieces;  // (read by the peers after the barrier below)
+  mine->row_bytes = (int64_t)row_bytes;
+  mine->elem_bytes = elem_bytes;
   GAIB_COMM_DBG(c, "exchange_begin: %lld rows out (%zu B), %lld rows in, handle published; waiting for the pack", (long long)n_send,
                 row_bytes * (size_t)n_send, (long long)n_recv);
   hipError_t e = hipEventSynchronize(c->ev_ready);  // the pack is done: peers may read the buffer
@@ -1094,6 +1105,12 @@ extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_ro
       if (ps->n_pieces != K) {
         gaib_set_error("gaib_halo_exchange_begin(rank %d): rank %d cuts this exchange into %d pieces, this rank into %d "
                        "(gaib_halo_set_pieces: the same on every rank)", c->rank, r, ps->n_pieces, K);
+        return fail(c, GAIB_ERR_INVALID);
+      }
+      if (ps->row_bytes != (int64_t)row_bytes || ps->elem_bytes != elem_bytes) {
+        gaib_set_error("gaib_halo_exchange_begin(rank %d): rank %d exchanges rows of %lld B in %d-byte elements, this rank rows of "
+                       "%zu B in %d-byte elements (bf16 tables -- \"agg_bf16\", GAIB_AGG_DTYPE -- on some ranks only?)", c->rank, r,
+                       (long long)ps->row_bytes, ps->elem_bytes, row_bytes, elem_bytes);
         return fail(c, GAIB_ERR_INVALID);
       }
       if (h->peer[r].gen != ps->gen) {  // the peer's allocations (or their layout) changed: every mapping of the old ones goes
@@ -1154,12 +1171,31 @@ extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_ro
   return GAIB_OK;
 }
 
+extern "C" int gaib_halo_exchange_begin(gaib_halo* h, int len, const float* d_rows) {
+  return halo_exchange_begin_impl(h, len, d_rows, 4);
+}
+
+// the same exchange carrying bf16 rows (raw bits) of `len` elements: 2 len bytes per row.  An odd len is refused here, locally
+// and before any collective step -- every rank decides the same from the same len, and no exchange is left pending.
+extern "C" int gaib_halo_exchange_begin_bf16(gaib_halo* h, int len, const uint16_t* d_rows) {
+  GAIB_CHECK(h && len >= 1, "gaib_halo_exchange_begin_bf16: bad argument");
+  if (len % 2 != 0) {
+    gaib_set_error("gaib_halo_exchange_begin_bf16: rows of %d bf16 elements (an odd number) are not whole 4-byte words: exchange "
+                   "such rows in fp32", len);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  GAIB_CHECK(((uintptr_t)d_rows & 3) == 0, "gaib_halo_exchange_begin_bf16: d_rows must be 4-byte aligned");
+  return halo_exchange_begin_impl(h, len / 2, reinterpret_cast<const float*>(d_rows), 2);
+}
+
 // between begin and end: the compute stream continues only after slice `piece` of every peer pair has landed -- the columns
 // gaib_halo_piece_ranges names are then valid in *d_table (the others are still on the wire).  Stream-ordered on both
 // transports (the host does not wait); gaib_halo_exchange_end is still due after the last piece.
-extern "C" int gaib_halo_exchange_wait_piece(gaib_halo* h, int piece, const float** d_table) {
+static int halo_exchange_wait_piece_impl(gaib_halo* h, int piece, const float** d_table, int elem_bytes) {
   GAIB_CHECK(h && d_table, "gaib_halo_exchange_wait_piece: NULL argument");
   GAIB_CHECK(h->pending_len > 0, "gaib_halo_exchange_wait_piece: no exchange in flight");
+  GAIB_CHECK(h->pending_elem == elem_bytes, "gaib_halo_exchange_wait_piece: the exchange in flight carries %s rows (wait for it with "
+             "the function of the element type it was begun with)", h->pending_elem == 2 ? "bf16" : "fp32");
   GAIB_CHECK(piece >= 0 && piece < h->n_pieces, "gaib_halo_exchange_wait_piece: piece %d of %d", piece, h->n_pieces);
   gaib_comm* c = h->c;
   GAIB_HIP(hipSetDevice(c->ctx->device));
@@ -1168,12 +1204,20 @@ extern "C" int gaib_halo_exchange_wait_piece(gaib_halo* h, int piece, const floa
   *d_table = h->table;
   return GAIB_OK;
 }
+extern "C" int gaib_halo_exchange_wait_piece(gaib_halo* h, int piece, const float** d_table) {
+  return halo_exchange_wait_piece_impl(h, piece, d_table, 4);
+}
+extern "C" int gaib_halo_exchange_wait_piece_bf16(gaib_halo* h, int piece, const uint16_t** d_table) {
+  return halo_exchange_wait_piece_impl(h, piece, reinterpret_cast<const float**>(d_table), 2);
+}
 
 // the compute stream continues after the rows have arrived; *d_table = [rows x len], grouped by owner rank in the
-// order of the recv counts
-extern "C" int gaib_halo_exchange_end(gaib_halo* h, const float** d_table) {
+// order of the recv counts.  (The wrong element type is refused and the exchange stays in flight: end it with the right one.)
+static int halo_exchange_end_impl(gaib_halo* h, const float** d_table, int elem_bytes) {
   GAIB_CHECK(h && d_table, "gaib_halo_exchange_end: NULL argument");
   GAIB_CHECK(h->pending_len > 0, "gaib_halo_exchange_end: no exchange in flight");
+  GAIB_CHECK(h->pending_elem == elem_bytes, "gaib_halo_exchange_end: the exchange in flight carries %s rows (end it with the "
+             "function of the element type it was begun with)", h->pending_elem == 2 ? "bf16" : "fp32");
   gaib_comm* c = h->c;
   GAIB_HIP(hipSetDevice(c->ctx->device));
   h->pending_len = 0;
@@ -1191,6 +1235,10 @@ extern "C" int gaib_halo_exchange_end(gaib_halo* h, const float** d_table) {
   GAIB_HIP(hipStreamWaitEvent(c->ctx->stream, c->ev_done, 0));
   *d_table = h->table;
   return GAIB_OK;
+}
+extern "C" int gaib_halo_exchange_end(gaib_halo* h, const float** d_table) { return halo_exchange_end_impl(h, d_table, 4); }
+extern "C" int gaib_halo_exchange_end_bf16(gaib_halo* h, const uint16_t** d_table) {
+  return halo_exchange_end_impl(h, reinterpret_cast<const float**>(d_table), 2);
 }
 
 // d_rows[idx[k], :] += buf[k, :]; the row ids of one peer's segment are distinct (ascending), one wave per row

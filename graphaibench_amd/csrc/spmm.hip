@@ -229,8 +229,8 @@ static int64_t pad_stride_floats(const gaib_ctx* ctx, const gaib_graph* g, int l
 
 // fills the launch arguments shared by every aggregation path; *wmode = kernel weight mode
 // d_in2 / n_first: column ids >= n_first index the second table d_in2 (row id - n_first) -- NULL: one table
-// bf16: d_in holds bf16 bits (gaib_spmm_bf16): gathered as it is (no re-strided copy, no cold-column flags), and the
-// buffer-descriptor path is chosen by the table's bf16 byte size
+// bf16: d_in (and d_in2) hold bf16 bits (gaib_spmm_bf16, gaib_spmm_part_bf16): gathered as they are (no re-strided copy, no
+// cold-column flags), and the buffer-descriptor path is chosen by the tables' bf16 byte sizes
 static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                       const float* d_in, float* d_out, int flags, int heads, SpmmArgs* pa, int* wmode,
                       const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false) {
@@ -289,7 +289,7 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   const int64_t table_bytes = (d_in2 ? n_first : g->nc) * a.ld * (bf16 ? 2 : 4);
   a.in_bytes = table_bytes < ((int64_t)1 << 32) ? (uint32_t)table_bytes : 0u;
   if (d_in2) {
-    const int64_t t2 = (g->nc - n_first) * a.ld * 4;
+    const int64_t t2 = (g->nc - n_first) * a.ld * (bf16 ? 2 : 4);
     a.in2_bytes = t2 < ((int64_t)1 << 32) ? (uint32_t)t2 : 0u;
   }
   switch (weight_kind) {
@@ -340,6 +340,10 @@ static bool chunk_rule(gaib_ctx* ctx, gaib_graph* g, int64_t ld) {
 int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len);
 int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
                          int vec, int wmode);
+// ... and over bf16 tables: spmm_part_bf16.hip
+int gaib_spmm_part_plain_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len);
+int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
+                              int vec, int wmode);
 // ... and so do the fused kernels over a bf16 table: spmm_gemm_bf16.hip
 int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
                          int vec, int wmode);
@@ -426,7 +430,8 @@ extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in
   return ctx && fuse_shape_ok(ctx, weight_kind, len_in, len_out, dual != 0) ? 1 : 0;
 }
 
-// bf16: d_in holds bf16 bits (gaib_spmm_gemm_bf16; whole graphs, checked by the caller).  Every test below is made on what the
+// bf16: d_in (and d_in2) hold bf16 bits (gaib_spmm_gemm_bf16: whole graphs, checked by the caller; gaib_spmm_gemm_part_bf16: row
+// classes of a partition too).  Every test below is made on what the
 // fp32 call would see for the same table widened -- the widened table sits at "twice the address" (a bf16 table aligned to 8 B
 // stands for an fp32 one aligned to 16), sizes and the chunk rule count fp32 bytes -- so both take the same route, and each route
 // runs with the bf16 gather: no fp32 copy of the table anywhere.
@@ -450,7 +455,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
              "gaib_spmm_gemm: buffers must not alias");
   const bool dual = d_rows2 != nullptr;
   const bool part = g->row_map != nullptr || d_in2 != nullptr;
-  const uintptr_t al = (bf16 ? (uintptr_t)d_in << 1 : (uintptr_t)d_in) | (uintptr_t)d_agg | (uintptr_t)d_in2;
+  const uintptr_t al = (bf16 ? ((uintptr_t)d_in | (uintptr_t)d_in2) << 1 : ((uintptr_t)d_in | (uintptr_t)d_in2)) | (uintptr_t)d_agg;
   // the weight matrices [len_out x (len_in+4)] and 16 row strips must fit the CU's 160 KB of LDS;
   // 65..128 columns need 8-byte lanes
   const int kpad = len_in <= 64 ? 64 : 128;
@@ -611,6 +616,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   f.heavy_agg = hv;
   f.heavy_rows = g->heavy_rows;
   f.n_heavy = (int)g->n_heavy;
+  if (part && bf16) return gaib_spmm_part_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
   if (part) return gaib_spmm_part_fused(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
   if (bf16) return gaib_spmm_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
   if (d_zs) {  // gather from the packed rows; the dense table stays behind them for over-capacity rows
@@ -826,4 +832,45 @@ extern "C" int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kin
   GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_bf16: NULL second operand");
   return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out,
                               flags);
+}
+
+// ---- bf16 feature tables on the row classes of a vertex-range partition (spmm_part_bf16.hip) ----------------------------------
+// gaib_spmm_ex (d_in2 == NULL; n_first is then ignored) / gaib_spmm_2t with the table(s) in bf16: graphs with or without a row map,
+// one table or [owned | halo].  A whole
+// graph over one table is gaib_spmm_bf16's call; a row class takes the class kernels' route (no ordered chunks, no re-strided
+// copy -- as gaib_spmm_ex on a class graph) with the bf16 gather, so the result is bit-identical to the fp32 call on the widened
+// tables.
+extern "C" int gaib_spmm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
+                                   const uint16_t* d_in, const uint16_t* d_in2, int64_t n_first, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_part_bf16: NULL ctx/graph");
+  if (!g->row_map && !d_in2) {
+    return gaib_spmm_bf16(ctx, g, weight_kind, d_edge_w, len, d_in, d_out, flags);
+  }
+  GAIB_CHECK(len >= 0, "gaib_spmm_part_bf16: len < 0");
+  GAIB_CHECK((flags & ~(GAIB_ACCUMULATE | GAIB_RELU)) == 0, "gaib_spmm_part_bf16: unsupported flags %d", flags);
+  GAIB_CHECK(ctx->device == g->device, "gaib_spmm_part_bf16: graph lives on device %d, ctx on %d", g->device, ctx->device);
+  if (len == 0 || g->nv == 0) return GAIB_OK;
+  GAIB_CHECK(d_in && d_out, "gaib_spmm_part_bf16: NULL feature pointer");
+  GAIB_CHECK((const void*)d_in != (const void*)d_out && (const void*)d_in2 != (const void*)d_out,
+             "gaib_spmm_part_bf16: in / in2 and out must not alias");
+  SpmmArgs a;
+  int wmode = 0;
+  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len, reinterpret_cast<const float*>(d_in), d_out, flags, 1, &a, &wmode,
+                      reinterpret_cast<const float*>(d_in2), n_first, true));
+  GAIB_CHECK(wmode <= 1, "gaib_spmm_part_bf16: a row class of a partition aggregates with GAIB_W_GCN / _MEAN / _MEAN_T / single-head "
+                         "_EDGE weights (got kind %d)", weight_kind);
+  return gaib_spmm_part_plain_bf16(ctx, g, &a, wmode, len);
+}
+
+// gaib_spmm_gemm_2t with the table(s) in bf16 (d_rows2 / d_W2: both or NULL; d_in2 may be NULL): the route of the fp32 call on the
+// widened tables -- a row class runs the fused class kernels or is refused where the fp32 call refuses it, a whole graph takes
+// gaib_spmm_gemm(2)_bf16's routes -- with every flag of gaib_spmm_gemm_2t, GAIB_OVERLAPS_TRANSFER included.
+extern "C" int gaib_spmm_gemm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                                        const uint16_t* d_in, const uint16_t* d_in2, int64_t n_first, float* d_agg, const float* d_W,
+                                        int transW, const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_gemm_part_bf16: NULL ctx/graph");
+  GAIB_CHECK(!d_in2 || ((const void*)d_in2 != (const void*)d_agg && (const void*)d_in2 != (const void*)d_out),
+             "gaib_spmm_gemm_part_bf16: buffers must not alias");
+  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2,
+                        d_W2, len_out, d_out, flags, reinterpret_cast<const float*>(d_in2), n_first, true);
 }

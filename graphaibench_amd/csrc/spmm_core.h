@@ -1,4 +1,4 @@
-// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_part.hip, spmm_gemm_bf16.hip):
+// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_part.hip, spmm_part_bf16.hip, spmm_gemm_bf16.hip):
 // launch arguments, the feature-row gather and the per-wave edge loop.
 #pragma once
 #include <type_traits>
@@ -36,7 +36,7 @@ struct SpmmArgs {
   const uint32_t* row_map;   // row r of the graph is row row_map[r] of out / the continued partial sums / rows2 / y (NULL: r itself)
   const float* in2;          // column ids >= n_first index this second table (row id - n_first): the halo table behind the
   uint32_t n_first;          //   rank's own rows.  in2 == NULL: one table, n_first = 0xffffffff
-  uint32_t in2_bytes;        // BUF kernels: size of the second table (< 4 GB)
+  uint32_t in2_bytes;        // BUF kernels: size of the second table (< 4 GB; of its bf16 bits when the tables are bf16)
 };
 
 // the row of the caller's matrices that row r of the graph stands for
@@ -166,7 +166,8 @@ constexpr int GAIB_ZS_CAP = 46;
 // (streaming) for every gather; 3 = buffer_load, nt only for COLD columns (top bit of the column id
 // set by gaib_graph_ensure_hot_flags), so the few thousand hub rows keep their place in the 4 MB L2.
 // PART: two tables -- column ids below n_first index `in`, the others `in2` (a rank's own rows and its halo table, which
-// live in different allocations); the choice is a scalar select on the (wave-uniform) column id.
+// live in different allocations); the choice is a scalar select on the (wave-uniform) column id.  Both tables hold the same
+// element type: fp32, or bf16 (spmm_part_bf16.hip) -- ldb, the n_first bias of inb2 and both descriptors then count bf16 bytes.
 // E: element type of the table -- float, or uint16_t for a bf16 table (a.in then points at bf16 bits, a.ld counts
 // elements, a.in_bytes is the bf16 size; voff is a byte offset into such a row); or zs_t for a zero-suppressed table (a.in
 // then points at the packed rows, a.ld = 96, a.in_bytes is the packed size, and a.in2 / a.in2_bytes name the dense table the
@@ -175,7 +176,7 @@ template <int VEC, int GM, bool PART = false, typename E = float>
 struct RowGather {
   static constexpr bool BUF = GM != 0;
   static constexpr bool ZS = std::is_same<E, zs_t>::value;
-  static_assert(!PART || (sizeof(E) == 4 && !ZS), "two-table gathers: fp32 tables only");
+  static_assert(!PART || !ZS, "two-table gathers: fp32 or bf16 tables");
   static_assert(!ZS || (VEC == 2 && GM == 1), "zero-suppressed tables: 8-byte lanes (128 columns), buffer addressing");
   __amdgpu_buffer_rsrc_t rsrc, rsrc2;
   const char *inb, *inb2;  // inb2 is biased by -n_first rows: row base = inb2 + col * ldb
@@ -245,7 +246,7 @@ struct RowGather {
         return load_rsrc<0>(second ? rsrc2 : rsrc, soff, voff);  // (scalar selects: straight-line code)
       } else {
         const char* rowp = (second ? inb2 : inb) + (int64_t)cj * ldb;
-        return *reinterpret_cast<const vec_t*>(rowp + voff);
+        return *reinterpret_cast<const raw_t*>(rowp + voff);  // (bf16: the packed words, as from the one-table gather)
       }
     } else if constexpr (GM == 3) {
       const uint32_t c = cj & 0x7fffffffu;

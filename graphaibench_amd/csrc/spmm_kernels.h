@@ -1,5 +1,5 @@
-// spmm_kernels.h -- the aggregation kernels and their launchers, shared by spmm.hip (whole graphs) and spmm_part.hip (the
-// row classes of a vertex-range partition).  Every kernel takes a compile-time PART flag:
+// spmm_kernels.h -- the aggregation kernels and their launchers, shared by spmm.hip (whole graphs), spmm_part.hip (the
+// row classes of a vertex-range partition) and spmm_part_bf16.hip (the same over bf16 tables).  Every kernel takes a compile-time PART flag:
 //   PART = false  the graph's row r is row r of the caller's matrices, one feature table (spmm.hip)
 //   PART = true   the graph is a COMPACT subset of a rank's rows (gaib_graph_split_classes): row r stands for row
 //                 row_map[r] of out / agg / rows2 / y, and column ids >= n_first index a second table (the halo table
@@ -165,7 +165,8 @@ int launch_w64_u(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
   if (grid > 0) {
     // (row classes of a partition are timed under keys of their own: interior / owned-column pass, halo-column pass, one pass)
     const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_l = (double)a.n_rows - (double)g->n_heavy;
-    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_light" : (!PART ? "spmm_light" : (a.in2 ? "part_light_2t" : (a.accumulate ? "part_light_acc" : "part_light"))),
+    ProfScope ps(ctx, sizeof(E) == 2 ? (!PART ? "spmm_bf16_light" : (a.in2 ? "part_bf16_light_2t" : (a.accumulate ? "part_bf16_light_acc" : "part_bf16_light")))
+                                     : (!PART ? "spmm_light" : (a.in2 ? "part_light_2t" : (a.accumulate ? "part_light_acc" : "part_light"))),
                  gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, EB), 2.0 * e_l * a.ncols, a.ncols);
     spmm_w64_kernel<VEC, CT, WMODE, U, BUF, PART, E><<<dim3(grid), 256, 0, ctx->stream>>>(a);
     GAIB_LAUNCH_CHECK();
@@ -885,14 +886,13 @@ inline int fuse_strip_rows(int kpad, int n_out, bool dual) {
   return fuse_lds_bytes(kpad, n_out, dual, 2) <= 160 * 1024 ? 2 : 0;
 }
 
-// E = uint16_t (whole graphs only): a.in points at bf16 bits, a.ld counts elements, a.in_bytes is the bf16 size.  Gathers in flight
+// E = uint16_t: a.in (and a.in2) point at bf16 bits, a.ld counts elements, a.in_bytes / a.in2_bytes are the bf16 sizes.  Gathers in flight
 // per wave: a bf16 gather is held packed (half the registers of an fp32 one), so the row forms keep GAIB_BF16_FUSE_U of them where
 // fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  The XCD-affine tile supply is not compiled in for bf16 (it would
 // triple this set of instantiations for the planted-locality case alone; the supply changes no row's sum): global counter.
 template <int VEC, int WMODE, bool PART = false, typename E = float>
 int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
   constexpr bool BF = sizeof(E) == 2;
-  static_assert(!BF || !PART, "bf16 tables: whole graphs only");
   constexpr int U = 16;                               // the heavy kernel's, and the fp32 row forms'
   constexpr int UROW = BF ? GAIB_BF16_FUSE_U : U;     // row forms
   constexpr int UFLAT = BF ? 16 : 8;                  // edge-stream forms
@@ -933,14 +933,16 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   const double fused_bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (dual ? 1 : 0), EB) +
                              r_all * 4.0 * f.n_out * (f.y_accum ? 2 : 1);
   const double fused_flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (dual ? 2 : 1);
-  ProfScope ps(ctx, BF ? "spmm_gemm_bf16_fused" : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused")), fused_bytes,
+  ProfScope ps(ctx, BF ? (!PART ? "spmm_gemm_bf16_fused" : (a.in2 ? "part_bf16_fused_2t" : (f.agg_in ? "part_bf16_fused_acc" : "part_bf16_fused")))
+                       : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused")), fused_bytes,
                fused_flops, a.ncols);
   // more than 64 KB of dynamic LDS has to be asked for
   // (the edge-stream form keeps 8 gathers in flight, not 16: with 16 the operand fragments of the dense product
   // spill and are reloaded inside the MFMA loop)
 #define GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, AFF, PRE)                                              \
   do {                                                                                                                \
-    constexpr int UU = FLAT ? UFLAT : UROW;                                                                           \
+    /* (two products over bf16 class tables, 8-B lanes: 32 rows in flight spilled 14-17 VGPRs at the kernel's 128 -- 16) */ \
+    constexpr int UU = FLAT ? UFLAT : ((BF && PART && DUAL && VEC == 2) ? 16 : UROW);                                 \
     GAIB_HIP(hipFuncSetAttribute(                                                                                     \
         (const void*)spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE, E>,          \
         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                     \
@@ -974,9 +976,9 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
                     (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * (int64_t)a.n_rows));
   const bool ring = flat && ctx->spmm_flat_ring != 0;  // the edge stream as a software pipeline (see RING)
   // option spmm_bf16_fuse_u (benchmark only): the other depth of the A/B, on the headline variant alone -- bf16 row form,
-  // 8-row strip, buffer addressing, 8-B lanes
+  // 8-row strip, buffer addressing, 8-B lanes (whole graphs)
   bool launched = false;
-  if constexpr (BF && VEC == 2) {
+  if constexpr (BF && VEC == 2 && !PART) {
     constexpr int UALT = UROW == 32 ? 16 : 32;
     if (ctx->spmm_bf16_fuse_u == UALT && buf && !dual && strip == 8 && !flat && !f.y_accum) {
       GAIB_HIP(hipFuncSetAttribute((const void*)spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>,

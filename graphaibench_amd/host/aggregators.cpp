@@ -50,10 +50,22 @@ static const uint16_t* to_bf16(size_t rows, int len, const float* in) {
   GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)n, in, t));
   return t;
 }
+// bf16 tables on a vertex-range partition need an exchange that carries bf16 rows: a library plan (set_halo_plan) or bf16
+// callbacks (set_halo_bf16).  A halo set with the fp32 callbacks alone (set_halo) cannot: refused as before.
 static void no_bf16_halo(Graph& g) {
-  if (!g.has_halo()) return;
-  fprintf(stderr, "GPU error: agg_bf16 (GAIB_AGG_DTYPE=bf16) covers whole graphs only; this graph has a halo (partitioned run)\n");
+  if (!g.has_halo() || g.halo_carries_bf16()) return;
+  fprintf(stderr, "GPU error: agg_bf16 (GAIB_AGG_DTYPE=bf16) on a graph with a halo (partitioned run) needs an exchange that "
+          "carries bf16 rows: a halo plan (set_halo_plan) or bf16 callbacks (set_halo_bf16); this graph's halo was set with fp32 "
+          "callbacks (set_halo)\n");
   exit(EXIT_FAILURE);
+}
+// does this aggregation of `len` columns run on bf16 tables?  Whole graphs: always under agg_bf16.  On a partition: even widths
+// (an odd-width bf16 row is not a whole number of the 4-byte words the exchange moves: such an aggregation -- the 47-wide ones --
+// runs on the fp32 path; the trainer's table line says so)
+static bool bf16_for(Graph& g, int len) {
+  if (!aggregator::bf16_tables()) return false;
+  no_bf16_halo(g);
+  return !g.has_halo() || len % 2 == 0;
 }
 
 // ---- zero-suppressed gradient tables (option agg_zs) ---------------------------------------------------------------------
@@ -155,19 +167,64 @@ static void zs_set_paused(int slot, bool p) {
 // exchange -- last(whole, table) --, or, where the exchange travels in K > 1 time slices (gaib_halo_set_pieces), piece by piece
 // as the slices land: plain(piece k, table) in accumulate mode for every piece but the last non-empty one, which takes last()
 // (the pass that carries the activation / the dense product).  Same terms per row, added piece by piece.  Ends the exchange.
-template <class Plain, class Last>
-static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
+// T: element type of the exchanged table (float, or uint16_t = bf16 bits: the exchange was begun with halo_begin_bf16).
+static const float* halo_end_t(Graph& g, int len, const float*) { return g.halo_end(len); }
+static const uint16_t* halo_end_t(Graph& g, int len, const uint16_t*) { return g.halo_end_bf16(len); }
+static const float* halo_wait_t(Graph& g, int k, const float*) { return g.halo_wait_piece(k); }
+static const uint16_t* halo_wait_t(Graph& g, int k, const uint16_t*) { return g.halo_wait_piece_bf16(k); }
+template <class T, class Plain, class Last>
+static void halo_half_t(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
   const int K = g.halo_pieces(len);
   if (K <= 1) {
-    last(whole, g.halo_end(len));
+    last(whole, halo_end_t(g, len, (const T*)NULL));
     return;
   }
   int last_k = 0;
   for (int k = 0; k < K; k++)
     if (gaib_graph_ne(g.halo_piece_graph(k)) > 0) last_k = k;
   for (int k = 0; k < last_k; k++)
-    if (gaib_graph_ne(g.halo_piece_graph(k)) > 0) plain(g.halo_piece_graph(k), g.halo_wait_piece(k));
-  last(g.halo_piece_graph(last_k), g.halo_end(len));  // (pieces behind last_k are empty: waiting for all of them costs nothing)
+    if (gaib_graph_ne(g.halo_piece_graph(k)) > 0) plain(g.halo_piece_graph(k), halo_wait_t(g, k, (const T*)NULL));
+  last(g.halo_piece_graph(last_k), halo_end_t(g, len, (const T*)NULL));  // (pieces behind last_k are empty: waiting for all of them costs nothing)
+}
+template <class Plain, class Last>
+static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
+  halo_half_t<float>(g, whole, len, plain, last);
+}
+
+// aggregate_rows on a partition with bf16 tables (agg_bf16, even len): the branch below with the same call structure and flags.
+// The owned rows are cast into the bf16 scratch ONCE -- the owned-column pass gathers from it -- and the exchange is begun FROM
+// that scratch (half the bytes packed and on the wire; over RCCL a contiguous send list is read straight from it), which no other
+// cast touches before the exchange has ended: every path below ends it before it returns.
+static void aggregate_rows_bf16_part(Graph& g, int kind, int len, const float* in, float* out, int act) {
+  gaib_graph* own = dev(g);
+  const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(own), len, in);
+  auto ex = [&](gaib_graph* gg, const uint16_t* t, int fl) {
+    GAIB_OR_DIE(gaib_spmm_part_bf16(C(), gg, kind, NULL, len, t, NULL, 0, out, fl));
+  };
+  auto acc = [&](gaib_graph* gh, const uint16_t* halo) { ex(gh, halo, GAIB_ACCUMULATE); };
+  auto acc_act = [&](gaib_graph* gh, const uint16_t* halo) { ex(gh, halo, GAIB_ACCUMULATE | act); };
+  const int mode = g.partition_mode(len);
+  g.halo_begin_bf16(len, tab);
+  if (mode != Graph::PART_SPLIT) {
+    ex(g.class_interior(), tab, act);
+    if (mode == Graph::PART_CLASSES) {
+      const bool have_halo_edges = gaib_graph_ne(g.class_boundary_halo()) > 0;  // (else: no boundary row either)
+      ex(g.class_boundary_own(), tab, have_halo_edges ? 0 : act);
+      if (have_halo_edges) halo_half_t<uint16_t>(g, g.class_boundary_halo(), len, acc, acc_act);
+      else g.halo_end_bf16(len);
+    } else {
+      const uint16_t* halo = g.halo_end_bf16(len);
+      GAIB_OR_DIE(gaib_spmm_part_bf16(C(), g.class_boundary_full(), kind, NULL, len, tab, halo, (int64_t)g.size(), out, act));
+    }
+    return;
+  }
+  const bool have_halo_edges = gaib_graph_ne(g.halo_graph()) > 0;
+  ex(own, tab, have_halo_edges ? 0 : act);
+  if (!have_halo_edges) {
+    g.halo_end_bf16(len);
+    return;
+  }
+  halo_half_t<uint16_t>(g, g.halo_graph(), len, acc, acc_act);
 }
 
 // One aggregation.  On a vertex-range partition the work that needs no halo row runs while the halo rows are in flight
@@ -178,8 +235,11 @@ static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last la
 static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* out, bool relu = false, bool count = true) {
   if (count) count_edges(g);
   const int act = relu ? GAIB_RELU : 0;
-  if (aggregator::bf16_tables()) {
-    no_bf16_halo(g);
+  if (bf16_for(g, len)) {
+    if (g.has_halo()) {
+      aggregate_rows_bf16_part(g, kind, len, in, out, act);
+      return;
+    }
     gaib_graph* dg = dev(g);
     GAIB_OR_DIE(gaib_spmm_bf16(C(), dg, kind, NULL, len, to_bf16((size_t)gaib_graph_nc(dg), len, in), out, act));
     return;
@@ -224,9 +284,57 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
                                        const float* rows2, const float* W2, bool relu_masked) {
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
-  if (bf16_tables()) {
+  if (bf16_for(g, len) && g.has_halo()) {
+    // bf16 tables on a partition: the fp32 branch further down with the same call structure and flags, the owned table cast once
+    // into the scratch, the exchange begun from it (see aggregate_rows_bf16_part) and every kernel gathering bf16
+    const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
+    const int mode = g.partition_mode(len);
+    if (mode != Graph::PART_SPLIT && !gaib_spmm_gemm_fusable(C(), kind, len, len_out, rows2 ? 1 : 0)) {
+      aggregate_rows(g, kind, len, in, agg, false, false);
+      const int act = relu ? GAIB_RELU : 0;
+      GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, agg, W, rows2 ? 0 : act, out));
+      if (rows2)
+        GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, rows2, W2, GAIB_ACCUMULATE | act, out));
+      return;
+    }
+    gaib_graph* own = dev(g);
+    const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(own), len, in);
+    auto fused16 = [&](gaib_graph* dg, const uint16_t* src, int fl) {
+      GAIB_OR_DIE(gaib_spmm_gemm_part_bf16(C(), dg, kind, NULL, len, src, NULL, 0, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
+    };
+    auto plain16 = [&](gaib_graph* gh, const uint16_t* t, int fl) {
+      GAIB_OR_DIE(gaib_spmm_part_bf16(C(), gh, kind, NULL, len, t, NULL, 0, agg, fl));
+    };
+    auto plain_acc16 = [&](gaib_graph* gh, const uint16_t* halo) { plain16(gh, halo, GAIB_ACCUMULATE); };
+    auto fused_acc16 = [&](gaib_graph* gh, const uint16_t* halo) { fused16(gh, halo, flags | GAIB_ACCUMULATE); };
+    g.halo_begin_bf16(len, tab);  // every rank joins every exchange, also one without halo edges
+    if (mode != Graph::PART_SPLIT) {
+      fused16(g.class_interior(), tab, flags | GAIB_OVERLAPS_TRANSFER);
+      if (mode == Graph::PART_CLASSES) {
+        if (gaib_graph_ne(g.class_boundary_halo()) == 0) {  // no boundary row
+          g.halo_end_bf16(len);
+          return;
+        }
+        plain16(g.class_boundary_own(), tab, 0);
+        halo_half_t<uint16_t>(g, g.class_boundary_halo(), len, plain_acc16, fused_acc16);
+      } else {
+        const uint16_t* halo = g.halo_end_bf16(len);
+        GAIB_OR_DIE(gaib_spmm_gemm_part_bf16(C(), g.class_boundary_full(), kind, NULL, len, tab, halo, (int64_t)g.size(), agg, W,
+                                             transW ? 1 : 0, rows2, W2, len_out, out, flags));
+      }
+      return;
+    }
+    if (gaib_graph_ne(g.halo_graph()) == 0) {
+      fused16(own, tab, flags | GAIB_OVERLAPS_TRANSFER);
+      g.halo_end_bf16(len);
+      return;
+    }
+    plain16(own, tab, 0);
+    halo_half_t<uint16_t>(g, g.halo_graph(), len, plain_acc16, fused_acc16);
+    return;
+  }
+  if (bf16_for(g, len)) {
     // bf16 table: the fused kernel gathers from it -- the route (and the bits) of the fp32 branch below on the rounded table
-    no_bf16_halo(g);
     gaib_graph* dg = dev(g);
     const int fl = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
     const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(dg), len, in);

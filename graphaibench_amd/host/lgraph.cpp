@@ -16,7 +16,38 @@ LearningGraph* LearningGraph::adopt_device(gaib_graph* g) {
 
 void LearningGraph::halo_begin(int len, const float* d_in) {
   if (halo_plan_) GAIB_OR_DIE(gaib_halo_exchange_begin(halo_plan_, len, d_in));
-  else halo_begin_(halo_user_, len, d_in);
+  else if (halo_begin_) halo_begin_(halo_user_, len, d_in);
+  else {
+    fprintf(stderr, "GPU error: this graph's halo has bf16 callbacks only (set_halo_bf16) and an aggregation of %d columns needs "
+            "an fp32 exchange (odd widths, or agg_bf16 off): give set_halo's callbacks as well\n", len);
+    exit(EXIT_FAILURE);
+  }
+}
+int LearningGraph::halo_elem_bytes(int len) const {
+  if (!has_halo() || !halo_carries_bf16() || len % 2 != 0) return 4;
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "agg_bf16", &v));
+  return v != 0 ? 2 : 4;
+}
+void LearningGraph::halo_begin_bf16(int len, const uint16_t* d_in) {
+  if (halo_plan_) GAIB_OR_DIE(gaib_halo_exchange_begin_bf16(halo_plan_, len, d_in));
+  else halo_begin16_(halo_user_, len, d_in);
+}
+const uint16_t* LearningGraph::halo_end_bf16(int len) {
+  if (!halo_plan_) return halo_end16_(halo_user_, len);
+  const uint16_t* table = NULL;
+  GAIB_OR_DIE(gaib_halo_exchange_end_bf16(halo_plan_, &table));
+  return table;
+}
+const uint16_t* LearningGraph::halo_wait_piece_bf16(int j) {
+  const int k = (j + 1) * (pieces_slices_ / pieces_built_) - 1;  // the last slice of piece j
+  if (!halo_plan_) {
+    fprintf(stderr, "GPU error: bf16 halo callbacks (set_halo_bf16) deliver the whole exchange at once (internal: halo_pieces is 1 there)\n");
+    exit(EXIT_FAILURE);
+  }
+  const uint16_t* table = NULL;
+  GAIB_OR_DIE(gaib_halo_exchange_wait_piece_bf16(halo_plan_, k, &table));
+  return table;
 }
 const float* LearningGraph::halo_end(int len) {
   if (!halo_plan_) return halo_end_(halo_user_, len);
@@ -49,12 +80,12 @@ void LearningGraph::drop_pieces() {
 // 4.8 TB/s on row segments of <= 3 edges, 7.7 TB/s from 12 edges on, and 8 % less where it is one of several pieces.
 namespace {
 struct SplitShape {
-  double row_bytes, t_wire;
+  double row_bytes, sum_bytes, t_wire;  // a gathered / exchanged row (2 len under bf16 tables, else 4 len); a row of fp32 partial sums
   int64_t ne_own, ne_halo, rows_half;  // owned-column edges of ALL rows; halo-column edges; rows of the halo-column half
 };
-double wire_seconds(int64_t link_rows, int len) {
+double wire_seconds(int64_t link_rows, double row_bytes) {
   const double link_gbs = getenv("GAIB_LINK_GBS") ? atof(getenv("GAIB_LINK_GBS")) : 100.0;
-  return link_rows * 4.0 * len / ((link_gbs > 0 ? link_gbs : 100.0) * 1e9);
+  return link_rows * row_bytes / ((link_gbs > 0 ? link_gbs : 100.0) * 1e9);
 }
 // the column split with the K slices consumed in kc pieces: owned-column work first, piece j once slice (j + 1) K / kc - 1 has
 // landed -- at (j + 1) / kc of the exchange --, every piece a read + write of the half's partial sums on top of its gathers
@@ -63,7 +94,7 @@ double model_split(const SplitShape& s, int kc) {
   double rate = 4.8e12 + (e - 3.0) / 9.0 * 2.9e12;
   rate = rate < 4.8e12 ? 4.8e12 : (rate > 7.7e12 ? 7.7e12 : rate);
   if (kc > 1) rate *= 0.92;
-  const double t_piece = (s.ne_halo * (s.row_bytes + 8) + kc * 2.0 * s.rows_half * s.row_bytes) / rate / kc;
+  const double t_piece = (s.ne_halo * (s.row_bytes + 8) + kc * 2.0 * s.rows_half * s.sum_bytes) / rate / kc;
   double t = s.ne_own * (s.row_bytes + 8) / 7.5e12;
   for (int j = 0; j < kc; j++) {
     const double arrive = s.t_wire * (j + 1) / kc;
@@ -95,7 +126,8 @@ int LearningGraph::consumption_rule(int K, int len) {
   if (link_rows < 0 && halo_plan_) link_rows = gaib_halo_link_rows(halo_plan_);
   if (link_rows < 0) link_rows = gaib_graph_nc(half) / 7 + 1;
   // (classes: interior rows + the boundary rows' owned columns run before the first wait = all of dev_'s edges)
-  const SplitShape s{4.0 * len, wire_seconds(link_rows, len), gaib_graph_ne(dev_), gaib_graph_ne(half), gaib_graph_nv(half)};
+  const double row_bytes = (double)halo_elem_bytes(len) * len;  // (bf16 tables: half the bytes gathered and on the wire)
+  const SplitShape s{row_bytes, 4.0 * len, wire_seconds(link_rows, row_bytes), gaib_graph_ne(dev_), gaib_graph_ne(half), gaib_graph_nv(half)};
   double t = 0.0;
   const int best = best_consumption(s, K, &t);
   if (getenv("GAIB_PART_VERBOSE"))
@@ -107,6 +139,8 @@ int LearningGraph::consumption_rule(int K, int len) {
 int LearningGraph::halo_pieces(int len) {
   const int K = halo_slices();
   if (K <= 1 || part_mode_ < 0) return 1;
+  // bf16 callbacks (set_halo_bf16) hand the whole table over at end: an aggregation on bf16 tables takes it in one piece
+  if (!halo_plan_ && halo_elem_bytes(len) == 2) return 1;
   gaib_graph* half = part_mode_ == PART_SPLIT ? halo_dev_ : (part_mode_ == PART_CLASSES ? cls_bhalo_ : NULL);
   if (!half || gaib_graph_ne(half) == 0) return 1;  // (the one-pass forms wait for the whole exchange)
   int want = pieces_want_;
@@ -115,10 +149,12 @@ int LearningGraph::halo_pieces(int len) {
     if (e && *e) want = atoi(e);
   }
   if (want < 0) {
-    if (pieces_rule_k_ != K || pieces_rule_len_ != len) {
+    const int elem = halo_elem_bytes(len);
+    if (pieces_rule_k_ != K || pieces_rule_len_ != len || pieces_rule_elem_ != elem) {
       pieces_rule_ = consumption_rule(K, len);
       pieces_rule_k_ = K;
       pieces_rule_len_ = len;
+      pieces_rule_elem_ = elem;
     }
     want = pieces_rule_;
   }
@@ -201,8 +237,8 @@ int LearningGraph::partition_mode(int len) {
     int64_t link_rows = link_rows_;
     if (link_rows < 0 && halo_plan_) link_rows = gaib_halo_link_rows(halo_plan_);
     if (link_rows < 0) link_rows = (ne_bhalo ? gaib_graph_nc(halo_dev_) : 0) / 7 + 1;  // (a callback transport that gave no figure: 8 ranks)
-    const double row_bytes = 4.0 * len;
-    const double t_exchange = wire_seconds(link_rows, len);
+    const double row_bytes = (double)halo_elem_bytes(len) * len;  // 2 len under bf16 tables: a figure every rank holds
+    const double t_exchange = wire_seconds(link_rows, row_bytes);
     // one pass: the interior rows' work hides the exchange (where a fair share of the edges is interior), the boundary rows --
     // all rows where next to none is interior -- run over [owned | halo] after the last row has landed
     const double t_interior = few_interior ? 0.0 : ne_int * (row_bytes + 8) / 7.5e12;
@@ -210,7 +246,7 @@ int LearningGraph::partition_mode(int len) {
     // the column split (of the boundary rows; of all rows where next to none is interior): the owned-column work of ALL rows
     // hides the exchange, the halo-column half follows -- piece by piece where the exchange travels in slices (round 6), in as
     // many pieces as serve it best
-    const SplitShape shape{row_bytes, t_exchange, gaib_graph_ne(dev_), ne_bhalo, few_interior ? (int64_t)size() : n_boundary_};
+    const SplitShape shape{row_bytes, 4.0 * len, t_exchange, gaib_graph_ne(dev_), ne_bhalo, few_interior ? (int64_t)size() : n_boundary_};
     const int K = halo_slices();
     double t_split = 0.0;
     const int kc = best_consumption(shape, K > 1 ? K : 1, &t_split);

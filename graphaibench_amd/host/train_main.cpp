@@ -201,13 +201,26 @@ struct Trainer {
     init_comm();
     // the aggregations' feature tables: fp32, or bf16 with GAIB_AGG_DTYPE=bf16 (context option agg_bf16; GCN / SAGE only)
     const bool bf16 = aggregator::bf16_tables();
+    if (world > 1) {
+      // every rank reads the same environment; one that does not would exchange rows of another element size (the peer-to-peer
+      // transport refuses that at the first exchange, RCCL would mismatch its counts): agree before anything is built
+      double v[1] = {bf16 ? 1.0 : 0.0};
+      GAIB_OR_DIE(gaib_allreduce_host_f64(comm, v, 1));
+      if (v[0] != 0.0 && v[0] != (double)world) {
+        std::cerr << "rank " << rank << ": GAIB_AGG_DTYPE differs between the ranks (" << (int)v[0] << " of " << world << " ask for bf16)\n";
+        exit(EXIT_FAILURE);
+      }
+    }
     if (root())
-      std::cout << "aggregation tables: " << (bf16 ? (ARCH == gnn_arch::GAT ? "fp32 (bf16 asked; GAT gathers fp32)" : "bf16") : "fp32")
+      std::cout << "aggregation tables: "
+                << (bf16 ? (ARCH == gnn_arch::GAT ? "fp32 (bf16 asked; GAT gathers fp32)"
+                                                  : (world > 1 ? "bf16 (odd widths on a partition: fp32)" : "bf16"))
+                         : "fp32")
                 << "\n";
     if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root())
       std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
-    if (bf16 && world > 1) {
-      std::cerr << "GAIB_AGG_DTYPE=bf16 runs on one GPU only (a partitioned run gathers fp32 tables)\n";
+    if (bf16 && world > 1 && ARCH == gnn_arch::GAT) {
+      std::cerr << "GAIB_AGG_DTYPE=bf16 with GAT runs on one GPU only (GAT gathers fp32 tables; GCN and SAGE take bf16 tables on a partition)\n";
       exit(EXIT_FAILURE);
     }
     if (world > 1 && (subg_size > 0 || inductive)) {

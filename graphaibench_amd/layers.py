@@ -27,6 +27,7 @@ SIGNATURES = {
     "gaibl_graph_num_edges": (C.c_uint64, [_vp]),
     "gaibl_graph_free": (None, [_vp]),
     "gaibl_graph_set_halo": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "gaibl_graph_set_halo_bf16": (None, [_vp, _vp, _vp, _vp, _vp]),
     "gaibl_layer_create": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _f, _f, _f]),
     "gaibl_layer_free": (None, [_vp]),
     "gaibl_layer_forward": (None, [_vp, _vp]),
@@ -153,6 +154,16 @@ class LGraph:
         self._halo_graph = halo_graph  # keep alive
         load().gaibl_graph_set_halo(self.h, halo_graph.h, C.cast(self._cb[0], C.c_void_p),
                                     C.cast(self._cb[1], C.c_void_p), None)
+
+    def set_halo_bf16(self, halo_graph: capi.Graph, begin, end):
+        """the callbacks of set_halo for bf16 tables (option agg_bf16): begin(len:int, d_in:int) receives the rank's rows as bf16
+        bits, end(len:int) -> int returns the device pointer of a bf16 halo table"""
+        BEGIN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p)
+        END = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int)
+        self._cb16 = (BEGIN(lambda _u, n, p: begin(int(n), int(p or 0))), END(lambda _u, n: end(int(n))))
+        self._halo_graph = halo_graph  # keep alive
+        load().gaibl_graph_set_halo_bf16(self.h, halo_graph.h, C.cast(self._cb16[0], C.c_void_p),
+                                         C.cast(self._cb16[1], C.c_void_p), None)
 
     PART_AUTO, PART_SPLIT, PART_CLASSES, PART_ONEPASS, PART_ONEPASS_ALL = -1, 0, 1, 2, 3
     PART_NAMES = {0: "split", 1: "classes", 2: "onepass"}

@@ -465,6 +465,23 @@ int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const flo
 int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                          const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                          const float* d_W2, int len_out, float* d_out, int flags);
+/* bf16 tables on the row classes of a vertex-range partition (the functions above keep their refusals; the capability has
+ * names of its own).  d_in / d_in2 hold bf16 bits, everything else is fp32.
+ * gaib_spmm_part_bf16: with d_in2 == NULL gaib_spmm_ex on a bf16 table (n_first is ignored), with d_in2 != NULL gaib_spmm_2t on
+ * two bf16 tables (column ids >= n_first index d_in2); graphs with or without a row map; flags GAIB_ACCUMULATE | GAIB_RELU.
+ * gaib_spmm_gemm_part_bf16: gaib_spmm_gemm_2t on bf16 tables (d_in2 may be NULL, d_rows2 / d_W2 both or NULL), with all of its
+ * flags -- GAIB_RELU, GAIB_AGG_SCRATCH, GAIB_ACCUMULATE, GAIB_OVERLAPS_TRANSFER.  On a class graph a shape that
+ * gaib_spmm_gemm_fusable says 0 to returns GAIB_ERR_UNSUPPORTED, exactly where the fp32 call does.
+ * Every route decision is made on the fp32 sizes, and everything after the gather -- the row map, weights, CSR order with
+ * separate multiply and add, the heavy threshold and its combine order, the GAIB_ACCUMULATE continuation, the product -- is the
+ * fp32 class kernels' own: d_out (and d_agg unless GAIB_AGG_SCRATCH) are BIT-IDENTICAL to gaib_spmm_ex / gaib_spmm_2t /
+ * gaib_spmm_gemm(2) / gaib_spmm_gemm_2t on the tables widened to fp32 (gaib_cast_bf16_f32), for bf16 tables aligned to 8 B and
+ * d_out / d_agg to 16.  Tables of >= 4 GB in bf16 (either one) are gathered with 64-bit addresses. */
+int gaib_spmm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, const uint16_t* d_in,
+                        const uint16_t* d_in2, int64_t n_first, float* d_out, int flags);
+int gaib_spmm_gemm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+                             const uint16_t* d_in, const uint16_t* d_in2, int64_t n_first, float* d_agg, const float* d_W,
+                             int transW, const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags);
 
 /* ---- dense update: matmul -> sgemm_gpu -> cublasSgemm (math_functions.cu:321-343) --------
  * row-major C[M x N] = op(A)[M x K] . op(B)[K x N]  (+ C if accum).  fp32 MFMA. */
@@ -652,6 +669,16 @@ int gaib_halo_pieces(const gaib_halo* halo);
 int gaib_halo_piece_slice(int64_t rows, int n_pieces, int piece, int64_t* h_lo, int64_t* h_hi); /* pure arithmetic, no device */
 int gaib_halo_piece_ranges(const gaib_halo* halo, int piece, int cap, int64_t* h_begin, int64_t* h_end, int* h_n);
 int gaib_halo_exchange_wait_piece(gaib_halo* halo, int piece, const float** d_table);
+/* The same exchange carrying bf16 rows (raw bits) of `len` elements: 2 * len bytes per row -- through the same pack, chunks,
+ * direct sends, pieces and pulls (a bf16 row of even len is byte for byte an fp32 row of len / 2; over RCCL it travels as len / 2
+ * ncclFloat32 words), so gaib_halo_bytes_sent counts half of the fp32 exchange of the same plan and len.  d_rows (4-byte aligned)
+ * stays valid and unmodified until the end, as above.  An odd len: GAIB_ERR_UNSUPPORTED, decided locally before any collective
+ * step -- the same on every rank, no exchange is left pending.  An exchange is ended / waited for with the functions of the
+ * element type it was begun with: the other type is GAIB_ERR_INVALID and leaves the exchange in flight.  The peer-to-peer
+ * transport publishes the row bytes and the element size and refuses a mismatch between peers (bf16 tables on some ranks only). */
+int gaib_halo_exchange_begin_bf16(gaib_halo* halo, int len, const uint16_t* d_rows);
+int gaib_halo_exchange_end_bf16(gaib_halo* halo, const uint16_t** d_table);
+int gaib_halo_exchange_wait_piece_bf16(gaib_halo* halo, int piece, const uint16_t** d_table);
 
 /* the reverse of an exchange: d_halo_rows [halo rows x len] (the table's layout) holds this rank's partial sums for its
  * HALO vertices; they travel back to the owners, which add them to their own rows: d_rows[send_idx[k], :] += arrived[k, :],
@@ -705,7 +732,8 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * its guard gathers dense because too many rows of the gradient are over the packed row's capacity.
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
  * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16 / gaib_spmm_gemm_bf16; GAT ignores
- * it, a partitioned graph refuses it); "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
+ * it; on a partitioned graph gaib_spmm_part_bf16 / gaib_spmm_gemm_part_bf16 over a bf16 halo exchange, odd widths in fp32);
+ * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
  * kernel (row form, 8-row strip, buffer addressing, 65..128 columns): 0 = what ships, 16 / 32 = that depth.  Same bits. */

@@ -44,6 +44,14 @@ typedef void (*gaibl_halo_begin_fn)(void* user, int len, const float* d_in);
 typedef const float* (*gaibl_halo_end_fn)(void* user, int len);
 void gaibl_graph_set_halo(void* graph, void* halo_graph, gaibl_halo_begin_fn begin, gaibl_halo_end_fn end,
                           void* user);
+/* the same for bf16 tables (LearningGraph::set_halo_bf16; option "agg_bf16"): begin() receives the rank's rows as bf16 bits,
+ * end() returns the halo table as bf16 bits -- a driver with its own exchange moves half the bytes.  Serves the aggregations of
+ * even width; gaibl_graph_set_halo's pair (same `user`) may be given as well for the others.  The table is consumed whole
+ * (one piece) by the aggregations on bf16 tables. */
+typedef void (*gaibl_halo_begin16_fn)(void* user, int len, const uint16_t* d_in);
+typedef const uint16_t* (*gaibl_halo_end16_fn)(void* user, int len);
+void gaibl_graph_set_halo_bf16(void* graph, void* halo_graph, gaibl_halo_begin16_fn begin, gaibl_halo_end16_fn end,
+                               void* user);
 
 /* vertex-range partition built on the host (include/gnn/partition.h): every rank derives its share from the global
  * CSR.  gaibl_partition_array: which = 0 rowptr_own (int64) 1 colidx_own (uint32) 2 rowptr_halo (int64) 3 colidx_halo

@@ -13,7 +13,10 @@ class aggregator {
   // extension: bf16 feature tables (context option "agg_bf16" = 1, or GAIB_AGG_DTYPE=bf16): the GCN / SAGE aggregations
   // cast their table into a bf16 scratch and gather from there (gaib_spmm_bf16, gaib_spmm_gemm_bf16 where the product rides along; fp32 sums and output).  The scratch is
   // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
-  // epoch 0 eagerly).  GAT ignores the option; a partitioned graph (halo) refuses it.
+  // epoch 0 eagerly).  GAT ignores the option.  On a partitioned graph (halo) whose exchange can carry bf16 rows -- a halo plan,
+  // or set_halo_bf16's callbacks -- the aggregations of even width run on bf16 tables too: the owned rows are cast once, the
+  // exchange is begun from the scratch and the class kernels gather bf16 (gaib_spmm_part_bf16, gaib_spmm_gemm_part_bf16); odd
+  // widths run in fp32 there; a halo with fp32 callbacks only refuses the option.
   static bool bf16_tables();
   // extension: zero-suppressed gradient tables (context option "agg_zs", default 1).  The backward aggregation of a layer with
   // a relu gathers a table that is about half +0.0 (the d_relu has just masked it): aggregate_then_matmul packs such a table

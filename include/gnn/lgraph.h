@@ -30,6 +30,9 @@ class LearningGraph {
   void (*halo_begin_)(void* user, int len, const float* d_in);
   const float* (*halo_end_)(void* user, int len);
   void* halo_user_;
+  // the same pair for bf16 tables (set_halo_bf16): begin receives the rank's rows as bf16 bits, end returns a bf16 halo table
+  void (*halo_begin16_)(void* user, int len, const uint16_t* d_in);
+  const uint16_t* (*halo_end16_)(void* user, int len);
   gaib_halo* halo_plan_;  // the exchange behind the C ABI (gaib_halo_exchange_begin/end); set_halo_plan
   // GAT on a partition (include/gnn/partition.h build_gat_structures): the rows over one [owned | halo] column space,
   // the transposed structure and the edge permutation between them
@@ -62,7 +65,7 @@ class LearningGraph {
   int pieces_slices_;  // ... out of this many slices on the wire
   int pieces_want_;    // set_halo_consumption / GAIB_HALO_CONSUME; -1 = by the rule
   int pieces_rule_;    // what the rule chose (cached with the K and row length it chose for)
-  int pieces_rule_k_, pieces_rule_len_;
+  int pieces_rule_k_, pieces_rule_len_, pieces_rule_elem_;
   // callback transports (set_halo) bring the slice structure themselves: set_halo_pieces
   int cb_pieces_;
   std::vector<int64_t> cb_range_begin_, cb_range_end_;
@@ -77,10 +80,10 @@ class LearningGraph {
   LearningGraph(bool use_gpu)
       : is_device(use_gpu), num_vertices_(0), num_edges_(0), max_degree(0), rowptr_(NULL),
         colidx_(NULL), vertex_data_(NULL), edge_data_(NULL), dev_(NULL), halo_dev_(NULL),
-        halo_begin_(NULL), halo_end_(NULL), halo_user_(NULL), halo_plan_(NULL), gat_full_(NULL), gat_t_(NULL),
+        halo_begin_(NULL), halo_end_(NULL), halo_user_(NULL), halo_begin16_(NULL), halo_end16_(NULL), halo_plan_(NULL), gat_full_(NULL), gat_t_(NULL),
         gat_tperm_(NULL), gat_n_halo_(0), owns_partition_(false), cls_int_(NULL), cls_bown_(NULL), cls_bhalo_(NULL),
         cls_bfull_(NULL), part_mode_(-1), part_mode_wanted_(-1), n_boundary_(0), boundary_edges_(0), link_rows_(-1),
-        pieces_built_(0), pieces_slices_(0), pieces_want_(-1), pieces_rule_(0), pieces_rule_k_(0), pieces_rule_len_(0), cb_pieces_(1),
+        pieces_built_(0), pieces_slices_(0), pieces_want_(-1), pieces_rule_(0), pieces_rule_k_(0), pieces_rule_len_(0), pieces_rule_elem_(0), cb_pieces_(1),
         halo_wait_piece_(NULL) {
     for (gaib_graph*& p : pieces_) p = NULL;
   }
@@ -128,6 +131,17 @@ class LearningGraph {
     halo_dev_ = halo_graph;
     halo_begin_ = begin;
     halo_end_ = end;
+    halo_user_ = user;
+  }
+  // a driver with its own exchange and bf16 tables ("agg_bf16"): begin(user, len, rows as bf16 bits) / end(user, len) -> the halo
+  // table as bf16 bits.  Serves the aggregations of even width under "agg_bf16"; set_halo's fp32 pair (same `user`) may be given as
+  // well and then serves everything else (odd widths, "agg_bf16" = 0).  The whole exchange lands at end: an aggregation on
+  // bf16 tables consumes it in one piece, whatever slices set_halo_pieces names for the fp32 pair (halo_pieces).
+  void set_halo_bf16(gaib_graph* halo_graph, void (*begin16)(void*, int, const uint16_t*),
+                     const uint16_t* (*end16)(void*, int), void* user) {
+    halo_dev_ = halo_graph;
+    halo_begin16_ = begin16;
+    halo_end16_ = end16;
     halo_user_ = user;
   }
   // the same with the exchange running behind the C ABI (gaib_comm / gaib_halo: RCCL or peer-to-peer pull);
@@ -186,6 +200,13 @@ class LearningGraph {
   gaib_graph* halo_graph() { return halo_dev_; }
   void halo_begin(int len, const float* d_in);
   const float* halo_end(int len);
+  // bf16 tables on a partition: can this graph's exchange carry bf16 rows (a library plan, or set_halo_bf16's callbacks)?
+  bool halo_carries_bf16() const { return halo_plan_ != NULL || halo_begin16_ != NULL; }
+  // bytes per element of the tables an aggregation of `len` columns gathers and exchanges on this partition: 2 under "agg_bf16"
+  // where the exchange can carry bf16 rows and len is even (odd widths run on the fp32 path), else 4.  What the rules below price.
+  int halo_elem_bytes(int len) const;
+  void halo_begin_bf16(int len, const uint16_t* d_in);  // len even
+  const uint16_t* halo_end_bf16(int len);
   // ---- the halo-column half piece by piece (see pieces_ above) ----
   // callback transports: the exchange lands in n_pieces slices; range j = [begin[j], end[j]) of the halo table belongs to slice
   // piece[j]; wait_piece(user, k) returns the table once slice k is there (stream-ordered).  Plans: gaib_halo_set_pieces.
@@ -206,6 +227,7 @@ class LearningGraph {
   gaib_graph* halo_piece_graph(int j) { return pieces_[j]; }
   // the compute stream continues once piece j -- slices j K / K' ... (j + 1) K / K' - 1 -- has landed
   const float* halo_wait_piece(int j);
+  const uint16_t* halo_wait_piece_bf16(int j);  // (plans only)
   // device pointers, as the reference's ENABLE_GPU accessors return them.  Row pointers are
   // int64 in HBM (the reference's uint32 offsets overflow past 2^32 edges*features).
   const int64_t* row_start_ptr() const { return gaib_graph_rowptr(dev_); }
