@@ -152,7 +152,7 @@ __device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
 //   dwords 0-1  M0: bit l set when column 2l holds anything but bit pattern 0        dwords 2-3  M1: the same for column 2l + 1
 //   dword 4 + 2k  the k-th kept value of the even columns (M0, in lane order)        dword 5 + 2k  the k-th of the odd columns (M1)
 // i.e. the 8-B load of lane 2 + k holds the k-th value of either half, which is what lets the gather find a lane's two values
-// with ONE cross-lane read each and no choice between a lane's two dwords (see widen_zs).  Either half holds up to GAIB_ZS_CAP
+// with ONE cross-lane read each and no choice between a lane's two dwords (see zs_issue).  Either half holds up to GAIB_ZS_CAP
 // values; a row with more in one half keeps only its masks there and is read from the dense table.  Unpacking reproduces every bit.
 struct zs_t { uint32_t bits; };
 constexpr int GAIB_ZS_ROW_BYTES = 384;
@@ -200,37 +200,57 @@ struct RowGather {
   typedef typename std::conditional<ZS, u2_t, typename std::conditional<sizeof(E) == 2, typename Bf16Raw<VEC>::type,
                                                                            typename VecT<VEC>::type>::type>::type raw_t;
   static __device__ __forceinline__ typename VecT<VEC>::type widen(const raw_t& r) {
-    static_assert(!ZS, "zero-suppressed tables are expanded by widen_zs");
+    static_assert(!ZS, "zero-suppressed tables are expanded by zs_issue / zs_select");
     if constexpr (sizeof(E) == 2) return widen_bf16<VEC>(r);
     else return r;
   }
-  // Expansion of one zero-suppressed row where it is consumed.  Control flow is wave-uniform here and every lane is live: the masks
+  // Expansion of a zero-suppressed row where it is consumed.  Control flow is wave-uniform here and every lane is live: the masks
   // come from lanes 0 and 1; a lane's even column is component 0 of lane 2 + (set bits of M0 below the lane), its odd column
   // component 1 of lane 2 + (set bits of M1 below the lane) -- one ds_bpermute each (no LDS is allocated); suppressed columns are
   // +0.0 by a select with the mask itself as its lane mask.  Per row: 4 readlane, 4 mbcnt, 2 shifts, 2 selects next to the dense
-  // loop's 2 multiplies and 2 adds.  A row with more than GAIB_ZS_CAP values in a half (wave-uniform test on the popcounts) holds
-  // only its masks: it is read from the dense table, 512 B per row, and waited for.
-  // (cvec / idx: the wave's column ids and the lane that holds this row's -- read only on the over-capacity path)
-  __device__ __forceinline__ typename VecT<VEC>::type widen_zs(const raw_t& r, uint32_t cvec, int idx, uint32_t voff) const {
-    typedef unsigned long long u64;
-    const u64 m0 = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 0);
-    const u64 m1 = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 1) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 1);
-    typename VecT<VEC>::type v;
-    if (__builtin_expect(__builtin_popcountll(m0) > GAIB_ZS_CAP || __builtin_popcountll(m1) > GAIB_ZS_CAP, 0)) {
+  // loop's 2 multiplies and 2 adds.  A row with more than GAIB_ZS_CAP values in a half holds only its masks: it is read from the
+  // dense table, 512 B per row, and waited for.
+  // The expansion runs in two phases, for a GROUP of rows (wave_accumulate): the cross-lane reads of every row of the group are
+  // issued back to back and travel together, instead of one round trip after the other with a branch in between.
+  // zs_issue: masks to SGPRs, ranks, and the two permutes (p holds garbage above the masks' set bits and on an over-capacity
+  // row).  The capacity test stays on the scalar unit: a popcount is at most 64, so bit 6 of popcount + (63 - GAIB_ZS_CAP) says
+  // "more than GAIB_ZS_CAP"; the group ORs these sums and branches once (zs_over).
+  typedef unsigned long long zs_mask_t;
+  static __device__ __forceinline__ uint32_t zs_over_bits(zs_mask_t m0, zs_mask_t m1) {
+    return ((uint32_t)__builtin_popcountll(m0) + (uint32_t)(63 - GAIB_ZS_CAP)) | ((uint32_t)__builtin_popcountll(m1) + (uint32_t)(63 - GAIB_ZS_CAP));
+  }
+  static __device__ __forceinline__ bool zs_over(uint32_t over) { return (over & 64u) != 0; }
+  static __device__ __forceinline__ void zs_issue(const raw_t& r, raw_t& p, zs_mask_t& m0, zs_mask_t& m1, uint32_t& over) {
+    m0 = ((zs_mask_t)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 0);
+    m1 = ((zs_mask_t)(uint32_t)__builtin_amdgcn_readlane((int)r[1], 1) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r[0], 1);
+    over |= zs_over_bits(m0, m1);
+    const uint32_t l0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 2u));
+    const uint32_t l1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 2u));
+    p[0] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l0 << 2), (int)r[0]);
+    p[1] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l1 << 2), (int)r[1]);
+  }
+  // zs_fix: the rare path, entered for a whole group when any of its rows is over capacity.  Such a row is read from the dense
+  // table, 512 B, and waited for; the others are selected as on the fast path.  It returns the row rather than repairing
+  // registers and masks for a select shared with the fast path: values that join after the branch cost the FAST path a copy
+  // of every register and mask of the group, and a wait for the dense load left to the join would drain the gathers in flight.
+  __device__ __forceinline__ typename VecT<VEC>::type zs_fix(const raw_t& p, zs_mask_t m0, zs_mask_t m1, uint32_t cvec, int idx, uint32_t voff) const {
+    if (zs_over(zs_over_bits(m0, m1))) {
       const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cvec, idx);
       const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * 512u), 0);
+      typename VecT<VEC>::type v;
       v[0] = __uint_as_float(d[0]);
       v[1] = __uint_as_float(d[1]);
       return v;
     }
-    const uint32_t l0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 2u));
-    const uint32_t l1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 2u));
-    const uint32_t x0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l0 << 2), (int)r[0]);
-    const uint32_t x1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l1 << 2), (int)r[1]);
-    // the zero fill, written out: from `(m >> lane) & 1` the compiler builds a 64-bit shift, two ands and a 64-bit compare per value
+    return zs_select(p, m0, m1);
+  }
+  // zs_select: the zero fill, with the mask itself as lane mask (written out: from `(m >> lane) & 1` the compiler builds a
+  // 64-bit shift, two ands and a 64-bit compare per value)
+  static __device__ __forceinline__ typename VecT<VEC>::type zs_select(const raw_t& r, zs_mask_t m0, zs_mask_t m1) {
     uint32_t k0, k1;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k0) : "v"(x0), "s"(m0));
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k1) : "v"(x1), "s"(m1));
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k0) : "v"(r[0]), "s"(m0));
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(k1) : "v"(r[1]), "s"(m1));
+    typename VecT<VEC>::type v;
     v[0] = __uint_as_float(k0);
     v[1] = __uint_as_float(k1);
     return v;
@@ -296,6 +316,49 @@ struct RowGather {
   }
 };
 
+// Rows per group of the packed expansion (RowGather::zs_issue / zs_fix / zs_select): the cross-lane reads of a group travel
+// together and the group has ONE branch, for the over-capacity path.  A row of a group in flight holds four mask SGPRs, so the
+// group size is bounded by the scalar registers: 4 compiles without spilling them in the hot loop, 8 spills (LEDGER 10.4).
+#ifndef GAIB_ZS_GROUP
+#define GAIB_ZS_GROUP 4
+#endif
+
+// G packed rows x[xo .. xo + G - 1] of a batch or of a tail piece -- edges j0 .. j0 + G - 1 of the wave's chunk -- expanded and
+// accumulated in CSR order: every product and every addition of the dense loop, in its order.  (The products and sums are
+// written on the 2-vector: left to pair them up itself, the compiler pairs the products of two ROWS and shuffles.)
+template <int G, int CT, int WMODE, int U, typename gather_t>
+__device__ __forceinline__ void zs_accumulate_group(const gather_t& gather, const typename gather_t::raw_t (&x)[U][CT], int xo, uint32_t c, float w,
+                                                    float roww, int j0, const uint32_t (&voff)[CT], typename VecT<2>::type (&acc)[CT]) {
+  typename gather_t::zs_mask_t m0[G][CT], m1[G][CT];
+  typename gather_t::raw_t p[G][CT];
+  uint32_t over = 0u;
+#pragma unroll
+  for (int u = 0; u < G; ++u)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) gather_t::zs_issue(x[xo + u][ct], p[u][ct], m0[u][ct], m1[u][ct], over);
+  if (__builtin_expect(gather_t::zs_over(over), 0)) {  // (wave-uniform: the masks are scalars)
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const float wj = (WMODE == 0) ? roww : readlane_f(w, j0 + u);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const typename VecT<2>::type t = gather.zs_fix(p[u][ct], m0[u][ct], m1[u][ct], c, j0 + u, voff[ct]) * wj;
+        acc[ct] = acc[ct] + t;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const float wj = (WMODE == 0) ? roww : readlane_f(w, j0 + u);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const typename VecT<2>::type t = gather_t::zs_select(p[u][ct], m0[u][ct], m1[u][ct]) * wj;
+        acc[ct] = acc[ct] + t;
+      }
+    }
+  }
+}
+
 // ---- the shared per-wave edge loop: accumulate edges [eb, ee) of one row -------------
 // chunk_stride: distance between this wave's 64-edge chunks (64 for a whole row, 64*W when
 // W waves share a row).
@@ -346,17 +409,20 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
       // all U gathers are issued before the first one is consumed: without the fence the scheduler may interleave
       // loads and uses to save registers (seen in the two-product fused kernel: vmcnt(1) after every load)
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (gather_t::ZS) {
+        constexpr int H = GAIB_ZS_GROUP < U ? GAIB_ZS_GROUP : U;
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, j + u));
+        for (int u = 0; u < U; u += H) zs_accumulate_group<H, CT, WMODE>(gather, x, u, c, w, roww, j + u, voff, acc);
+      } else {
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          float wsel = wj;
-          if constexpr (MH) wsel = wv[u][ct];
-          if constexpr (gather_t::ZS)
-            vacc<VEC>(acc[ct], wsel, gather.widen_zs(x[u][ct], c, j + u, voff[ct]));
-          else
+        for (int u = 0; u < U; ++u) {
+          const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, j + u));
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct) {
+            float wsel = wj;
+            if constexpr (MH) wsel = wv[u][ct];
             vacc<VEC>(acc[ct], wsel, gather_t::widen(x[u][ct]));
+          }
         }
       }
     }
@@ -382,18 +448,26 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
 #pragma unroll
       for (int p = U / 2; p >= 1; p >>= 1) {
         if (r & p) {
+          if constexpr (gather_t::ZS) {  // a piece is one group, or whole groups
+            if (p >= GAIB_ZS_GROUP) {
 #pragma unroll
-          for (int u = 0; u < p; ++u) {
-            const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, jj + u));
+              for (int u = 0; u < p; u += GAIB_ZS_GROUP)
+                zs_accumulate_group<GAIB_ZS_GROUP, CT, WMODE>(gather, x, p + u, c, w, roww, jj + u, voff, acc);
+            } else if (p == 8) zs_accumulate_group<8, CT, WMODE>(gather, x, p, c, w, roww, jj, voff, acc);
+            else if (p == 4) zs_accumulate_group<4, CT, WMODE>(gather, x, p, c, w, roww, jj, voff, acc);
+            else if (p == 2) zs_accumulate_group<2, CT, WMODE>(gather, x, p, c, w, roww, jj, voff, acc);
+            else zs_accumulate_group<1, CT, WMODE>(gather, x, p, c, w, roww, jj, voff, acc);
+          } else {
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              // (the tail is short: its per-head weights are fetched at the point of use)
-              float wh = wj;
-              if constexpr (MH) wh = load_edge_w<WMODE>(a, base + jj + u, hd[ct]);
-              if constexpr (gather_t::ZS)
-                vacc<VEC>(acc[ct], wh, gather.widen_zs(x[p + u][ct], c, jj + u, voff[ct]));
-              else
+            for (int u = 0; u < p; ++u) {
+              const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, jj + u));
+#pragma unroll
+              for (int ct = 0; ct < CT; ++ct) {
+                // (the tail is short: its per-head weights are fetched at the point of use)
+                float wh = wj;
+                if constexpr (MH) wh = load_edge_w<WMODE>(a, base + jj + u, hd[ct]);
                 vacc<VEC>(acc[ct], wh, gather_t::widen(x[p + u][ct]));
+              }
             }
           }
           jj += p;

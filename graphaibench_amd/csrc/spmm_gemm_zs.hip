@@ -3,7 +3,7 @@
 //   agg[i,:] = sum_e w_e * unpack(zs[col_e,:]) ;  y[i,:] = act(agg[i,:] . op(W) [+ rows2[i,:] . op(W2)])
 // A relu-masked gradient is about half +0.0: packed, a row of 128 floats is three 128-B lines instead of four, and the
 // aggregation's time follows the lines a gathered row touches.  Only the gather differs from the fp32 instantiations of spmm.hip:
-// a row in flight is the two dwords a lane asked for, expanded with cross-lane permutes where it is consumed (RowGather::widen_zs);
+// a row in flight is the two dwords a lane asked for, expanded with cross-lane permutes where it is consumed, four rows at a time (RowGather::zs_issue / zs_select);
 // suppressed columns enter as +0.0, so every product w * x and every addition of the fp32 kernels is still made, in the same
 // order: agg and y are bit-identical to gaib_spmm_gemm(2) on the dense table.
 // Row forms only (8-row strip, or the 2-row strip with two products), per-row and per-edge weights, buffer addressing; the

@@ -72,13 +72,14 @@ static bool bf16_for(Graph& g, int len) {
 // Where the packed launch set (pack + heavy + fused) stops beating the dense one: the share of rows over capacity from which
 // the layers gather dense.  An over-capacity row costs a dense 512-B gather that the wave waits for on top of its packed one.
 // scripts/zs_aggregation.py sweeps the kept share of the gradient from 40 to 90 % on the products-shaped graph
-// (profiles/zs/zs_aggregation.json): packed wins by 0.32 ms at 50 % kept (0.02 % of the rows over capacity), by 0.10 ms at 60 %
-// (3.5 %), loses 3.8 ms at 70 % (55 %) -- about 6.3 ms per unit share, so the two sets cross at 5 % of the rows.
-static const double ZS_GUARD_SHARE = 0.05;
+// (profiles/zs/zs_gather_groups.json, LEDGER 10.4): packed wins by 1.13 ms at 50 % kept (0.02 % of the rows over capacity), by
+// 0.65 ms at 60 % (3.5 %), by 0.15 ms at 62 % (7.3 %), loses 0.68 ms at 64 % (13.9 %) -- the two sets cross near 8.5 % of the rows.
+static const double ZS_GUARD_SHARE = 0.08;
 static const unsigned ZS_PROBE_EVERY = 8;
-// Two products (SAGE's backward: the self term rides along, the 2-row-strip kernel at 128 VGPRs with 8-9 spilled): the packed
-// kernels exist and are bit-identical (gaib_spmm_gemm2_zs), but the layers take them only once they are MEASURED faster than the
-// dense call on the SAGE step -- until then SAGE gathers dense (LEDGER 10.3).
+// Two products (SAGE's backward: the self term rides along, the 2-row-strip kernel at 127 VGPRs with 10 spilled): the packed
+// kernels exist and are bit-identical (gaib_spmm_gemm2_zs).  With the grouped expansion the packed call is the faster one at the
+// kernel level (8.83 -> 8.14 ms at 50 % kept, pack included; LEDGER 10.4), but it has not been measured on the SAGE layer step in
+// alternating pairs, and tests/test_gpu_zs.py holds SAGE to the dense gather: until both are settled SAGE gathers dense.
 static const bool ZS_TWO_PRODUCTS = false;
 bool aggregator::zs_tables() {
   int64_t v = 0;
