@@ -103,6 +103,8 @@ SIGNATURES = {
     "gaib_gat_alpha_grads": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gaib_gat_backward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_edge_transpose_mh": (_i, [_vp, _vp, _i, _vp, _vp]),
     "gaib_gat_scores": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_sddmm": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -748,6 +750,35 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gat_backward_fused")
+        return True
+
+    def gat_forward_fused_bf16(self, g, h, alpha_l, alpha_r, out, row_stats, eps: float = 0.2, heads: int = 1,
+                               relu: bool = False) -> bool:
+        """gat_forward_fused over a torch.bfloat16 table h [nv, len]: the bits of the fp32 call on the widened table.
+        False = not applicable"""
+        import torch
+
+        assert h.dtype == torch.bfloat16 and h.dim() == 2
+        rc = self.lib.gaib_gat_forward_fused_bf16(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(alpha_l), _ptr(alpha_r),
+                                                  eps, int(relu), _ptr(out), _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_forward_fused_bf16")
+        return True
+
+    def gat_backward_fused_bf16(self, g, feat, grad, fwd_out, alpha_l, alpha_r, grad_out, lgrad, rgrad, row_stats,
+                                eps: float = 0.2, heads: int = 1) -> bool:
+        """gat_backward_fused (row-statistics form) over torch.bfloat16 tables feat and grad [nv, len].  False = not
+        applicable (nothing touched)"""
+        import torch
+
+        assert feat.dtype == torch.bfloat16 and grad.dtype == torch.bfloat16 and feat.dim() == 2
+        rc = self.lib.gaib_gat_backward_fused_bf16(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad),
+                                                   _ptr(fwd_out), _ptr(alpha_l), _ptr(alpha_r), _ptr(row_stats), eps,
+                                                   _ptr(grad_out), _ptr(lgrad), _ptr(rgrad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_backward_fused_bf16")
         return True
 
     def edge_transpose(self, g, in_e, out_e, heads: int = 1):

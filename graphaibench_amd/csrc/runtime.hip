@@ -83,6 +83,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->comm_reserve_cus = -1;  // unset: the communicator's default applies (an explicit 0 stays 0)
   c->comm_reserve_default = 0;
   c->gat_interleave = 0;
+  c->gat_bf16 = 0;
   c->gat_bwd_pk = 0;  // measured, round 6: the packed-math sweep saves a third of the VALU instructions and nothing at the real
                       // column ids (6.27 vs 6.25 ms at the reddit shape: the sweep is bound by the L2 -> fabric gather stream there)
   c->gat_chunk_xcd = 0;
@@ -526,6 +527,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_flat_ring")) *h_value = ctx->spmm_flat_ring;
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
+  else if (!strcmp(key, "gat_bf16")) *h_value = ctx->gat_bf16;
   else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
   else if (!strcmp(key, "capturing")) *h_value = ctx->capturing;  // a recording is open (gaib_capture_begin)
   else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
@@ -579,6 +581,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "agg_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->agg_bf16 = (int)value;
+  } else if (!strcmp(key, "gat_bf16")) {
+    GAIB_CHECK(value == 0 || value == 1, "gat_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
+    ctx->gat_bf16 = (int)value;
   } else if (!strcmp(key, "agg_zs")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_zs must be 0 (dense gradient tables) or 1 (zero-suppressed)");
     ctx->agg_zs = (int)value;

@@ -552,6 +552,10 @@ void GAT_Aggregator::release() {
   }
   if (d_attn_masks) GAIB_OR_DIE(gaib_free(c, d_attn_masks));
   d_attn_masks = NULL;
+  if (d_hb16) GAIB_OR_DIE(gaib_free(c, d_hb16));
+  d_hb16 = NULL;
+  hb16_elems = 0;
+  fwd_bf16 = false;
   drop_cap = tbuf_floats = ptab_floats = pvec_floats = pgrad_floats = prec_floats = stats_floats = 0;
   stats_valid = part_fused_last = dropped_last = false;
   last_graph = NULL;
@@ -726,8 +730,21 @@ void GAT_Aggregator::d_aggregate_partition(int len, Graph& g, const float* grad_
   GAIB_OR_DIE(gaib_halo_reduce(g.halo_plan(), len, d_pout + n_own * len, grad_out));
 }
 
+bool GAT_Aggregator::gat_bf16_tables() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "gat_bf16", &v));
+  return v != 0;
+}
+// bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32
+static void no_gat_bf16_partition() {
+  fprintf(stderr, "GPU error: gat_bf16 (GAIB_GAT_DTYPE=bf16) on a partitioned GAT graph: the one-sweep kernels over bf16 tables "
+          "run on whole graphs only\n");
+  exit(EXIT_FAILURE);
+}
+
 void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   count_edges(g);
+  if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
   if (g.gat_full_graph()) {
     aggregate_partition(len, g, in, out);
     return;
@@ -748,8 +765,24 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
       stats_floats = need;
     }
     OpTimer t(OP_SPARSEMM);
-    const int rc = gaib_gat_forward_fused(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0,
-                                          out, d_row_stats);
+    fwd_bf16 = false;
+    int rc = GAIB_ERR_UNSUPPORTED;
+    if (gat_bf16_tables()) {
+      const size_t elems = (size_t)g.size() * len;
+      if (elems > hb16_elems) {
+        if (d_hb16) GAIB_OR_DIE(gaib_free(C(), d_hb16));
+        d_hb16 = NULL;
+        GAIB_OR_DIE(gaib_malloc(C(), elems * sizeof(uint16_t), (void**)&d_hb16));
+        hb16_elems = elems;
+      }
+      GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)elems, in, d_hb16));
+      rc = gaib_gat_forward_fused_bf16(C(), dev(g), len, heads, d_hb16, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0, out,
+                                       d_row_stats);
+      fwd_bf16 = rc == GAIB_OK;
+    }
+    if (rc == GAIB_ERR_UNSUPPORTED)
+      rc = gaib_gat_forward_fused(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0, out,
+                                  d_row_stats);
     if (rc == GAIB_OK) {
       fuse_relu = false;
       stats_valid = true;
@@ -761,6 +794,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     if (rc != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(rc);
   }
   stats_valid = false;
+  fwd_bf16 = false;
   if (g.sizeEdges() > num_edges) {  // a larger graph than the one the layer was built on (sampling -> full graph)
     num_edges = g.sizeEdges();
     float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t};
@@ -791,6 +825,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
 void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const float* grad_in,
                                  float* grad_out) {
   count_edges(g);
+  if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
   if (g.gat_full_graph()) {
     d_aggregate_partition(len, g, grad_in, grad_out);
     return;
@@ -805,9 +840,15 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
       float_malloc_device64(need, d_tbuf);
       tbuf_floats = need;
     }
-    const int rc = gaib_gat_backward_fused(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_alpha_r,
-                                           stats_valid ? NULL : d_norm_scores, stats_valid ? d_row_stats : NULL, epsilon,
-                                           d_tbuf, d_alpha_lgrad, d_alpha_rgrad);
+    int rc = GAIB_ERR_UNSUPPORTED;
+    // bf16 tables: the kept copy of h is reused, one cast (of grad_in) is made
+    if (fwd_bf16 && stats_valid && feat_in == last_in && &g == last_graph && len == last_len)
+      rc = gaib_gat_backward_fused_bf16(C(), dev(g), len, heads, d_hb16, to_bf16(g.size(), len, grad_in), fwd_out, d_alpha_l,
+                                        d_alpha_r, d_row_stats, epsilon, d_tbuf, d_alpha_lgrad, d_alpha_rgrad);
+    if (rc == GAIB_ERR_UNSUPPORTED)
+      rc = gaib_gat_backward_fused(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_alpha_r,
+                                   stats_valid ? NULL : d_norm_scores, stats_valid ? d_row_stats : NULL, epsilon, d_tbuf,
+                                   d_alpha_lgrad, d_alpha_rgrad);
     if (rc == GAIB_OK) {
       fwd_out = NULL;
       fwd_out_given = false;

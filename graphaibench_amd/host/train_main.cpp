@@ -199,7 +199,17 @@ struct Trainer {
     if (subg_size > 0 || ARCH == gnn_arch::GAT) use_l2norm = use_dense = true;
     if (subg_size > 0) inductive = 1;  // net.cpp:160
     init_comm();
-    // the aggregations' feature tables: fp32, or bf16 with GAIB_AGG_DTYPE=bf16 (context option agg_bf16; GCN / SAGE only)
+    if (ARCH == gnn_arch::GAT) {
+      // GAT's own tables: fp32, or bf16 with GAIB_GAT_DTYPE=bf16 (context option gat_bf16; whole graphs only)
+      int64_t gat16 = 0;
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_bf16", &gat16));
+      if (gat16 && world > 1) {  // (every rank reads the same environment: refused before any collective)
+        std::cerr << "GAIB_GAT_DTYPE=bf16 (gat_bf16) runs on one GPU only: the one-sweep GAT kernels over bf16 tables take whole graphs\n";
+        exit(EXIT_FAILURE);
+      }
+      if (world == 1) std::cout << "GAT tables: " << (gat16 ? "bf16" : "fp32") << "\n";
+    }
+    // the aggregations' feature tables: fp32, or bf16 with GAIB_AGG_DTYPE=bf16 (context option agg_bf16; GCN / SAGE only -- GAT has GAIB_GAT_DTYPE / gat_bf16)
     const bool bf16 = aggregator::bf16_tables();
     if (world > 1) {
       // every rank reads the same environment; one that does not would exchange rows of another element size (the peer-to-peer

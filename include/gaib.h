@@ -310,6 +310,30 @@ int gaib_gat_backward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, co
  * array exists at all.  Same cover as gaib_gat_backward_fused (option "gat_fused_fwd"); GAIB_ERR_UNSUPPORTED otherwise. */
 int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
                            const float* d_alpha_r, float epsilon, int relu, float* d_out, float* d_row_stats);
+/* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
+ * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
+ * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
+ * gradients.  Everything else (alpha vectors, forward output, row statistics, the per-vertex records inside the sweep) is fp32.
+ * Outputs: fp32, and BIT-IDENTICAL to gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) called on the
+ * tables widened to fp32 (gaib_cast_bf16_f32) under the same options: "gat_fused_unroll", "gat_chunk_xcd" and "gat_bwd_pk" are
+ * honoured exactly as by the fp32 calls -- with gat_bwd_pk = 1 the result has the bits of the fp32 packed-math sweep, over a
+ * table row of len dwords (h_k in the low half, grad_k in the high half) followed by the fp32 records, 4 len + 16 heads bytes,
+ * the table below 4 GB; on a shape the packed-math sweep does not cover (a head of 32 lanes) the option changes nothing, as
+ * in fp32.  "gat_interleave" is ignored by the bf16 calls (it changes no bits in fp32 either).
+ * Cover and refusals are those of the fp32 calls: len 32 / 64 / 128 with 1, 2, 4, 8 or 16 heads of >= 4 columns, square graphs
+ * only (no _rect forms), options "gat_fused_fwd" / "gat_fused_bwd" = 0 switch them off, a misaligned buffer (bf16 tables: 8
+ * bytes, fp32 buffers: 16) -> GAIB_ERR_UNSUPPORTED with nothing touched; a graph without rows is handled as by the fp32 calls
+ * (forward: GAIB_ERR_UNSUPPORTED; backward: zero alpha gradients, GAIB_OK).  d_row_stats == NULL in backward is
+ * GAIB_ERR_INVALID: there is no attention-array form.
+ * Profile: the launches are timed under the fp32 calls' keys "gat_fwd_fused" / "gat_bwd_fused" with the fp32 byte formula, so
+ * the achieved rate of such a row is a work rate in dense (fp32) bytes. */
+int gaib_gat_forward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_h_bf16,
+                                const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float* d_out,
+                                float* d_row_stats);
+int gaib_gat_backward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_feat_bf16,
+                                 const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_alpha_l,
+                                 const float* d_alpha_r, const float* d_row_stats, float epsilon, float* d_grad_out,
+                                 float* d_alpha_lgrad, float* d_alpha_rgrad);
 /* Test / diagnostic: d_sign_out [ne][heads] (uint8) = (t_e > 0) of every pre-activation score a_l.h[i] + a_r.h[col_e]
  * EXACTLY as the one-sweep kernels form it.  leaky_relu' jumps at 0, so a score within rounding of zero takes either
  * slope in two correct fp32 evaluations; a comparison of the alpha gradients with an fp64 evaluation imposes these signs
@@ -732,7 +756,10 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * its guard gathers dense because too many rows of the gradient are over the packed row's capacity.
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
  * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16 / gaib_spmm_gemm_bf16; GAT ignores
- * it; on a partitioned graph gaib_spmm_part_bf16 / gaib_spmm_gemm_part_bf16 over a bf16 halo exchange, odd widths in fp32);
+ * it and has "gat_bf16" instead; on a partitioned graph gaib_spmm_part_bf16 / gaib_spmm_gemm_part_bf16 over a bf16 halo exchange, odd widths in fp32);
+ * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
+ * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs, no
+ * attention dropout); a partitioned GAT graph refuses the option;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
@@ -740,7 +767,7 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
- * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
+ * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "agg_zs", "agg_zs_paused", "capturing" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 

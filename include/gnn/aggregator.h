@@ -13,7 +13,7 @@ class aggregator {
   // extension: bf16 feature tables (context option "agg_bf16" = 1, or GAIB_AGG_DTYPE=bf16): the GCN / SAGE aggregations
   // cast their table into a bf16 scratch and gather from there (gaib_spmm_bf16, gaib_spmm_gemm_bf16 where the product rides along; fp32 sums and output).  The scratch is
   // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
-  // epoch 0 eagerly).  GAT ignores the option.  On a partitioned graph (halo) whose exchange can carry bf16 rows -- a halo plan,
+  // epoch 0 eagerly).  GAT ignores the option (it has "gat_bf16", see GAT_Aggregator).  On a partitioned graph (halo) whose exchange can carry bf16 rows -- a halo plan,
   // or set_halo_bf16's callbacks -- the aggregations of even width run on bf16 tables too: the owned rows are cast once, the
   // exchange is begun from the scratch and the class kernels gather bf16 (gaib_spmm_part_bf16, gaib_spmm_gemm_part_bf16); odd
   // widths run in fp32 there; a halo with fp32 callbacks only refuses the option.
@@ -157,5 +157,18 @@ class GAT_Aggregator : public aggregator {
   const float* last_in;
   int last_len;
   void materialise_scores();
+  // extension: bf16 tables (context option "gat_bf16" = 1, or GAIB_GAT_DTYPE=bf16).  On a whole graph, without attention
+  // dropout and at a shape the one-sweep kernels cover, aggregate() casts `in` into d_hb16 and runs
+  // gaib_gat_forward_fused_bf16; d_aggregate() then casts grad_in (process-wide scratch) and runs
+  // gaib_gat_backward_fused_bf16 on the KEPT copy of h -- when that forward ran on bf16, the layer's forward output is at
+  // hand and feat_in is the table that forward cast; in every other case the fp32 path runs as without the option.  The
+  // layer then computes forward and backward of the fp32 layer on the rounded h and grad.  d_hb16 belongs to the aggregator:
+  // it lives from a layer's forward to its backward while other layers run.  It grows on demand like d_tbuf, which has to
+  // happen outside a capture.  A partitioned GAT graph refuses the option.  (norm_scores_ptr() after such a forward forms the
+  // attention array from the fp32 `in`, like the staged path it serves: within the bf16 rounding of what the sweep used.)
+  static bool gat_bf16_tables();
+  uint16_t* d_hb16 = NULL;
+  size_t hb16_elems = 0;
+  bool fwd_bf16 = false;  // the last forward ran on d_hb16 = bf16(last_in) over last_graph
   optimizer* alpha_opt;
 };
