@@ -54,6 +54,8 @@ SIGNATURES = {
     "gaib_scale_f32": (_i, [_vp, _i64, _f, _vp]),
     "gaib_cast_f32_bf16": (_i, [_vp, _i64, _vp, _vp]),
     "gaib_cast_bf16_f32": (_i, [_vp, _i64, _vp, _vp]),
+    "gaib_cast_f32_bf16_rows": (_i, [_vp, _i64, _i, _vp, _i64, _vp]),
+    "gaib_bf16_row_stride": (_i, [_vp, _vp, _i, C.POINTER(_i64)]),
     "gaib_pack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "gaib_unpack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "gaib_graph_create": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _i, _pp]),
@@ -78,11 +80,14 @@ SIGNATURES = {
     "gaib_spmm_gemm2": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_mh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i]),
     "gaib_spmm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "gaib_spmm_bf16_ld": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _i]),
     "gaib_spmm_gemm_zs_route": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "gaib_spmm_gemm_zs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "gaib_spmm_gemm2_zs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_gemm_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "gaib_spmm_gemm2_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    "gaib_spmm_gemm_bf16_ld": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "gaib_spmm_gemm2_bf16_ld": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_graph_split_classes": (_i, [_vp, _vp, _vp, _pp, _pp, _pp, _pp, C.POINTER(_i64), C.POINTER(_i64), _i]),
     "gaib_graph_split_pieces": (_i, [_vp, _vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _pp]),
     "gaib_graph_set_row_map": (_i, [_vp, _vp, _vp, _i64]),
@@ -530,12 +535,36 @@ class Context:
         _check(self.lib.gaib_cast_bf16_f32(self.h, x.numel(), _ptr(x), _ptr(out)), "gaib_cast_bf16_f32")
         return out
 
-    def spmm_bf16(self, g: "Graph", kind: int, x, out, edge_w=None, accumulate: bool = False, relu: bool = False):
-        """gaib_spmm_bf16: x a [nc x len] torch.bfloat16 table, out fp32 [nv x len]"""
+    def cast_f32_bf16_rows(self, x, ld: int, out=None):
+        """gaib_cast_f32_bf16_rows: x fp32 [rows x len] -> torch.bfloat16 [rows x ld], ld >= len; the columns behind len are +0.0"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+        rows, length = x.shape
+        if out is None:
+            out = torch.empty((rows, ld), dtype=torch.bfloat16, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == rows * ld
+        _check(self.lib.gaib_cast_f32_bf16_rows(self.h, rows, length, _ptr(x), ld, _ptr(out)), "gaib_cast_f32_bf16_rows")
+        return out
+
+    def bf16_row_stride(self, g: "Graph", length: int) -> int:
+        """gaib_bf16_row_stride: the row stride (elements) at which a bf16 table of `length` columns is gathered from on g"""
+        v = _i64()
+        _check(self.lib.gaib_bf16_row_stride(self.h, g.h, length, C.byref(v)), "gaib_bf16_row_stride")
+        return v.value
+
+    def spmm_bf16(self, g: "Graph", kind: int, x, out, edge_w=None, accumulate: bool = False, relu: bool = False, ld=None):
+        """gaib_spmm_bf16: x a [nc x len] torch.bfloat16 table, out fp32 [nv x len].  ld: gaib_spmm_bf16_ld -- x is [nc x ld],
+        its first out.shape[1] columns are the table"""
         import torch
 
         assert x.is_contiguous() and out.is_contiguous() and x.dim() == 2 and x.dtype == torch.bfloat16
         flags = (1 if accumulate else 0) | (2 if relu else 0)
+        if ld is not None:
+            assert x.shape[1] == ld
+            _check(self.lib.gaib_spmm_bf16_ld(self.h, g.h, kind, _ptr(edge_w), out.shape[1], ld, _ptr(x), _ptr(out), flags),
+                   "gaib_spmm_bf16_ld")
+            return out
         _check(self.lib.gaib_spmm_bf16(self.h, g.h, kind, _ptr(edge_w), x.shape[1], _ptr(x), _ptr(out), flags),
                "gaib_spmm_bf16")
         return out
@@ -558,9 +587,10 @@ class Context:
         return out
 
     def spmm_gemm_bf16(self, g: "Graph", kind: int, x, agg, W, out, transW: bool = False, relu: bool = False,
-                       agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None):
+                       agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None, ld=None):
         """gaib_spmm_gemm_bf16 / gaib_spmm_gemm2_bf16: spmm_gemm with x a [nc x len_in] torch.bfloat16 table; agg, W, rows2, W2
-        and out fp32.  The bits of spmm_gemm on the widened table."""
+        and out fp32.  The bits of spmm_gemm on the widened table.  ld: the _ld entry points -- x is [nc x ld], its first
+        len_in columns are the table."""
         import torch
 
         assert x.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
@@ -568,6 +598,17 @@ class Context:
         len_in, len_out = agg.shape[1], out.shape[1]
         assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))
         flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0)
+        if ld is not None:
+            assert x.shape[1] == ld
+            if rows2 is not None:
+                assert rows2.is_contiguous() and W2.is_contiguous() and W2.shape == W.shape and rows2.shape[1] == len_in
+                _check(self.lib.gaib_spmm_gemm2_bf16_ld(self.h, g.h, kind, _ptr(edge_w), len_in, ld, _ptr(x), _ptr(agg), _ptr(W),
+                                                        1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags),
+                       "gaib_spmm_gemm2_bf16_ld")
+                return out
+            _check(self.lib.gaib_spmm_gemm_bf16_ld(self.h, g.h, kind, _ptr(edge_w), len_in, ld, _ptr(x), _ptr(agg), _ptr(W),
+                                                   1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm_bf16_ld")
+            return out
         if rows2 is not None:
             assert rows2.is_contiguous() and W2.is_contiguous() and W2.shape == W.shape and rows2.shape[1] == len_in
             _check(self.lib.gaib_spmm_gemm2_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),

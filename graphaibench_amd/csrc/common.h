@@ -88,6 +88,8 @@ struct gaib_ctx {
   int spmm_hot_bytes;        // L2 budget for the hot rows of gather mode 3
   int spmm_bf16_layout;      // gaib_spmm_bf16's lane layout: 0 = one row per wave (auto lane width), 4 / 8 = sub-wave rows of 4 / 8 elements per lane
   int spmm_bf16_fuse_u;      // benchmark only: gathers in flight of the bf16 fused kernel's headline variant, 0 = default (GAIB_BF16_FUSE_U), 16 / 32
+  int spmm_bf16_pad;         // 1 = gaib_bf16_row_stride line-aligns odd-width bf16 rows where that saves >10 % of the gathered lines, 0 = never
+  int agg_bf16_ld_last;      // written by the layer library: the row stride (elements) of the bf16 table it cast last
   int agg_zs;                // 1: the layer library's GCN / SAGE backward gathers a relu-masked gradient from its zero-suppressed image (gaib_pack_zs, gaib_spmm_gemm_zs)
   int agg_zs_paused;         // written by the layer library's guard: 1 while it gathers dense because too many rows are over capacity
   int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16, gaib_spmm_gemm_bf16)

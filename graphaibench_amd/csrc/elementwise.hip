@@ -526,6 +526,47 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_scalar_kernel(int64_t n, co
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint16_t)f32_to_bf16_bits(in[i]);
 }
+// rows of `len` floats -> rows of `ld` bf16 elements (ld >= len), the columns behind len written as +0.0: the table a strided
+// gather reads (gaib_spmm_bf16_ld), made in the one pass the cast is anyway.  One thread per 8 output elements (ld % 8 == 0,
+// out 16-B aligned): one 16-B store; the load side reads the thread's 8 floats as two 16-B loads where the input row allows
+// (in 16-B aligned, len % 4 == 0), else float by float (a 47-float row starts on any 4-B boundary).
+template <bool VIN>
+__global__ __launch_bounds__(256) void cast_f32_bf16_rows_kernel(int64_t n8, int len, int ld8, const float* __restrict__ in,
+                                                                 uint16_t* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+    const int64_t r = i / ld8;
+    const int c = (int)(i - r * ld8) * 8;
+    const float* src = in + r * len + c;
+    float v[8];
+    if (VIN && c + 8 <= len) {
+      const f4 a = reinterpret_cast<const f4*>(src)[0], b = reinterpret_cast<const f4*>(src)[1];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = a[k], v[4 + k] = b[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = c + k < len ? src[k] : 0.f;
+    }
+    u4v o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned lo = c + 2 * k < len ? f32_to_bf16_bits(v[2 * k]) : 0u;  // (a pad column is +0.0 whatever sign a 0.f would round to)
+      const unsigned hi = c + 2 * k + 1 < len ? f32_to_bf16_bits(v[2 * k + 1]) : 0u;
+      o[k] = lo | (hi << 16);
+    }
+    reinterpret_cast<u4v*>(out)[i] = o;
+  }
+}
+// element-wise form (ld % 8 != 0 or a misaligned output): one output element per thread
+__global__ __launch_bounds__(256) void cast_f32_bf16_rows_scalar_kernel(int64_t n, int len, int64_t ld, const float* __restrict__ in,
+                                                                        uint16_t* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t r = i / ld;
+    const int64_t c = i - r * ld;
+    out[i] = c < len ? (uint16_t)f32_to_bf16_bits(in[r * len + c]) : (uint16_t)0;
+  }
+}
 __global__ __launch_bounds__(256) void cast_bf16_f32_scalar_kernel(int64_t n, const uint16_t* __restrict__ in,
                                                                    float* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -657,6 +698,28 @@ extern "C" int gaib_cast_f32_bf16(gaib_ctx* ctx, int64_t n, const float* d_in, u
   ProfScope ps(ctx, "cast_f32_bf16", 6.0 * (double)n);
   if (vec) cast_f32_bf16_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, ctx->stream>>>(n, d_in, d_out, 1);
   else cast_f32_bf16_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, d_in, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_cast_f32_bf16_rows(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, int64_t ld_out, uint16_t* d_out) {
+  GAIB_CHECK(ctx, "gaib_cast_f32_bf16_rows: NULL ctx");
+  GAIB_CHECK(rows >= 0 && len >= 0, "gaib_cast_f32_bf16_rows: rows or len < 0");
+  GAIB_CHECK(ld_out >= len, "gaib_cast_f32_bf16_rows: ld_out (%lld) below len (%d)", (long long)ld_out, len);
+  if (rows == 0 || ld_out == 0) return GAIB_OK;
+  if (ld_out == len) return gaib_cast_f32_bf16(ctx, rows * len, d_in, d_out);  // dense rows: the flat cast
+  GAIB_CHECK(d_out && (d_in || len == 0), "gaib_cast_f32_bf16_rows: NULL argument");
+  GAIB_CHECK((const void*)d_in != (const void*)d_out, "gaib_cast_f32_bf16_rows: in and out must not alias");
+  const int64_t n = rows * ld_out;
+  ProfScope ps(ctx, "cast_f32_bf16", 4.0 * (double)rows * len + 2.0 * (double)n);
+  if (ld_out % 8 == 0 && ((uintptr_t)d_out & 15) == 0 && ld_out / 8 <= 0x7fffffff) {
+    const bool vin = len % 4 == 0 && ((uintptr_t)d_in & 15) == 0;
+    const unsigned grid = stream_grid(n / 8, 256);
+    if (vin) cast_f32_bf16_rows_kernel<true><<<grid, 256, 0, ctx->stream>>>(n / 8, len, (int)(ld_out / 8), d_in, d_out);
+    else cast_f32_bf16_rows_kernel<false><<<grid, 256, 0, ctx->stream>>>(n / 8, len, (int)(ld_out / 8), d_in, d_out);
+  } else {
+    cast_f32_bf16_rows_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, len, ld_out, d_in, d_out);
+  }
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

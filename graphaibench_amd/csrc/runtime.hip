@@ -66,6 +66,8 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_hot_bytes = 3 << 20;
   c->spmm_bf16_layout = 0;
   c->spmm_bf16_fuse_u = 0;
+  c->spmm_bf16_pad = 1;
+  c->agg_bf16_ld_last = 0;
   c->agg_bf16 = 0;
   c->agg_zs = 1;
   c->agg_zs_paused = 0;
@@ -533,6 +535,8 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
   else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
   else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
+  else if (!strcmp(key, "spmm_bf16_pad")) *h_value = ctx->spmm_bf16_pad;
+  else if (!strcmp(key, "agg_bf16_ld_last")) *h_value = ctx->agg_bf16_ld_last;
   else {
     gaib_set_error("gaib_get_option: no readable option '%s'", key);
     return GAIB_ERR_INVALID;
@@ -578,6 +582,12 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "spmm_bf16_fuse_u")) {
     GAIB_CHECK(value == 0 || value == 16 || value == 32, "spmm_bf16_fuse_u must be 0 (default), 16 or 32");
     ctx->spmm_bf16_fuse_u = (int)value;
+  } else if (!strcmp(key, "spmm_bf16_pad")) {
+    GAIB_CHECK(value == 0 || value == 1, "spmm_bf16_pad must be 0 (dense stride) or 1 (line-aligned rows where they save lines)");
+    ctx->spmm_bf16_pad = (int)value;
+  } else if (!strcmp(key, "agg_bf16_ld_last")) {
+    GAIB_CHECK(value >= 0 && value <= (1 << 30), "agg_bf16_ld_last out of range");
+    ctx->agg_bf16_ld_last = (int)value;
   } else if (!strcmp(key, "agg_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->agg_bf16 = (int)value;

@@ -227,13 +227,34 @@ static int64_t pad_stride_floats(const gaib_ctx* ctx, const gaib_graph* g, int l
   return 0;
 }
 
+// The same rule on bf16 rows (2 B per element, rows at any 2-B alignment when packed): a 47-wide row is 94 B -- 1.72 lines
+// packed, one line from a 128-B stride --, a 100-wide one 200 B -- 2.55 lines packed, two from a 256-B stride.  No copy pass
+// here: the cast that makes the bf16 table writes it at this stride (gaib_cast_f32_bf16_rows), the aggregation reads it
+// through gaib_spmm_bf16_ld / gaib_spmm_gemm(2)_bf16_ld.  Returns the stride in elements, len where nothing is gained.
+static int64_t bf16_row_stride(const gaib_ctx* ctx, const gaib_graph* g, int len) {
+  const int bytes = len * 2, stride = (bytes + 63) & ~63;
+  if (ctx->spmm_bf16_pad && !g->row_map && len > 16 && stride != bytes && g->ne > 4 * g->nc &&
+      lines_strided(bytes, stride) < 0.9 * (1.0 + (bytes - 2) / 128.0))
+    return stride / 2;
+  return len;
+}
+
+extern "C" int gaib_bf16_row_stride(gaib_ctx* ctx, gaib_graph* g, int len, int64_t* ld) {
+  GAIB_CHECK(ctx && g && ld, "gaib_bf16_row_stride: NULL argument");
+  GAIB_CHECK(len >= 0, "gaib_bf16_row_stride: len < 0");
+  *ld = bf16_row_stride(ctx, g, len);
+  return GAIB_OK;
+}
+
 // fills the launch arguments shared by every aggregation path; *wmode = kernel weight mode
 // d_in2 / n_first: column ids >= n_first index the second table d_in2 (row id - n_first) -- NULL: one table
 // bf16: d_in (and d_in2) hold bf16 bits (gaib_spmm_bf16, gaib_spmm_part_bf16): gathered as they are (no re-strided copy, no
 // cold-column flags), and the buffer-descriptor path is chosen by the tables' bf16 byte sizes
+// ld_bf16 > 0: the row stride of a bf16 table in elements (gaib_spmm_bf16_ld; the caller cast it that way: gaib_cast_f32_bf16_rows)
+// -- it enters the gather addresses, the descriptor size and the 4 GB test, nothing else
 static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                       const float* d_in, float* d_out, int flags, int heads, SpmmArgs* pa, int* wmode,
-                      const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false) {
+                      const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false, int64_t ld_bf16 = 0) {
   SpmmArgs& a = *pa;
   const bool part = g->row_map != nullptr || d_in2 != nullptr;  // a row class of a partition (spmm_part.hip)
   GAIB_CHECK(!d_in2 || (n_first >= 0 && n_first <= g->nc), "gaib_spmm: n_first (%lld) outside the %lld columns",
@@ -285,6 +306,7 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
       a.ld = lp;
     }
   }
+  if (bf16 && ld_bf16 > 0) a.ld = ld_bf16;
   // feature table = nc rows of a.ld elements (4 B, or 2 B in bf16); the 32-bit buffer path needs it below 4 GB
   const int64_t table_bytes = (d_in2 ? n_first : g->nc) * a.ld * (bf16 ? 2 : 4);
   a.in_bytes = table_bytes < ((int64_t)1 << 32) ? (uint32_t)table_bytes : 0u;
@@ -441,7 +463,8 @@ extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in
 static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                           const float* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                           const float* d_W2, int len_out, float* d_out, int flags, const float* d_in2 = nullptr,
-                          int64_t n_first = 0, bool bf16 = false, const void* d_zs = nullptr, bool zs_query = false) {
+                          int64_t n_first = 0, bool bf16 = false, const void* d_zs = nullptr, bool zs_query = false,
+                          int64_t ld_bf16 = 0) {
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm: NULL ctx/graph");
   GAIB_CHECK(len_in >= 0 && len_out >= 0, "gaib_spmm_gemm: negative length");
   GAIB_CHECK(ctx->device == g->device, "gaib_spmm_gemm: graph lives on device %d, ctx on %d", g->device,
@@ -493,7 +516,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   // accumulating GEMM below runs over rows [0, nv) of rows2 / out; it gets GAIB_ERR_UNSUPPORTED further down)
   if (!part && shape_ok && dual && fuse_strip_rows(kpad, len_out, true) == 0 && fuse_strip_rows(kpad, len_out, false) != 0) {
     GAIB_TRY(spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out,
-                            flags & ~GAIB_RELU, nullptr, 0, bf16));
+                            flags & ~GAIB_RELU, nullptr, 0, bf16, nullptr, false, ld_bf16));
     return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2,
                          GAIB_ACCUMULATE | ((flags & GAIB_RELU) ? GAIB_RELU : 0), d_out);
   }
@@ -520,7 +543,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   if (kslab) {
     SpmmArgs a0;
     int wmode = 0;
-    GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode, nullptr, 0, bf16));
+    GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode, nullptr, 0, bf16, ld_bf16));
     const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;
     const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * len_in + 255) & ~(size_t)255;
     GAIB_TRY(gaib_ws_reserve(ctx, wt_bytes + hv_bytes + 256));
@@ -536,7 +559,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
     }
     for (int k0 = 0; k0 < len_in; k0 += 128) {
       SpmmArgs a = a0;
-      // (bf16: the slab offset and in_bytes count bf16 elements)
+      // (bf16: the slab offset and in_bytes count bf16 elements; the offset is one of columns, whatever the row stride)
       a.in = bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0) : a0.in + k0;
       a.ncols = len_in - k0 < 128 ? len_in - k0 : 128;
       a.accumulate = 0;
@@ -569,7 +592,8 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   }
   if (!fusable) {
     const int act = (flags & GAIB_RELU) ? GAIB_RELU : 0;
-    if (bf16) GAIB_TRY(gaib_spmm_bf16(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const uint16_t*>(d_in), d_agg, flags & GAIB_ACCUMULATE));
+    if (bf16) GAIB_TRY(gaib_spmm_bf16_ld(ctx, g, weight_kind, d_edge_w, len_in, ld_bf16 > 0 ? ld_bf16 : len_in,
+                                         reinterpret_cast<const uint16_t*>(d_in), d_agg, flags & GAIB_ACCUMULATE));
     else GAIB_TRY(spmm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, flags & GAIB_ACCUMULATE));
     GAIB_TRY(gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_agg, d_W, dual ? 0 : act, d_out));
     if (dual) return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2, GAIB_ACCUMULATE | act, d_out);
@@ -577,7 +601,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   }
   SpmmArgs a;
   int wmode = 0;
-  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first, bf16));
+  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first, bf16, ld_bf16));
   a.accumulate = 0;  // (the fused kernel takes the partial sums through f.agg_in)
   if (flags & GAIB_AGG_SCRATCH) a.out = nullptr;  // the caller does not read agg: skip its store
   // scratch: op(W) (and op(W2)) k-contiguous + the heavy rows' aggregates + the tile counter
@@ -707,11 +731,12 @@ namespace {
 template <int WMODE>
 int dispatch_bf16(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a0, int len) {
   typedef uint16_t bf16_t;
-  // widest vector the row length and base pointers allow: VEC elements = 2 VEC bytes per gather, 4 VEC bytes per store
+  // widest vector the row length, the row stride and the base pointers allow: VEC elements = 2 VEC bytes per gather, 4 VEC bytes
+  // per store (a lane never reaches past column len: the columns behind it in a strided table are not read)
   const uintptr_t ai = (uintptr_t)a0.in, ao = (uintptr_t)a0.out;
   int vmax = 1;
   for (int v = 8; v > 1; v >>= 1)
-    if (len % v == 0 && (ai & (2 * v - 1)) == 0 && (ao & ((v >= 4 ? 16 : 4 * v) - 1)) == 0) {
+    if (len % v == 0 && a0.ld % v == 0 && (ai & (2 * v - 1)) == 0 && (ao & ((v >= 4 ? 16 : 4 * v) - 1)) == 0) {
       vmax = v;
       break;
     }
@@ -766,10 +791,14 @@ int dispatch_bf16(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a0, int len) {
 
 }  // namespace
 
-extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
-                              const uint16_t* d_in, float* d_out, int flags) {
+// ld: the table's row stride in elements -- len (dense), or a multiple of 4 above it (rows keep the table's 8-B alignment).  It
+// enters the gather addresses only: every route decision below is made on len, so a strided call sums in the dense call's order.
+extern "C" int gaib_spmm_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, int64_t ld,
+                                 const uint16_t* d_in, float* d_out, int flags) {
   GAIB_CHECK(ctx && g, "gaib_spmm_bf16: NULL ctx/graph");
   GAIB_CHECK(len >= 0, "gaib_spmm_bf16: len < 0");
+  GAIB_CHECK(ld == len || (ld > len && ld % 4 == 0), "gaib_spmm_bf16_ld: row stride ld (%lld) must be len (%d) or a multiple of 4 above it",
+             (long long)ld, len);
   GAIB_CHECK((flags & ~(GAIB_ACCUMULATE | GAIB_RELU)) == 0, "gaib_spmm_bf16: unsupported flags %d", flags);
   GAIB_CHECK(ctx->device == g->device, "gaib_spmm_bf16: graph lives on device %d, ctx on %d", g->device, ctx->device);
   if (g->row_map) {
@@ -782,7 +811,7 @@ extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, con
   SpmmArgs a;
   int wmode = 0;
   GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len, reinterpret_cast<const float*>(d_in), d_out, flags, 1, &a, &wmode,
-                      nullptr, 0, true));
+                      nullptr, 0, true, ld));
   // the fp32 path's choice of the ordered-chunk form, made on what IT would see (the row stride of its possibly re-strided
   // table; 16-B aligned rows) -- the same graph and len take the same summation order
   const int64_t ld32 = pad_stride_floats(ctx, g, len, false) > 0 ? pad_stride_floats(ctx, g, len, false) : len;
@@ -802,13 +831,21 @@ extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, con
   }
 }
 
+extern "C" int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
+                              const uint16_t* d_in, float* d_out, int flags) {
+  return gaib_spmm_bf16_ld(ctx, g, weight_kind, d_edge_w, len, len, d_in, d_out, flags);
+}
+
 // agg = A.widen(in) ; out = act(agg . op(W) [+ rows2 . op(W2)]) with `in` in bf16 (raw bits), everything else fp32: the route
 // gaib_spmm_gemm(2) takes on the widened table, run with the bf16 gather -- d_agg (unless scratch) and d_out bit-identical to
 // that call, for d_in aligned to 8 B and d_agg to 16.
-static int spmm_gemm_bf16_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
+// ld: the table's row stride in elements (see gaib_spmm_bf16_ld); the route is chosen on len_in, as for the dense table.
+static int spmm_gemm_bf16_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
                                 const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                                 const float* d_W2, int len_out, float* d_out, int flags) {
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm_bf16: NULL ctx/graph");
+  GAIB_CHECK(ld == len_in || (ld > len_in && ld % 4 == 0),
+             "gaib_spmm_gemm_bf16_ld: row stride ld (%lld) must be len_in (%d) or a multiple of 4 above it", (long long)ld, len_in);
   GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm_bf16: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which "
                                                 "aggregate fp32 tables");
   if (g->row_map) {
@@ -816,13 +853,28 @@ static int spmm_gemm_bf16_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, c
     return GAIB_ERR_UNSUPPORTED;
   }
   return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2,
-                        d_W2, len_out, d_out, flags, nullptr, 0, true);
+                        d_W2, len_out, d_out, flags, nullptr, 0, true, nullptr, false, ld);
 }
 
 extern "C" int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                                    const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
                                    int flags) {
-  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out,
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out,
+                              d_out, flags);
+}
+
+extern "C" int gaib_spmm_gemm_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                                      const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
+                                      int flags) {
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, ld, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out,
+                              d_out, flags);
+}
+
+extern "C" int gaib_spmm_gemm2_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                                       const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                                       const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_bf16_ld: NULL second operand");
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, ld, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out,
                               flags);
 }
 
@@ -830,8 +882,8 @@ extern "C" int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kin
                                     const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                                     const float* d_W2, int len_out, float* d_out, int flags) {
   GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_bf16: NULL second operand");
-  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out,
-                              flags);
+  return spmm_gemm_bf16_entry(ctx, g, weight_kind, d_edge_w, len_in, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out,
+                              d_out, flags);
 }
 
 // ---- bf16 feature tables on the row classes of a vertex-range partition (spmm_part_bf16.hip) ----------------------------------

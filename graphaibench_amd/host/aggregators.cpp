@@ -50,6 +50,17 @@ static const uint16_t* to_bf16(size_t rows, int len, const float* in) {
   GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)n, in, t));
   return t;
 }
+// ... of a WHOLE graph `dg`, at the row stride the library's rule names for it (gaib_bf16_row_stride: odd widths line-aligned
+// where that saves gathered lines; the strided cast is the one pass the cast is anyway).  *ld = that stride, which the caller
+// hands to the _ld aggregation; option "agg_bf16_ld_last" reports it.  Partitions and GAT keep the dense stride (to_bf16 above).
+static const uint16_t* to_bf16(gaib_graph* dg, int len, const float* in, int64_t* ld) {
+  const size_t rows = (size_t)gaib_graph_nc(dg);
+  GAIB_OR_DIE(gaib_bf16_row_stride(C(), dg, len, ld));
+  uint16_t* t = bf16_table(rows * (size_t)*ld);
+  GAIB_OR_DIE(gaib_cast_f32_bf16_rows(C(), (int64_t)rows, len, in, *ld, t));
+  GAIB_OR_DIE(gaib_set_option(C(), "agg_bf16_ld_last", *ld));
+  return t;
+}
 // bf16 tables on a vertex-range partition need an exchange that carries bf16 rows: a library plan (set_halo_plan) or bf16
 // callbacks (set_halo_bf16).  A halo set with the fp32 callbacks alone (set_halo) cannot: refused as before.
 static void no_bf16_halo(Graph& g) {
@@ -242,7 +253,9 @@ static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* 
       return;
     }
     gaib_graph* dg = dev(g);
-    GAIB_OR_DIE(gaib_spmm_bf16(C(), dg, kind, NULL, len, to_bf16((size_t)gaib_graph_nc(dg), len, in), out, act));
+    int64_t ld = len;
+    const uint16_t* tab = to_bf16(dg, len, in, &ld);
+    GAIB_OR_DIE(gaib_spmm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, out, act));
     return;
   }
   if (!g.has_halo()) {
@@ -338,11 +351,12 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     // bf16 table: the fused kernel gathers from it -- the route (and the bits) of the fp32 branch below on the rounded table
     gaib_graph* dg = dev(g);
     const int fl = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
-    const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(dg), len, in);
+    int64_t ld = len;
+    const uint16_t* tab = to_bf16(dg, len, in, &ld);
     if (rows2)
-      GAIB_OR_DIE(gaib_spmm_gemm2_bf16(C(), dg, kind, NULL, len, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
+      GAIB_OR_DIE(gaib_spmm_gemm2_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
     else
-      GAIB_OR_DIE(gaib_spmm_gemm_bf16(C(), dg, kind, NULL, len, tab, agg, W, transW ? 1 : 0, len_out, out, fl));
+      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, fl));
     return;
   }
   const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);

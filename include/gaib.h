@@ -111,6 +111,11 @@ int gaib_scale_f32(gaib_ctx* ctx, int64_t n, float alpha, float* d_x);
  * of its bits, quiet bit set).  bf16 -> f32 is exact (bits << 16).  in and out must not alias. */
 int gaib_cast_f32_bf16(gaib_ctx* ctx, int64_t n, const float* d_in, uint16_t* d_out);
 int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in, float* d_out);
+/* gaib_cast_f32_bf16 into rows with a stride: d_in is dense fp32 [rows x len], d_out bf16 bits [rows x ld_out], ld_out >= len.
+ * Columns < len carry gaib_cast_f32_bf16's rounding, columns len .. ld_out - 1 are written as +0.0; ld_out == len gives the bits
+ * of gaib_cast_f32_bf16.  One pass; 16-byte stores where ld_out % 8 == 0 and d_out is 16-B aligned.  The table the _ld
+ * aggregation calls below gather from, at the stride gaib_bf16_row_stride names. */
+int gaib_cast_f32_bf16_rows(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, int64_t ld_out, uint16_t* d_out);
 
 /* Zero-suppressed tables ("zs"): a row of 128 floats as 384 bytes on a 128-byte boundary -- two 64-bit masks (M0: bit l set when
  * column 2l holds anything but bit pattern 0x00000000; M1: the same for column 2l + 1), then pairs of fp32 bit patterns: dword
@@ -231,6 +236,20 @@ int gaib_spmm_ex(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_e
  * with 64-bit addresses. */
 int gaib_spmm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, const uint16_t* d_in,
                    float* d_out, int flags);
+/* bf16 tables with a row stride.  The time of a gather follows the 128-byte lines a row touches: packed bf16 rows of 47 (94 B)
+ * or 100 columns (200 B) touch 1.72 / 2.55 lines on average, rows that start on line boundaries 1 / 2.
+ * gaib_bf16_row_stride: *ld = the stride (elements) a table of len columns should be cast to for graph g -- the row bytes
+ * rounded up to 64 where that saves more than 10 % of the lines (64 at len 47, 128 at len 100), else len (64, 128, 200, 256,
+ * ...); always len for len <= 16, on a graph with ne <= 4 nc or with a row map, and under option "spmm_bf16_pad" = 0.
+ * gaib_spmm_bf16_ld: gaib_spmm_bf16 on d_in = [nc x ld] bf16 bits whose first len columns are the table.  ld == len, or
+ * ld > len with ld % 4 == 0 (rows keep the table's 8-B alignment); anything else is GAIB_ERR_INVALID before any launch.  The
+ * columns behind len are never read into a result (they may hold anything).  Lane layout, ordered chunks, heavy threshold and
+ * column slabs are chosen on len as in the dense call, so d_out is BIT-IDENTICAL to gaib_spmm_bf16 on the same values stored
+ * densely; ld enters the gather addresses, the buffer-descriptor size nc * ld * 2 and the 4 GB test only.  Profile keys and
+ * algorithmic bytes (2 len per gathered row) are the dense call's.  Refusals as gaib_spmm_bf16. */
+int gaib_bf16_row_stride(gaib_ctx* ctx, gaib_graph* g, int len, int64_t* ld);
+int gaib_spmm_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, int64_t ld,
+                      const uint16_t* d_in, float* d_out, int flags);
 /* multi-head attention weights: d_edge_w is [ne][heads]; column c uses head c / (len/heads).
  * weight_kind must be GAIB_W_EDGE or GAIB_W_EDGE_T when heads > 1. */
 int gaib_spmm_mh(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int heads,
@@ -489,6 +508,15 @@ int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const flo
 int gaib_spmm_gemm2_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                          const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                          const float* d_W2, int len_out, float* d_out, int flags);
+/* ... over d_in = [nc x ld] bf16 bits (the contract of gaib_spmm_bf16_ld: ld == len_in, or ld > len_in with ld % 4 == 0): the
+ * route -- fused, K-slabs, fused + accumulating GEMM, ordered chunks, two kernels, the edge stream -- is the dense call's, chosen
+ * on len_in; d_agg and d_out are bit-identical to it, the columns behind len_in reach no output. */
+int gaib_spmm_gemm_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                           const uint16_t* d_in, float* d_agg, const float* d_W, int transW, int len_out, float* d_out,
+                           int flags);
+int gaib_spmm_gemm2_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                            const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                            const float* d_W2, int len_out, float* d_out, int flags);
 /* bf16 tables on the row classes of a vertex-range partition (the functions above keep their refusals; the capability has
  * names of its own).  d_in / d_in2 hold bf16 bits, everything else is fp32.
  * gaib_spmm_part_bf16: with d_in2 == NULL gaib_spmm_ex on a bf16 table (n_first is ignored), with d_in2 != NULL gaib_spmm_2t on
@@ -755,7 +783,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * SAGE's two-product backward until that form is measured faster than the dense one.  "agg_zs_paused" (readable; written by that library): 1 while
  * its guard gathers dense because too many rows of the gradient are over the packed row's capacity.
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
- * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16 + gaib_spmm_bf16 / gaib_spmm_gemm_bf16; GAT ignores
+ * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16_rows at gaib_bf16_row_stride's stride +
+ * gaib_spmm_bf16_ld / gaib_spmm_gemm_bf16_ld on whole graphs -- "spmm_bf16_pad" (default 1): 0 = always the dense stride;
+ * "agg_bf16_ld_last" (readable; written by that library): the stride of the table it cast last --; GAT ignores
  * it and has "gat_bf16" instead; on a partitioned graph gaib_spmm_part_bf16 / gaib_spmm_gemm_part_bf16 over a bf16 halo exchange, odd widths in fp32);
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
  * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs, no
@@ -768,7 +798,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
- * "agg_zs", "agg_zs_paused", "capturing" */
+ * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_paused", "capturing" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -17,6 +17,15 @@ and SAGE layer steps at 128 and 256 (fp32 | bf16 tables | bf16 tables under spmm
 had a bf16 form).
 
     python scripts/bf16_aggregation.py --fused [--scale 1.0] [--iters 20] [--out PATH]
+
+--strided: odd-width bf16 tables at a line-aligned row stride (default record profiles/bf16/bf16_strided.json).  At 47 and 100
+columns, GCN weights: after a bit check of gaib_spmm_bf16_ld against gaib_spmm_bf16, the dense-stride leg (gaib_cast_f32_bf16 +
+gaib_spmm_bf16) against the padded one (gaib_cast_f32_bf16_rows to 64 / 128 elements + gaib_spmm_bf16_ld), INTERLEAVED as above,
+--iters rounds (at least 20) after warm-up; the gathers alone and the two casts alone the same way; median, min and max per
+leg, the stream-copy rate before and after.  `gate`: the padded leg's median below the dense one's by more than the two
+legs' min-max spreads together -- what gaib_bf16_row_stride's rule has to meet at a width to keep its stride there.
+
+    python scripts/bf16_aggregation.py --strided [--scale 1.0] [--iters 20] [--out PATH]
 """
 import argparse
 import json
@@ -162,15 +171,68 @@ def fused_main(args):
     print("wrote", out_path)
 
 
+def strided_main(args):
+    iters = max(args.iters, 20)
+    ctx = L.init(0)
+    sg = synth.make("ogbn-products", device="cuda", scale=args.scale)
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    ctx.sync()
+    nv, ne = g.nv, g.ne
+    copy0 = ctx.probe_stream_copy()
+    rec = dict(graph="ogbn-products synth", nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=copy0, widths=[])
+    print(f"nv={nv} ne={ne} stream copy {copy0:.0f} GB/s", flush=True)
+    none = lambda: None
+    for d in (47, 100):
+        ld = ((2 * d + 63) // 64 * 64) // 2  # the row bytes rounded up to 64: the rule's candidate, whatever the rule says today
+        x = torch.randn(nv, d, device="cuda")
+        xb = torch.empty(nv, d, dtype=torch.bfloat16, device="cuda")
+        xs = torch.empty(nv, ld, dtype=torch.bfloat16, device="cuda")
+        out, ref = torch.empty(nv, d, device="cuda"), torch.empty(nv, d, device="cuda")
+        ctx.cast_f32_bf16(x, xb)
+        ctx.cast_f32_bf16_rows(x, ld, xs)
+        ctx.spmm_bf16(g, capi.W_GCN, xb, ref)
+        ctx.spmm_bf16(g, capi.W_GCN, xs, out, ld=ld)
+        torch.cuda.synchronize()
+        assert torch.equal(xs[:, :d].contiguous().view(torch.int16), xb.view(torch.int16)) and not bool(xs[:, d:].view(torch.int16).any())
+        assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), f"strided bf16 aggregation differs from the dense one at {d}"
+        del ref
+        cast_d, cast_p = (lambda: ctx.cast_f32_bf16(x, xb)), (lambda: ctx.cast_f32_bf16_rows(x, ld, xs))
+        gather_d = lambda: ctx.spmm_bf16(g, capi.W_GCN, xb, out)
+        gather_p = lambda: ctx.spmm_bf16(g, capi.W_GCN, xs, out, ld=ld)
+        r = dict(d=d, ld=ld, rule_ld=ctx.bf16_row_stride(g, d), kind="W_GCN", bit_identical=True)
+        r["cast_and_gather"] = interleaved(dict(dense=(none, lambda: (cast_d(), gather_d())), padded=(none, lambda: (cast_p(), gather_p()))), iters)
+        r["gather"] = interleaved(dict(dense=(none, gather_d), padded=(none, gather_p)), iters)
+        r["cast"] = interleaved(dict(dense=(none, cast_d), padded=(none, cast_p)), iters)
+        a, b = r["cast_and_gather"]["dense"], r["cast_and_gather"]["padded"]
+        r["gate"] = bool(a["median_ms"] - b["median_ms"] > (a["max_ms"] - a["min_ms"]) + (b["max_ms"] - b["min_ms"]))
+        b16 = ne * (2.0 * d + 8) + nv * 4.0 * d + (nv + 1) * 8.0  # algorithmic: 2 d bytes per gathered row at either stride
+        for k in ("dense", "padded"):
+            r["gather"][k]["frac_8tbs"] = b16 / r["gather"][k]["median_ms"] / 1e6 / 8000
+        print(json.dumps(r), flush=True)
+        rec["widths"].append(r)
+        del x, xb, xs, out
+        torch.cuda.empty_cache()
+    rec["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    out_path = Path(args.out) if args.out else ROOT / "profiles" / "bf16" / "bf16_strided.json"
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(rec, indent=1) + "\n")
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--fused", action="store_true", help="the fused aggregation + product over a bf16 table (see above)")
+    ap.add_argument("--strided", action="store_true", help="odd-width bf16 tables at a line-aligned row stride (see above)")
     args = ap.parse_args()
     if args.fused:
         return fused_main(args)
+    if args.strided:
+        return strided_main(args)
     if args.out is None:
         args.out = str(ROOT / "profiles" / "bf16" / "bf16_aggregation.json")
     ctx = L.init(0)  # the layer library's context: the layer steps below run on it too
