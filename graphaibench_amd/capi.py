@@ -118,6 +118,8 @@ SIGNATURES = {
     "gaib_sgemm": (_i, [_vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _i, _vp]),
     "gaib_sgemm_drelu": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
     "gaib_sgemm_ex": (_i, [_vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _i, _vp]),
+    "gaib_gemm_bf16": (_i, [_vp, _i, _i64, _i, _i, _i64, _vp, _vp, _i, _vp]),
+    "gaib_gemm_bf16_cover": (_i, [_vp, _i, _i, _i, _i64]),
     "gaib_bias_add": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_colsum": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_rng_uniform": (_i, [_vp, _i64, _f, _f, _u64, _vp]),
@@ -841,6 +843,25 @@ class Context:
         _check(self.lib.gaib_sgemm_ex(self.h, int(transA), int(transB), M, N, K, _ptr(A), _ptr(B),
                                       flags, _ptr(Cm)), "gaib_sgemm")
         return Cm
+
+    def gemm_bf16(self, A, B, Cm, K=None, transB=False, accum=False, relu=False):
+        """gaib_gemm_bf16: Cm[M x N] (=|+=) A[:, :K] . op(B) for a torch.bfloat16 table A [M x lda] (K defaults to lda) and fp32 B
+        ([K x N], or [N x K] with transB), B split exactly into three bf16 planes on the device.  Raises GaibError (status -5)
+        where gemm_bf16_cover says no."""
+        import torch
+
+        assert A.dtype == torch.bfloat16 and A.dim() == 2 and A.is_contiguous() and Cm.is_contiguous() and B.is_contiguous()
+        M, N = Cm.shape
+        lda = A.shape[1]
+        K = lda if K is None else K
+        assert A.shape[0] == M and tuple(B.shape) == ((N, K) if transB else (K, N))
+        flags = (1 if accum else 0) | (2 if relu else 0)
+        _check(self.lib.gaib_gemm_bf16(self.h, int(transB), M, N, K, lda, _ptr(A), _ptr(B), flags, _ptr(Cm)), "gaib_gemm_bf16")
+        return Cm
+
+    def gemm_bf16_cover(self, N: int, K: int, lda: int, transB=False) -> bool:
+        """gaib_gemm_bf16_cover: would gaib_gemm_bf16 run this shape and stride (option gemm_bf16_kernel included)?"""
+        return bool(self.lib.gaib_gemm_bf16_cover(self.h, int(transB), N, K, lda))
 
     # ---- elementwise / loss / optimizer -----------------------------------------------------
     def bias_add(self, x, b):

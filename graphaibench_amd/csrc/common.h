@@ -93,6 +93,8 @@ struct gaib_ctx {
   int agg_zs;                // 1: the layer library's GCN / SAGE backward gathers a relu-masked gradient from its zero-suppressed image (gaib_pack_zs, gaib_spmm_gemm_zs)
   int agg_zs_paused;         // written by the layer library's guard: 1 while it gathers dense because too many rows are over capacity
   int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16, gaib_spmm_gemm_bf16)
+  int gemm_bf16;             // 1: the layer library's SAGE self products multiply the bf16 table the aggregation has just cast (gaib_gemm_bf16) where it covers the shape
+  int gemm_bf16_kernel;      // 1 (default): gaib_gemm_bf16 runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_gemm_bf16_cover says 0
   int sgemm_variant;         // 0 = auto
   int gat_fast;              // reserved
   int gat_chunk_colsum;      // GAT backward column sums by ordered chunks: -1 = dense graphs, 0 never, 1 always

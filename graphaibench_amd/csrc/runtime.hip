@@ -69,6 +69,8 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_bf16_pad = 1;
   c->agg_bf16_ld_last = 0;
   c->agg_bf16 = 0;
+  c->gemm_bf16 = 0;
+  c->gemm_bf16_kernel = 1;
   c->agg_zs = 1;
   c->agg_zs_paused = 0;
   c->sgemm_variant = 0;
@@ -530,6 +532,8 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
   else if (!strcmp(key, "gat_bf16")) *h_value = ctx->gat_bf16;
+  else if (!strcmp(key, "gemm_bf16")) *h_value = ctx->gemm_bf16;
+  else if (!strcmp(key, "gemm_bf16_kernel")) *h_value = ctx->gemm_bf16_kernel;
   else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
   else if (!strcmp(key, "capturing")) *h_value = ctx->capturing;  // a recording is open (gaib_capture_begin)
   else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
@@ -594,6 +598,12 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "gat_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->gat_bf16 = (int)value;
+  } else if (!strcmp(key, "gemm_bf16")) {
+    GAIB_CHECK(value == 0 || value == 1, "gemm_bf16 must be 0 (fp32 self products) or 1 (products on the bf16 table)");
+    ctx->gemm_bf16 = (int)value;
+  } else if (!strcmp(key, "gemm_bf16_kernel")) {
+    GAIB_CHECK(value == 0 || value == 1, "gemm_bf16_kernel must be 0 or 1");
+    ctx->gemm_bf16_kernel = (int)value;
   } else if (!strcmp(key, "agg_zs")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_zs must be 0 (dense gradient tables) or 1 (zero-suppressed)");
     ctx->agg_zs = (int)value;

@@ -20,6 +20,11 @@ bool aggregator::bf16_tables() {
   GAIB_OR_DIE(gaib_get_option(C(), "agg_bf16", &v));
   return v != 0;
 }
+bool aggregator::gemm_bf16_products() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "gemm_bf16", &v));
+  return v != 0;
+}
 // One process-wide scratch.  A buffer that has to grow is kept, not freed: a recorded epoch (gaib_exec) may still name it.
 static uint16_t* g_bf16_tab = nullptr;
 static size_t g_bf16_cap = 0;
@@ -353,6 +358,17 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     const int fl = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
     int64_t ld = len;
     const uint16_t* tab = to_bf16(dg, len, in, &ld);
+    // option gemm_bf16: the self rows ARE the table just cast and every dense route runs the self term as a separate
+    // accumulating product (spmm.hip: two matrices that do not fit LDS together, the K-slab route, the unfused one) -- that
+    // product on the bf16 table (gaib_gemm_bf16: exactly split weights), the neighbour half as before: both terms are then
+    // "the fp32 layer on the rounded table"
+    if (rows2 == in && gemm_bf16_products() && gaib_spmm_gemm_fusable(C(), kind, len, len_out, 1) == 0 &&
+        gaib_gemm_bf16_cover(C(), transW ? 1 : 0, len_out, len, ld) == 1) {
+      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, fl & ~GAIB_RELU));
+      GAIB_OR_DIE(gaib_gemm_bf16(C(), transW ? 1 : 0, (int64_t)g.size(), len_out, len, ld, tab, W2,
+                                 GAIB_ACCUMULATE | (relu ? GAIB_RELU : 0), out));
+      return;
+    }
     if (rows2)
       GAIB_OR_DIE(gaib_spmm_gemm2_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
     else

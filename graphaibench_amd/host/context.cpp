@@ -58,6 +58,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "agg_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_AGG_DTYPE)");
   }
+  // the dense self products of the SAGE layers under bf16 tables: fp32 rows (default) or the bf16 table with exactly split
+  // weights (option gemm_bf16; without GAIB_AGG_DTYPE=bf16 there is no table and nothing changes)
+  if (const char* d = getenv("GAIB_GEMM_DTYPE")) {
+    const std::string dt(d);
+    if (dt != "fp32" && dt != "bf16") {
+      fprintf(stderr, "GAIB_GEMM_DTYPE=%s: expected fp32 or bf16\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gemm_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

@@ -227,6 +227,7 @@ struct Trainer {
                                                   : (world > 1 ? "bf16 (odd widths on a partition: fp32)" : "bf16"))
                          : "fp32")
                 << "\n";
+    if (aggregator::gemm_bf16_products() && root()) std::cout << "dense self products: bf16 tables\n";
     if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root())
       std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
     if (bf16 && world > 1 && ARCH == gnn_arch::GAT) {

@@ -543,6 +543,28 @@ int gaib_sgemm(gaib_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int6
 int gaib_sgemm_ex(gaib_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K,
                   const float* d_A, const float* d_B, int flags, float* d_C);
 
+/* ---- dense product on a bf16 table with exactly split fp32 weights (gemm_bf16.hip) ----
+ * C[M x N] (=|+=) A . op(B), A = bf16 bits [M x K] at row stride lda (elements), B fp32 ([K x N], or [N x K] with transB),
+ * C fp32 [M x N] dense; flags = GAIB_ACCUMULATE | GAIB_RELU as gaib_sgemm_ex.
+ * op(B) is split ON THE DEVICE, on every call (weights change every step), into three bf16 planes: w0 = rne(B), w1 = rne(B - w0),
+ * w2 = rne(B - w0 - w1), rne = gaib_cast_f32_bf16's rounding; w0 + w1 + w2 == B exactly.  The split is part of the kernel: no
+ * host synchronisation, no workspace, safe inside gaib_capture_begin/end.  Every A[i][k] . w_t[k][j] is exact in fp32 and
+ * enters an fp32 accumulator of the bf16 matrix cores: the result is a sum of 3 K exact terms (+ C when accumulating) in an
+ * unspecified order -- the rounding of an fp32 product's accumulation, not bit-identical to any fp32 call; deterministic from
+ * run to run (no atomics, no split over K).  Finite inputs only: a +-inf in the table meets zero residual terms and gives NaN
+ * where fp32 gives +-inf.  |B| below about 2^-100 loses its low bits (the residuals underflow bf16's range).
+ * Subnormal bf16 table entries, subnormal plane values, subnormal fp32 results and C inputs are all kept, not flushed (measured on
+ * the MI355X: the bf16 MFMA takes 2^-133 x 2^100 to 2^-33).
+ * Cover: 8 <= K <= 256, K % 8 == 0; 4 <= N <= 256, N % 4 == 0; lda >= K, lda % 8 == 0 (and lda <= 2^22); d_A_bf16 and d_C on
+ * 16-byte boundaries; any M >= 0 (M == 0: GAIB_OK, nothing launched); option "gemm_bf16_kernel" = 1.  Anything else:
+ * GAIB_ERR_UNSUPPORTED with nothing written -- the caller falls back to gaib_sgemm_ex.  Columns K .. lda - 1 of a row are
+ * never read.  The table is read through per-tile buffer descriptors: 4 GB and more need no other path.
+ * Profile: key "gemm_bf16", tag MxNxK; bytes 2 M K + 4 M N (1 + accum) + 4 K N, flops 2 M N K (the useful ones, not x 3). */
+int gaib_gemm_bf16(gaib_ctx* ctx, int transB, int64_t M, int N, int K, int64_t lda, const uint16_t* d_A_bf16,
+                   const float* d_B, int flags, float* d_C);
+/* 1 when the call above would run (shape, stride and option "gemm_bf16_kernel" only; no pointer, no launch), else 0 */
+int gaib_gemm_bf16_cover(gaib_ctx* ctx, int transB, int N, int K, int64_t lda);
+
 /* weight gradient with the layer's d_relu folded in (d_relu_gpu on grad_in followed by matmul(transA),
  * gcn_layer.cpp:33-52): d_G <- d_G where d_mask > 0 else 0 (IN PLACE, what d_relu_gpu leaves behind) and
  * C[M x N] (=|+=) A^T . G for A [K x M], G / mask [K x N].  One pass over G instead of two. */
@@ -787,6 +809,11 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * gaib_spmm_bf16_ld / gaib_spmm_gemm_bf16_ld on whole graphs -- "spmm_bf16_pad" (default 1): 0 = always the dense stride;
  * "agg_bf16_ld_last" (readable; written by that library): the stride of the table it cast last --; GAT ignores
  * it and has "gat_bf16" instead; on a partitioned graph gaib_spmm_part_bf16 / gaib_spmm_gemm_part_bf16 over a bf16 halo exchange, odd widths in fp32);
+ * "gemm_bf16" (default 0; needs "agg_bf16" = 1 to have any effect): 1 = where a SAGE layer on a whole graph runs its self term
+ * as a separate accumulating product (256 -> 256, 128 -> 256 ...; the 100-wide input stays fp32: K % 8 != 0; gaib_spmm_gemm_fusable(.., 1) == 0) and
+ * gaib_gemm_bf16_cover says 1, that product is gaib_gemm_bf16 on the bf16 table the aggregation has just cast instead of
+ * gaib_sgemm_ex on the fp32 rows; "gemm_bf16_kernel" (default 1): 0 = gaib_gemm_bf16 refuses every call (GAIB_ERR_UNSUPPORTED),
+ * gaib_gemm_bf16_cover says 0;
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
  * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs, no
  * attention dropout); a partitioned GAT graph refuses the option;
@@ -798,7 +825,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
- * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_paused", "capturing" */
+ * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

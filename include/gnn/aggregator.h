@@ -18,6 +18,11 @@ class aggregator {
   // exchange is begun from the scratch and the class kernels gather bf16 (gaib_spmm_part_bf16, gaib_spmm_gemm_part_bf16); odd
   // widths run in fp32 there; a halo with fp32 callbacks only refuses the option.
   static bool bf16_tables();
+  // extension: dense self products on that bf16 table (context option "gemm_bf16" = 1, or GAIB_GEMM_DTYPE=bf16; only under
+  // bf16_tables()): where a SAGE layer on a whole graph runs its self term as a separate accumulating product and
+  // gaib_gemm_bf16 covers the shape, the product multiplies the table the aggregation has just cast (weights split exactly
+  // into three bf16 planes) instead of the fp32 rows.  Weight gradients, partitions, GCN and GAT keep their paths.
+  static bool gemm_bf16_products();
   // extension: zero-suppressed gradient tables (context option "agg_zs", default 1).  The backward aggregation of a layer with
   // a relu gathers a table that is about half +0.0 (the d_relu has just masked it): aggregate_then_matmul packs such a table
   // of 128 columns into a process-wide scratch (gaib_pack_zs) and gathers from there (gaib_spmm_gemm_zs: the same bits).  The
