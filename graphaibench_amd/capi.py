@@ -58,6 +58,8 @@ SIGNATURES = {
     "gaib_bf16_row_stride": (_i, [_vp, _vp, _i, C.POINTER(_i64)]),
     "gaib_pack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "gaib_unpack_zs": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
+    "gaib_pack_zs_wide": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
+    "gaib_unpack_zs_wide": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "gaib_graph_create": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_create_rect": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _vp, _i, _pp]),
     "gaib_graph_destroy": (_i, [_vp]),
@@ -644,10 +646,33 @@ class Context:
         _check(self.lib.gaib_unpack_zs(self.h, dense.shape[0], dense.shape[1], _ptr(zs), _ptr(dense), _ptr(out)), "gaib_unpack_zs")
         return out
 
+    def pack_zs_wide(self, x, out=None, overflow=None):
+        """gaib_pack_zs_wide: x fp32 [rows x 256] -> [2 x rows x 96] int32, image s = pack_zs(x[:, 128 s : 128 s + 128]); overflow:
+        a 1-element int32 tensor the number of over-capacity row-slabs is added to"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+        if out is None:
+            out = torch.empty((2, x.shape[0], 96), dtype=torch.int32, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.int32 and out.numel() == 2 * x.shape[0] * 96
+        _check(self.lib.gaib_pack_zs_wide(self.h, x.shape[0], x.shape[1], _ptr(x), _ptr(out), _ptr(overflow)), "gaib_pack_zs_wide")
+        return out
+
+    def unpack_zs_wide(self, zs, dense, out=None):
+        """gaib_unpack_zs_wide: the inverse of pack_zs_wide (dense: the table the image was made from, read for over-capacity half rows)"""
+        import torch
+
+        assert zs.is_contiguous() and dense.is_contiguous() and dense.dtype == torch.float32
+        if out is None:
+            out = torch.empty_like(dense)
+        _check(self.lib.gaib_unpack_zs_wide(self.h, dense.shape[0], dense.shape[1], _ptr(zs), _ptr(dense), _ptr(out)),
+               "gaib_unpack_zs_wide")
+        return out
+
     def spmm_gemm_zs(self, g: "Graph", kind: int, x, zs, agg, W, out, transW: bool = False, relu: bool = False,
                      agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None) -> bool:
-        """gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs: spmm_gemm gathering from zs = pack_zs(x).  False when the call has no packed
-        gather (GAIB_ERR_UNSUPPORTED, nothing touched): use spmm_gemm."""
+        """gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs: spmm_gemm gathering from zs = pack_zs(x) (128 columns) or pack_zs_wide(x) (256).
+        False when the call has no packed gather (GAIB_ERR_UNSUPPORTED, nothing touched): use spmm_gemm."""
         assert x.is_contiguous() and zs.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
         len_in, len_out = agg.shape[1], out.shape[1]
         assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))

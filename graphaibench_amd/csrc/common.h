@@ -91,6 +91,7 @@ struct gaib_ctx {
   int spmm_bf16_pad;         // 1 = gaib_bf16_row_stride line-aligns odd-width bf16 rows where that saves >10 % of the gathered lines, 0 = never
   int agg_bf16_ld_last;      // written by the layer library: the row stride (elements) of the bf16 table it cast last
   int agg_zs;                // 1: the layer library's GCN / SAGE backward gathers a relu-masked gradient from its zero-suppressed image (gaib_pack_zs, gaib_spmm_gemm_zs)
+  int agg_zs_wide;           // 1 (with agg_zs): ... and a gradient of 256 columns from its wide image (gaib_pack_zs_wide, the K-slab route)
   int agg_zs_paused;         // written by the layer library's guard: 1 while it gathers dense because too many rows are over capacity
   int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16, gaib_spmm_gemm_bf16)
   int gemm_bf16;             // 1: the layer library's SAGE self products multiply the bf16 table the aggregation has just cast (gaib_gemm_bf16) where it covers the shape

@@ -671,6 +671,90 @@ __global__ __launch_bounds__(256) void unpack_zs_kernel(int64_t rows, const unsi
   }
 }
 
+// ---- wide zero-suppressed tables: rows of 256 floats, one image per 128-column K-slab ------------------------------------
+// The aggregation of a 256-column table runs as two 128-column K-slab launches (spmm.hip), so the table packs as two independent
+// images, slab-major: [2][rows][384 B], image s bit for bit what pack_zs_kernel writes for columns 128 s .. 128 s + 127.  One pass
+// over the table, one wave per row: two 8-B loads per lane (one per slab), each slab's row put together in its own 384 B of the
+// wave's LDS and stored as three whole lines.  `overflow` counts over-capacity ROW-SLABS (a row can count twice).
+__global__ __launch_bounds__(256) void pack_zs_wide_kernel(int64_t rows, const float* __restrict__ in, unsigned* __restrict__ out,
+                                                            unsigned* __restrict__ overflow) {
+  __shared__ __attribute__((aligned(16))) unsigned buf[4][2][ZS_ROW_DW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned over = 0;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
+    zs_u2 x[2];
+    bool b0[2], b1[2], fits[2];
+    unsigned long long m0[2], m1[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) x[s] = __builtin_nontemporal_load(reinterpret_cast<const zs_u2*>(in + r * 256 + 128 * s) + lane);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      unsigned* w = buf[wave][s];
+      b0[s] = x[s][0] != 0u;
+      b1[s] = x[s][1] != 0u;
+      m0[s] = __ballot(b0[s]);
+      m1[s] = __ballot(b1[s]);
+      fits[s] = __builtin_popcountll(m0[s]) <= ZS_CAP && __builtin_popcountll(m1[s]) <= ZS_CAP;  // wave-uniform
+      if (lane < ZS_ROW_DW / 2) {
+        zs_u2 z = {0u, 0u};
+        if (lane == 0) z = zs_u2{(unsigned)m0[s], (unsigned)(m0[s] >> 32)};
+        if (lane == 1) z = zs_u2{(unsigned)m1[s], (unsigned)(m1[s] >> 32)};
+        *reinterpret_cast<zs_u2*>(w + 2 * lane) = z;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      unsigned* w = buf[wave][s];
+      if (fits[s]) {
+        const unsigned k0 = __builtin_amdgcn_mbcnt_hi((unsigned)(m0[s] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0[s], 0u));
+        const unsigned k1 = __builtin_amdgcn_mbcnt_hi((unsigned)(m1[s] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1[s], 0u));
+        if (b0[s]) w[4 + 2 * k0] = x[s][0];
+        if (b1[s]) w[5 + 2 * k1] = x[s][1];
+      } else {
+        ++over;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < ZS_ROW_DW / 2) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const zs_u2 o = *reinterpret_cast<const zs_u2*>(buf[wave][s] + 2 * lane);
+        __builtin_nontemporal_store(o, reinterpret_cast<zs_u2*>(out + ((int64_t)s * rows + r) * ZS_ROW_DW) + lane);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  if (overflow && over > 0 && lane == 0) atomicAdd(overflow, over);  // (a vector atomic, once per wave)
+}
+
+// (tests and tools: not on any hot path) blockIdx.y = slab
+__global__ __launch_bounds__(256) void unpack_zs_wide_kernel(int64_t rows, const unsigned* __restrict__ zs, const float* __restrict__ dense,
+                                                              float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) unsigned buf[4][ZS_ROW_DW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.y;
+  unsigned* w = buf[wave];
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
+    if (lane < ZS_ROW_DW / 2)
+      *reinterpret_cast<zs_u2*>(w + 2 * lane) = reinterpret_cast<const zs_u2*>(zs + ((int64_t)s * rows + r) * ZS_ROW_DW)[lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const unsigned long long m0 = ((unsigned long long)w[1] << 32) | w[0], m1 = ((unsigned long long)w[3] << 32) | w[2];
+    const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1);
+    zs_u2 v;
+    if (n0 > ZS_CAP || n1 > ZS_CAP) {
+      v = reinterpret_cast<const zs_u2*>(dense + r * 256 + 128 * s)[lane];
+    } else {
+      const unsigned p0 = 4u + 2u * (unsigned)__builtin_popcountll(m0 & ((1ull << lane) - 1ull));
+      const unsigned p1 = 5u + 2u * (unsigned)__builtin_popcountll(m1 & ((1ull << lane) - 1ull));
+      v[0] = ((m0 >> lane) & 1ull) ? w[p0 < (unsigned)ZS_ROW_DW ? p0 : 0u] : 0u;
+      v[1] = ((m1 >> lane) & 1ull) ? w[p1 < (unsigned)ZS_ROW_DW ? p1 : 0u] : 0u;
+    }
+    reinterpret_cast<zs_u2*>(out + r * 256 + 128 * s)[lane] = v;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+}
+
 }  // namespace
 
 extern "C" int gaib_fill_f32(gaib_ctx* ctx, int64_t n, float value, float* d_x) {
@@ -766,6 +850,39 @@ extern "C" int gaib_unpack_zs(gaib_ctx* ctx, int64_t rows, int len, const void* 
   GAIB_CHECK(d_dense != d_out, "gaib_unpack_zs: dense and out must not alias");
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(rows, 4), (int64_t)ctx->num_cus * 32);
   unpack_zs_kernel<<<grid, 256, 0, ctx->stream>>>(rows, static_cast<const unsigned*>(d_zs), d_dense, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_pack_zs_wide(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, void* d_zs, uint32_t* d_overflow) {
+  GAIB_CHECK(ctx && ((d_in && d_zs) || rows == 0), "gaib_pack_zs_wide: NULL argument");
+  GAIB_CHECK(rows >= 0, "gaib_pack_zs_wide: rows < 0");
+  if (len != 256) {
+    gaib_set_error("gaib_pack_zs_wide: rows of %d columns (the wide zero-suppressed format holds rows of 256: two slabs of 128)", len);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return GAIB_OK;
+  GAIB_CHECK(((uintptr_t)d_in & 7) == 0 && ((uintptr_t)d_zs & 127) == 0, "gaib_pack_zs_wide: the table must sit on an 8-B, the image on a 128-B boundary");
+  GAIB_CHECK((const void*)d_in != (const void*)d_zs, "gaib_pack_zs_wide: in and out must not alias");
+  ProfScope ps(ctx, "pack_zs_wide", (1024.0 + 768.0) * (double)rows);
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(rows, 4), (int64_t)ctx->num_cus * 32);
+  pack_zs_wide_kernel<<<grid, 256, 0, ctx->stream>>>(rows, d_in, static_cast<unsigned*>(d_zs), d_overflow);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_unpack_zs_wide(gaib_ctx* ctx, int64_t rows, int len, const void* d_zs, const float* d_dense, float* d_out) {
+  GAIB_CHECK(ctx && ((d_zs && d_dense && d_out) || rows == 0), "gaib_unpack_zs_wide: NULL argument");
+  GAIB_CHECK(rows >= 0, "gaib_unpack_zs_wide: rows < 0");
+  if (len != 256) {
+    gaib_set_error("gaib_unpack_zs_wide: rows of %d columns (the wide zero-suppressed format holds rows of 256: two slabs of 128)", len);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return GAIB_OK;
+  GAIB_CHECK((((uintptr_t)d_dense | (uintptr_t)d_out | (uintptr_t)d_zs) & 7) == 0, "gaib_unpack_zs_wide: tables must sit on 8-B boundaries");
+  GAIB_CHECK(d_dense != d_out, "gaib_unpack_zs_wide: dense and out must not alias");
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(rows, 4), (int64_t)ctx->num_cus * 32);
+  unpack_zs_wide_kernel<<<dim3(grid, 2), 256, 0, ctx->stream>>>(rows, static_cast<const unsigned*>(d_zs), d_dense, d_out);
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

@@ -72,6 +72,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->gemm_bf16 = 0;
   c->gemm_bf16_kernel = 1;
   c->agg_zs = 1;
+  c->agg_zs_wide = 0;
   c->agg_zs_paused = 0;
   c->sgemm_variant = 0;
   if (const char* e = getenv("GAIB_SGEMM_VARIANT")) c->sgemm_variant = atoi(e);  // (A/B of a whole trainer run: 61 = without sgemm_skinny.hip)
@@ -536,6 +537,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "gemm_bf16_kernel")) *h_value = ctx->gemm_bf16_kernel;
   else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
   else if (!strcmp(key, "capturing")) *h_value = ctx->capturing;  // a recording is open (gaib_capture_begin)
+  else if (!strcmp(key, "agg_zs_wide")) *h_value = ctx->agg_zs_wide;
   else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
   else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
   else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
@@ -607,6 +609,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "agg_zs")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_zs must be 0 (dense gradient tables) or 1 (zero-suppressed)");
     ctx->agg_zs = (int)value;
+  } else if (!strcmp(key, "agg_zs_wide")) {
+    GAIB_CHECK(value == 0 || value == 1, "agg_zs_wide must be 0 (256-column gradient tables gathered dense) or 1 (zero-suppressed, with agg_zs)");
+    ctx->agg_zs_wide = (int)value;
   } else if (!strcmp(key, "agg_zs_paused")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_zs_paused must be 0 or 1");
     ctx->agg_zs_paused = (int)value;

@@ -372,6 +372,9 @@ int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_ar
 // ... and over a zero-suppressed table: spmm_gemm_zs.hip
 int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
                        int wmode);
+// ... one K-slab of a 256-column aggregation over its slab of a wide zero-suppressed table
+int gaib_spmm_kslab_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
+                       int wmode);
 
 static int spmm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                      const float* d_in, float* d_out, int flags, int heads = 1, const float* d_in2 = nullptr,
@@ -457,9 +460,10 @@ extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in
 // fp32 call would see for the same table widened -- the widened table sits at "twice the address" (a bf16 table aligned to 8 B
 // stands for an fp32 one aligned to 16), sizes and the chunk rule count fp32 bytes -- so both take the same route, and each route
 // runs with the bf16 gather: no fp32 copy of the table anywhere.
-// d_zs: the zero-suppressed image of d_in (gaib_pack_zs; gaib_spmm_gemm_zs).  Only the one-launch fused route over a whole graph
-// has such a gather (128 columns, buffer addressing, row forms): every other route is GAIB_ERR_UNSUPPORTED, decided on the dense
-// sizes before anything is launched.
+// d_zs: the zero-suppressed image of d_in (gaib_pack_zs, or gaib_pack_zs_wide at 256 columns; gaib_spmm_gemm_zs).  Only the
+// one-launch fused route over a whole graph (128 columns) and the K-slab route (256 columns: one slab image per launch) have
+// such a gather (buffer addressing, row forms): every other route is GAIB_ERR_UNSUPPORTED, decided on the dense sizes before
+// anything is launched.
 static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                           const float* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                           const float* d_W2, int len_out, float* d_out, int flags, const float* d_in2 = nullptr,
@@ -492,20 +496,29 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
                         g->nv >= 1 &&
                         (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN ||
                          weight_kind == GAIB_W_MEAN_T || weight_kind == GAIB_W_EDGE);
+  // (the K-slab route of 129..256 columns, described where it runs below)
+  const bool kslab = !part && ctx->spmm_fuse != 0 && !dense && len_in > 128 && len_in <= 256 && len_in % 2 == 0 && (al & 7) == 0 &&
+                     len_out >= 1 && fuse_strip_rows(128, len_out, false) != 0 && g->ne > 0 &&
+                     (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN || weight_kind == GAIB_W_MEAN_T ||
+                      weight_kind == GAIB_W_EDGE);
   if (d_zs) {
     const int strip = shape_ok ? fuse_strip_rows(kpad, len_out, dual) : 0;
     const int64_t dense_bytes = g->nc * (int64_t)len_in * 4;
-    bool ok = !part && len_in == 128 && strip == (dual ? 2 : 8) && dense_bytes < ((int64_t)1 << 32) && ctx->spmm_addr_mode != 2 &&
-              ((uintptr_t)d_zs & 127) == 0;
+    // 128 columns: the one-launch fused route.  256 columns (a wide image, gaib_pack_zs_wide): the K-slab route, whose two launches
+    // are one-product launches whatever `dual` says (the self term follows as a dense product).  129 .. 255: a second slab narrower
+    // than 128 columns has no packed form.
+    const bool wide = len_in == 256;
+    bool ok = (wide ? kslab : (!part && len_in == 128 && strip == (dual ? 2 : 8))) && dense_bytes < ((int64_t)1 << 32) &&
+              ctx->spmm_addr_mode != 2 && ((uintptr_t)d_zs & 127) == 0;
     // the variants the dense call would pick for this graph and have no packed form (launch_fused's own predicates): the edge
     // stream on short rows (20-34 % faster than the row form at 3-5 edges per row), the XCD-affine tile supply on a numbering
     // with locality.  The caller gathers dense there.
-    if (ok && !dual && (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv))) ok = false;
+    if (ok && (wide || !dual) && (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv))) ok = false;
     if (ok && tile_xcd_arg(ctx, g) != 0) ok = false;
     if (!ok) {
-      gaib_set_error("gaib_spmm_gemm_zs: no zero-suppressed gather for this call (whole graph, 128 columns, the one-launch fused route "
-                     "in its row form -- 8-row strip or two products, no edge stream, global tile counter --, table below 4 GB, "
-                     "buffer addressing, image on a 128-B boundary)");
+      gaib_set_error("gaib_spmm_gemm_zs: no zero-suppressed gather for this call (whole graph, 128 columns on the one-launch fused route "
+                     "or 256 columns -- a wide image -- on the K-slab route, in the row form -- 8-row strip, two products or a K-slab, "
+                     "no edge stream, global tile counter --, table below 4 GB, buffer addressing, image on a 128-B boundary)");
       return GAIB_ERR_UNSUPPORTED;
     }
     if (zs_query) return GAIB_OK;
@@ -536,10 +549,6 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   // the activation).  The gathered bytes are the same as one 1-KB row gather per edge; colidx / weights are streamed
   // twice and y is read-modify-written once -- against a separate pass over agg and a 2 x 2.45 M x 256 x 256 GEMM.
   // A second product (SAGE's self term) follows as an accumulating GEMM.
-  const bool kslab = !part && ctx->spmm_fuse != 0 && !dense && len_in > 128 && len_in <= 256 && len_in % 2 == 0 && (al & 7) == 0 &&
-                     len_out >= 1 && fuse_strip_rows(128, len_out, false) != 0 && g->ne > 0 &&
-                     (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN || weight_kind == GAIB_W_MEAN_T ||
-                      weight_kind == GAIB_W_EDGE);
   if (kslab) {
     SpmmArgs a0;
     int wmode = 0;
@@ -582,7 +591,14 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
       f.heavy_agg = hv + k0;
       f.heavy_rows = g->heavy_rows;
       f.n_heavy = (int)g->n_heavy;
-      if (bf16) GAIB_TRY(gaib_spmm_fused_bf16(ctx, g, &a, &f, hv + k0, 2, wmode));
+      if (d_zs) {  // the slab's image in front, the dense table at the slab's first column behind it for over-capacity half rows
+        a.in2 = a.in;
+        a.in2_bytes = a.in_bytes;
+        a.in = reinterpret_cast<const float*>(static_cast<const char*>(d_zs) + (int64_t)(k0 / 128) * g->nc * GAIB_ZS_ROW_BYTES);
+        a.ld = GAIB_ZS_ROW_BYTES / 4;
+        a.in_bytes = (uint32_t)(g->nc * (int64_t)GAIB_ZS_ROW_BYTES);
+        GAIB_TRY(gaib_spmm_kslab_zs(ctx, g, &a, &f, hv + k0, wmode));
+      } else if (bf16) GAIB_TRY(gaib_spmm_fused_bf16(ctx, g, &a, &f, hv + k0, 2, wmode));
       else GAIB_TRY(wmode == 0 ? (launch_fused<2, 0>(ctx, g, a, f, hv + k0)) : (launch_fused<2, 1>(ctx, g, a, f, hv + k0)));
     }
     if (dual)
@@ -681,8 +697,9 @@ extern "C" int gaib_spmm_gemm_zs_route(gaib_ctx* ctx, gaib_graph* g, int weight_
                         0, nullptr, 0, false, d_zs, true);
 }
 
-// agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]) gathering from the zero-suppressed image d_zs of d_in (gaib_pack_zs):
-// three lines per gathered row instead of four, d_agg (unless scratch) and d_out bit-identical to gaib_spmm_gemm(2) on d_in.
+// agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]) gathering from the zero-suppressed image d_zs of d_in (gaib_pack_zs at 128
+// columns, gaib_pack_zs_wide at 256): three lines per gathered (half) row instead of four, d_agg (unless scratch) and d_out
+// bit-identical to gaib_spmm_gemm(2) on d_in.
 extern "C" int gaib_spmm_gemm_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
                                  const float* d_in, const void* d_zs, float* d_agg, const float* d_W, int transW, int len_out,
                                  float* d_out, int flags) {

@@ -157,6 +157,13 @@ __device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
 struct zs_t { uint32_t bits; };
 constexpr int GAIB_ZS_ROW_BYTES = 384;
 constexpr int GAIB_ZS_CAP = 46;
+// E = zs_wide_t: one 128-column slab of a 256-column table (gaib_pack_zs_wide: one image per slab, each in the format above).  The
+// packed gather is zs_t's; only the dense table behind it differs: its rows are 1024 B apart, and a.in2 points at the slab's first
+// column, so an over-capacity half row is read at col * 1024 + the lane's offset.
+struct zs_wide_t { uint32_t bits; };
+template <typename E> struct ZsTraits { static constexpr bool zs = false; static constexpr uint32_t dense_row_bytes = 0u; };
+template <> struct ZsTraits<zs_t> { static constexpr bool zs = true; static constexpr uint32_t dense_row_bytes = 512u; };
+template <> struct ZsTraits<zs_wide_t> { static constexpr bool zs = true; static constexpr uint32_t dense_row_bytes = 1024u; };
 
 // One feature-row gather.  BUF: `buffer_load_dwordxN v, voff, s[rsrc], soff offen` -- the row
 // base (col * row bytes) is a 32-bit SGPR offset against one descriptor for the whole table,
@@ -171,11 +178,12 @@ constexpr int GAIB_ZS_CAP = 46;
 // E: element type of the table -- float, or uint16_t for a bf16 table (a.in then points at bf16 bits, a.ld counts
 // elements, a.in_bytes is the bf16 size; voff is a byte offset into such a row); or zs_t for a zero-suppressed table (a.in
 // then points at the packed rows, a.ld = 96, a.in_bytes is the packed size, and a.in2 / a.in2_bytes name the dense table the
-// packed one was made from; voff is the lane's byte offset into the DENSE row, 8 * lane).
+// packed one was made from; voff is the lane's byte offset into the DENSE row, 8 * lane); or zs_wide_t for one slab of a wide
+// zero-suppressed table (the same, with dense rows 1024 B apart).
 template <int VEC, int GM, bool PART = false, typename E = float>
 struct RowGather {
   static constexpr bool BUF = GM != 0;
-  static constexpr bool ZS = std::is_same<E, zs_t>::value;
+  static constexpr bool ZS = ZsTraits<E>::zs;
   static_assert(!PART || !ZS, "two-table gathers: fp32 or bf16 tables");
   static_assert(!ZS || (VEC == 2 && GM == 1), "zero-suppressed tables: 8-byte lanes (128 columns), buffer addressing");
   __amdgpu_buffer_rsrc_t rsrc, rsrc2;
@@ -230,13 +238,13 @@ struct RowGather {
     p[1] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l1 << 2), (int)r[1]);
   }
   // zs_fix: the rare path, entered for a whole group when any of its rows is over capacity.  Such a row is read from the dense
-  // table, 512 B, and waited for; the others are selected as on the fast path.  It returns the row rather than repairing
+  // table, 512 B (of a row ZsTraits<E>::dense_row_bytes long), and waited for; the others are selected as on the fast path.  It returns the row rather than repairing
   // registers and masks for a select shared with the fast path: values that join after the branch cost the FAST path a copy
   // of every register and mask of the group, and a wait for the dense load left to the join would drain the gathers in flight.
   __device__ __forceinline__ typename VecT<VEC>::type zs_fix(const raw_t& p, zs_mask_t m0, zs_mask_t m1, uint32_t cvec, int idx, uint32_t voff) const {
     if (zs_over(zs_over_bits(m0, m1))) {
       const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cvec, idx);
-      const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * 512u), 0);
+      const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * ZsTraits<E>::dense_row_bytes), 0);
       typename VecT<VEC>::type v;
       v[0] = __uint_as_float(d[0]);
       v[1] = __uint_as_float(d[1]);
@@ -373,7 +381,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
                                                 const uint32_t (&voff)[CT],
                                                 typename VecT<VEC>::type (&acc)[CT], uint32_t c_first = 0u,
                                                 float w_first = 0.f) {
-  static_assert((sizeof(E) == 4 && !std::is_same<E, zs_t>::value) || WMODE < 3, "bf16 and zero-suppressed tables: single-head weights");
+  static_assert((sizeof(E) == 4 && !ZsTraits<E>::zs) || WMODE < 3, "bf16 and zero-suppressed tables: single-head weights");
   typedef RowGather<VEC, BUF, PART, E> gather_t;
   const gather_t gather(a);
   typename gather_t::raw_t x[U][CT];  // gather destinations (bf16: packed words, widened where consumed); the tail's piece p lives in x[p .. 2p-1]

@@ -90,6 +90,9 @@ static bool bf16_for(Graph& g, int len) {
 // scripts/zs_aggregation.py sweeps the kept share of the gradient from 40 to 90 % on the products-shaped graph
 // (profiles/zs/zs_gather_groups.json, LEDGER 10.4): packed wins by 1.13 ms at 50 % kept (0.02 % of the rows over capacity), by
 // 0.65 ms at 60 % (3.5 %), by 0.15 ms at 62 % (7.3 %), loses 0.68 ms at 64 % (13.9 %) -- the two sets cross near 8.5 % of the rows.
+// At 256 columns (agg_zs_wide) the pack counts over-capacity ROW-SLABS, two per row, and each slab launch has the economics of
+// the 128-column launch set: the same share, of rows * 2.  A starting value -- the crossing has not been measured at this width
+// (scripts/zs_wide.py reports it).
 static const double ZS_GUARD_SHARE = 0.08;
 static const unsigned ZS_PROBE_EVERY = 8;
 // Two products (SAGE's backward: the self term rides along, the 2-row-strip kernel at 127 VGPRs with 10 spilled): the packed
@@ -102,6 +105,11 @@ bool aggregator::zs_tables() {
   GAIB_OR_DIE(gaib_get_option(C(), "agg_zs", &v));
   return v != 0;
 }
+bool aggregator::zs_wide_tables() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs_wide", &v));
+  return v != 0;
+}
 bool aggregator::zs_paused() {
   int64_t v = 0;
   GAIB_OR_DIE(gaib_get_option(C(), "agg_zs_paused", &v));
@@ -112,26 +120,26 @@ bool aggregator::zs_paused() {
 static const int ZS_SLOTS = 16;  // tables watched at a time (a deeper model shares slots round robin: counts then mix)
 struct ZsWatch {
   const float* table = nullptr;
-  size_t counted_rows = 0;  // rows of the pack the slot's count belongs to (0: no pack yet)
+  size_t counted_rows = 0;  // rows (256 columns: row-slabs) of the pack the slot's count belongs to (0: no pack yet)
   bool paused = false;
   unsigned since_probe = 0;
 };
 static struct {
   gaib_ctx* ctx = nullptr;
-  void* tab = nullptr;  // [cap_rows x 384 B]
-  size_t cap_rows = 0;
+  void* tab = nullptr;  // [cap_bytes]: rows x 384 B, or 2 x rows x 384 B for a table of 256 columns
+  size_t cap_bytes = 0;
   uint32_t* d_over = nullptr;           // [ZS_SLOTS] the packs' counts of over-capacity rows ...
   volatile uint32_t* h_over = nullptr;  // [ZS_SLOTS] ... read back into pinned memory behind every pack
   ZsWatch watch[ZS_SLOTS];
   int n_watch = 0, next_evict = 0;
   std::vector<void*> retired;  // (a recorded epoch may still name a buffer that had to grow)
 } g_zs;
-static void* zs_table(size_t rows) {
+static void* zs_table(size_t bytes) {
   if (g_zs.ctx != C()) {  // a new process context: start over on its device (the old context's buffers went with it)
     if (g_zs.h_over) GAIB_OR_DIE(gaib_host_free(C(), const_cast<uint32_t*>(g_zs.h_over)));
     g_zs.retired.clear();
     g_zs.tab = nullptr;
-    g_zs.cap_rows = 0;
+    g_zs.cap_bytes = 0;
     g_zs.ctx = C();
     g_zs.n_watch = g_zs.next_evict = 0;
     GAIB_OR_DIE(gaib_malloc(C(), sizeof(uint32_t) * ZS_SLOTS, (void**)&g_zs.d_over));
@@ -140,13 +148,13 @@ static void* zs_table(size_t rows) {
     g_zs.h_over = static_cast<volatile uint32_t*>(h);
     for (int i = 0; i < ZS_SLOTS; i++) g_zs.h_over[i] = 0;
   }
-  if (rows > g_zs.cap_rows) {
+  if (bytes > g_zs.cap_bytes) {
     if (g_zs.tab) g_zs.retired.push_back(g_zs.tab);
     g_zs.tab = nullptr;
-    g_zs.cap_rows = 0;
+    g_zs.cap_bytes = 0;
     // (inside a capture gaib_malloc refuses: the run has to reserve the scratch before it records)
-    GAIB_OR_DIE(gaib_malloc(C(), rows * (size_t)384, &g_zs.tab));
-    g_zs.cap_rows = rows;
+    GAIB_OR_DIE(gaib_malloc(C(), bytes, &g_zs.tab));
+    g_zs.cap_bytes = bytes;
   }
   return g_zs.tab;
 }
@@ -160,13 +168,16 @@ static int zs_slot(const float* table) {
   g_zs.watch[i].table = table;
   return i;
 }
-// pack `rows` x 128 floats at `in` into the scratch; the count of over-capacity rows follows into the slot's pinned word
-static const void* zs_pack(int slot, size_t rows, const float* in) {
-  void* t = zs_table(rows);
+// pack `rows` x len (128, or 256: the wide image) floats at `in` into the scratch; the count of over-capacity rows (row-slabs)
+// follows into the slot's pinned word
+static const void* zs_pack(int slot, size_t rows, int len, const float* in) {
+  const size_t slabs = (size_t)len / 128;
+  void* t = zs_table(rows * slabs * 384);
   GAIB_OR_DIE(gaib_fill_f32(C(), 1, 0.f, reinterpret_cast<float*>(g_zs.d_over + slot)));
-  GAIB_OR_DIE(gaib_pack_zs(C(), (int64_t)rows, 128, in, t, g_zs.d_over + slot));
+  if (len == 128) GAIB_OR_DIE(gaib_pack_zs(C(), (int64_t)rows, len, in, t, g_zs.d_over + slot));
+  else GAIB_OR_DIE(gaib_pack_zs_wide(C(), (int64_t)rows, len, in, t, g_zs.d_over + slot));
   GAIB_OR_DIE(gaib_memcpy_d2h_async(C(), const_cast<uint32_t*>(g_zs.h_over + slot), g_zs.d_over + slot, sizeof(uint32_t)));
-  g_zs.watch[slot].counted_rows = rows;
+  g_zs.watch[slot].counted_rows = rows * slabs;
   return t;
 }
 // ("agg_zs_paused" reads 1 while ANY watched table is gathered dense by the guard)
@@ -429,9 +440,13 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
               [&](gaib_graph* gh, const float* halo) { fused(gh, halo, flags | GAIB_ACCUMULATE); });
     return;
   }
-  if (relu_masked && len == 128 && (!rows2 || ZS_TWO_PRODUCTS) && zs_tables()) {
+  // (256 columns, option agg_zs_wide: the K-slab route, whose launches are one-product ones -- ZS_TWO_PRODUCTS concerns the
+  // 128-column two-product kernel only)
+  const bool zs_narrow = len == 128 && (!rows2 || ZS_TWO_PRODUCTS);
+  if (relu_masked && (zs_narrow || len == 256) && zs_tables() && (len == 128 || zs_wide_tables())) {
     gaib_graph* dg = dev(g);
     const size_t rows = (size_t)gaib_graph_nc(dg);
+    const size_t tab_bytes = rows * (size_t)(len / 128) * 384;
     int64_t capturing = 0;
     GAIB_OR_DIE(gaib_get_option(C(), "capturing", &capturing));
     if (g_zs.ctx != C()) zs_table(0);
@@ -440,9 +455,9 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     // variants).  The query reads nothing through the image pointer: any 128-B aligned address stands for it.
     int route = gaib_spmm_gemm_zs_route(C(), dg, kind, len, in, g_zs.d_over, agg, rows2, len_out, out);
     if (route != GAIB_OK && route != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(route);
-    if (route == GAIB_OK && rows > g_zs.cap_rows) {
+    if (route == GAIB_OK && tab_bytes > g_zs.cap_bytes) {
       if (capturing) route = GAIB_ERR_UNSUPPORTED;  // (a recording that would have to grow the scratch: dense)
-      else zs_table(rows);
+      else zs_table(tab_bytes);
     }
     if (route == GAIB_OK) {
       const int slot = zs_slot(in);
@@ -452,9 +467,9 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
       if (w.paused) {
         // a look at the count every ZS_PROBE_EVERY-th call -- never inside a recording: a recorded epoch of a paused table
         // gathers dense and packs nothing, whatever the call count was when it was recorded
-        if (!capturing && ++w.since_probe % ZS_PROBE_EVERY == 0) zs_pack(slot, rows, in);
+        if (!capturing && ++w.since_probe % ZS_PROBE_EVERY == 0) zs_pack(slot, rows, len, in);
       } else {
-        const void* tab = zs_pack(slot, rows, in);
+        const void* tab = zs_pack(slot, rows, len, in);
         if (rows2)
           GAIB_OR_DIE(gaib_spmm_gemm2_zs(C(), dg, kind, NULL, len, in, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, flags));
         else

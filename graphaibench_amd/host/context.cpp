@@ -68,6 +68,15 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gemm_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
   }
+  // relu-masked gradients of 256 columns gathered zero-suppressed on the K-slab route (option agg_zs_wide; off by default)
+  if (const char* d = getenv("GAIB_AGG_ZS_WIDE")) {
+    const std::string v(d);
+    if (v != "0" && v != "1") {
+      fprintf(stderr, "GAIB_AGG_ZS_WIDE=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "agg_zs_wide", v == "1" ? 1 : 0), "gaib_set_option (GAIB_AGG_ZS_WIDE)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

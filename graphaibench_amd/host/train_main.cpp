@@ -230,6 +230,8 @@ struct Trainer {
     if (aggregator::gemm_bf16_products() && root()) std::cout << "dense self products: bf16 tables\n";
     if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root())
       std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
+    if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root() && aggregator::zs_wide_tables())
+      std::cout << "relu-masked gradients of 256 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs_wide = 1)" : "dense (agg_zs = 0 overrides agg_zs_wide = 1)") << "\n";
     if (bf16 && world > 1 && ARCH == gnn_arch::GAT) {
       std::cerr << "GAIB_AGG_DTYPE=bf16 with GAT runs on one GPU only (GAT gathers fp32 tables; GCN and SAGE take bf16 tables on a partition)\n";
       exit(EXIT_FAILURE);

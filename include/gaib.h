@@ -127,6 +127,13 @@ int gaib_cast_f32_bf16_rows(gaib_ctx* ctx, int64_t rows, int len, const float* d
  * from (read for over-capacity rows only).  len != 128: GAIB_ERR_UNSUPPORTED. */
 int gaib_pack_zs(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, void* d_zs, uint32_t* d_overflow);
 int gaib_unpack_zs(gaib_ctx* ctx, int64_t rows, int len, const void* d_zs, const float* d_dense, float* d_out);
+/* Wide zero-suppressed tables: rows of 256 floats, packed as one image per 128-column K-slab of the aggregation, slab-major:
+ * d_zs [2][rows][384 B] (128-B aligned).  Image s is bit for bit what gaib_pack_zs writes for columns 128 s .. 128 s + 127 of d_in
+ * (same format, 46 values per half of a half row); one pass over d_in [rows x 256] (8-B aligned).  d_overflow (may be NULL): the
+ * number of over-capacity ROW-SLABS is ADDED to it -- a row over capacity in both slabs counts twice.  gaib_unpack_zs_wide: the
+ * inverse, d_dense [rows x 256] being the table the image was made from.  len != 256: GAIB_ERR_UNSUPPORTED, nothing written. */
+int gaib_pack_zs_wide(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, void* d_zs, uint32_t* d_overflow);
+int gaib_unpack_zs_wide(gaib_ctx* ctx, int64_t rows, int len, const void* d_zs, const float* d_dense, float* d_out);
 
 /* ---- graph: LearningGraph's device half (include/gnn/lgraph.h:20-277) ------------------
  * gaib_graph_create  = alloc_on_device + copy_to_gpu (src/gnn/lgraph.cu:51-92).
@@ -491,7 +498,13 @@ int gaib_spmm_gemm2(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* 
  * and a graph the dense call runs in its row form off the global tile counter (not the edge stream of short rows -- fewer than 12
  * edges per row, or "spmm_flat" = 1 --, not the XCD-affine supply of a numbering with locality).  Anything
  * else -- another width, a graph with a row map, a dense graph the ordered chunks would take, "spmm_fuse" = 0 -- returns
- * GAIB_ERR_UNSUPPORTED before anything is launched: call the dense function. */
+ * GAIB_ERR_UNSUPPORTED before anything is launched: call the dense function.
+ * len_in == 256 with d_zs a WIDE image (gaib_pack_zs_wide): covers the K-slab route the dense call takes at that width -- whole
+ * graph, "spmm_fuse" != 0, not the ordered chunks, a [len_out x 128] slab of op(W) in LDS beside 8- or 2-row strips -- under the
+ * same conditions (row form: 12 edges per row or "spmm_flat" = 0; global tile counter; table below 4 GB; "spmm_addr_mode" != 2;
+ * image 128-B aligned).  Each slab launch gathers its slab's image, three lines per half row instead of four; with two products
+ * the self term follows as the dense route's accumulating gaib_sgemm_ex.  Same bit-identity contract.  Widths 129 .. 255 are
+ * refused: a second slab narrower than 128 columns has no packed form. */
 /* gaib_spmm_gemm_zs_route: would the packed call (two products when d_rows2 != NULL) be taken?  GAIB_OK or GAIB_ERR_UNSUPPORTED
  * from the route information alone -- nothing is launched or read: ask before packing. */
 int gaib_spmm_gemm_zs_route(gaib_ctx* ctx, gaib_graph* g, int weight_kind, int len_in, const float* d_in, const void* d_zs,
@@ -804,6 +817,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * under "agg_bf16", on a partitioned graph, at other widths, on graphs without a packed route (gaib_spmm_gemm_zs_route), and for
  * SAGE's two-product backward until that form is measured faster than the dense one.  "agg_zs_paused" (readable; written by that library): 1 while
  * its guard gathers dense because too many rows of the gradient are over the packed row's capacity.
+ * "agg_zs_wide" (default 0; needs "agg_zs" = 1): 1 = the GCN and SAGE backward passes also gather a relu-masked gradient of 256
+ * columns packed (gaib_pack_zs_wide + gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs on the K-slab route), same bits, same guard (counted
+ * in row-slabs); off until it has been measured on the layer steps.
  * Two options are features rather than knobs: "agg_bf16" (default 0): 1 = the layer library's GCN and SAGE aggregations
  * (libgaib_gnn) gather from a bf16 copy of their table (gaib_cast_f32_bf16_rows at gaib_bf16_row_stride's stride +
  * gaib_spmm_bf16_ld / gaib_spmm_gemm_bf16_ld on whole graphs -- "spmm_bf16_pad" (default 1): 0 = always the dense stride;
@@ -825,7 +841,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
- * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel" */
+ * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

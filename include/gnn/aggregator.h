@@ -30,7 +30,11 @@ class aggregator {
   // into a pinned host word that is read WITHOUT synchronising (a past step's value); above ZS_GUARD_SHARE of the rows the
   // aggregation gathers dense, packing every ZS_PROBE_EVERY-th call only to look at the count again (never inside a recording).
   // The guard's state is kept per gathered table.  Calls with a second product (SAGE) gather dense for now (ZS_TWO_PRODUCTS).
+  // Option "agg_zs_wide" (default 0, GAIB_AGG_ZS_WIDE=1; only under zs_tables()): a masked gradient of 256 columns is packed
+  // too (gaib_pack_zs_wide: one image per 128-column K-slab) and gathered on the K-slab route, GCN and SAGE alike (at that width
+  // the self term is a separate dense product either way).  Same scratch, guard and cadence; the count is in row-slabs.
   static bool zs_tables();
+  static bool zs_wide_tables();
   static bool zs_paused();
   void set_vlen(int vlen) { length = vlen; }
   // extension: the next aggregate() call clamps its output at 0 (the layer's relu_gpu fused
