@@ -153,6 +153,8 @@ SIGNATURES = {
     "gaib_gat_backward_fused_rect": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _i]),
     "gaib_gather_scatter_rows": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp]),
     "gaib_graph_reorder": (_i, [_vp, _vp, _i, _pp, _vp, _vp]),
+    "gaib_graph_induce": (_i, [_vp, _vp, _i64, _vp, _i, _i, _pp, _vp]),
+    "gaib_gather_rows_u8": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
     "gaib_graph_sort_rows": (_i, [_vp, _vp]),
     "gaib_graph_locality": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
     "gaib_graph_stats": (_i, [_vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
@@ -198,6 +200,7 @@ class GaibError(RuntimeError):
 
 COMM_RCCL, COMM_IPC = 0, 1
 ORDER_DEGREE, ORDER_BFS, ORDER_CM = 1, 2, 3
+INDUCE_RELABEL, INDUCE_KEEP_IDS = 0, 1
 COMM_ID_BYTES = 128
 
 
@@ -992,6 +995,12 @@ class Context:
         _check(self.lib.gaib_gather_rows(self.h, idx.numel(), _ptr(idx), x.shape[1], _ptr(x), _ptr(out)),
                "gaib_gather_rows")
 
+    def gather_rows_u8(self, idx, x, out):
+        """out[k, :] = x[idx[k], :] for uint8 rows of any width (x, out: [n, width] or [n]; no alignment needed)"""
+        width = x.shape[1] if x.dim() > 1 else 1
+        _check(self.lib.gaib_gather_rows_u8(self.h, idx.numel(), _ptr(idx), width, _ptr(x), _ptr(out)),
+               "gaib_gather_rows_u8")
+
 
 class Graph:
     """gaib_graph: CSR resident in HBM.  rowptr: int64 or int32/uint32 tensor/array [nv+1];
@@ -1055,6 +1064,26 @@ class Graph:
         _check(self.lib.gaib_graph_reorder(self.ctx.h, self.h, method, C.byref(h), new_of_old.data_ptr(), old_of_new.data_ptr()),
                "gaib_graph_reorder")
         return Graph(self.ctx, _handle=h), new_of_old, old_of_new
+
+    def induce(self, kept, keep_ids: bool = False):
+        """(induced graph, rows) -- gaib_graph_induce on the strictly ascending vertex ids `kept` (numpy array / cpu or
+        cuda tensor).  Default: the relabelled subgraph of len(kept) rows; keep_ids=True: nv rows under the old ids, dropped
+        vertices' rows empty.  rows: int64 device tensor of the kept ids (the index list for gather_rows / gather_rows_u8)."""
+        import numpy as np
+        import torch
+
+        if isinstance(kept, torch.Tensor):
+            k = kept.to(torch.int32).contiguous() if kept.dtype != torch.int32 else kept.contiguous()
+            n, ptr, on_dev = k.numel(), k.data_ptr(), int(k.is_cuda)
+        else:
+            k = np.ascontiguousarray(np.asarray(kept).astype(np.uint32, copy=False))
+            n, ptr, on_dev = int(k.size), k.ctypes.data, 0
+        h = C.c_void_p()
+        rows = torch.empty(n, dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+        _check(self.lib.gaib_graph_induce(self.ctx.h, self.h, n, ptr if n else None, on_dev,
+                                          INDUCE_KEEP_IDS if keep_ids else INDUCE_RELABEL, C.byref(h), rows.data_ptr() if n else None),
+               "gaib_graph_induce")
+        return Graph(self.ctx, _handle=h), rows
 
     def sort_rows(self):
         """sort every row's column ids (a relabelled graph keeps its rows' edge order: GAT backward needs sorted rows)"""

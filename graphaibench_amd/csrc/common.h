@@ -109,6 +109,7 @@ struct gaib_ctx {
   int gat_interleave;        // one-sweep GAT backward: 1 = gather from ONE interleaved [h | grad | records] row per vertex (built per call), 0 = three tables
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort
+  int sampler_device;        // read by the trainer: 1 = sampled subgraphs are induced on the device (gaib_graph_induce), 0 (default) = on the host
   hipStream_t owned_stream;  // gaib_ctx_own_stream: a stream the context created (destroyed with it), else NULL
   int capturing;             // 1 between gaib_capture_begin and gaib_capture_end: calls are recorded into a HIP graph, nothing runs
   // recorded sequences (gaib_exec) freeze the ws / pad pointers of their capture in their kernel nodes: while any of
@@ -208,6 +209,9 @@ struct gaib_graph {
   int64_t n_out_rows;
   int rows_unsorted;  // 1: a row's column ids are not ascending (gaib_graph_reorder keeps the edge ORDER of every row);
                       // the reverse-edge permutation needs sorted rows: gaib_graph_sort_rows first
+  // membership bitmap of gaib_graph_induce (induce.hip): nv bits in 64-bit words + one prefix count per word; lazily, cleared per call
+  void* induce_bits;        // uint64 [ceil(nv / 64)]
+  uint32_t* induce_prefix;  // [ceil(nv / 64) + 1] kept vertices in the words before
   float near_frac;  // share of (sampled) edges whose column id lies within 32 768 of the row id: locality of the numbering; < 0 = not measured yet
 };
 
@@ -220,6 +224,9 @@ int gaib_graph_ensure_rev(gaib_ctx* ctx, gaib_graph* g);
 int gaib_graph_ensure_heavy(gaib_ctx* ctx, gaib_graph* g, int thr);
 int gaib_graph_ensure_chunks(gaib_ctx* ctx, gaib_graph* g);
 int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int len);
+int gaib_graph_ensure_induce(gaib_ctx* ctx, gaib_graph* g);
+// an empty square graph of nv rows with rowptr [nv + 1] and colidx [ne] allocated, nothing filled (graph.hip)
+int gaib_graph_new(int64_t nv, int64_t ne, int device, gaib_graph** out);
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

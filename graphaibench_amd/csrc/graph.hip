@@ -149,6 +149,8 @@ int new_graph(int64_t nv, int64_t ne, int device, gaib_graph** out) {
 
 }  // namespace
 
+int gaib_graph_new(int64_t nv, int64_t ne, int device, gaib_graph** out) { return new_graph(nv, ne, device, out); }
+
 extern "C" int gaib_graph_create(gaib_ctx* ctx, int64_t nv, int64_t ne, const void* rowptr,
                                  int rowptr_bits, const uint32_t* colidx, int src_on_device,
                                  gaib_graph** out) {
@@ -246,7 +248,8 @@ extern "C" int gaib_graph_destroy(gaib_graph* g) {
   (void)hipSetDevice(g->device);
   void* ptrs[] = {g->rowptr, g->colidx,   g->vdata, g->edata,      g->inv_deg,  g->col_vdata,
                   g->col_inv_deg, g->w_gcn, g->w_mean_t, g->rev,   g->heavy_rows,
-                  g->chunk_row, g->chunk_ebase, g->chunk_start, g->colidx_flagged, g->row_map};
+                  g->chunk_row, g->chunk_ebase, g->chunk_start, g->colidx_flagged, g->row_map,
+                  g->induce_bits, g->induce_prefix};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete g;

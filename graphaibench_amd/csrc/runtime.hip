@@ -81,6 +81,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->gat_chunk_sort = 1;
   c->gat_chunk_colsum = -1;
   c->graph_rev_search = 0;
+  c->sampler_device = 0;
   c->gat_fused_bwd = -1;
   c->gat_fused_fwd = -1;
   c->gat_fused_unroll = 4;
@@ -543,6 +544,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
   else if (!strcmp(key, "spmm_bf16_pad")) *h_value = ctx->spmm_bf16_pad;
   else if (!strcmp(key, "agg_bf16_ld_last")) *h_value = ctx->agg_bf16_ld_last;
+  else if (!strcmp(key, "sampler_device")) *h_value = ctx->sampler_device;
   else {
     gaib_set_error("gaib_get_option: no readable option '%s'", key);
     return GAIB_ERR_INVALID;
@@ -642,7 +644,10 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
     ctx->gat_fused_bwd = (int)value;
   else if (!strcmp(key, "graph_rev_search"))
     ctx->graph_rev_search = (int)value;
-  else if (!strcmp(key, "gat_row_waves")) {
+  else if (!strcmp(key, "sampler_device")) {
+    GAIB_CHECK(value == 0 || value == 1, "sampler_device must be 0 (subgraphs built on the host) or 1 (on the device)");
+    ctx->sampler_device = (int)value;
+  } else if (!strcmp(key, "gat_row_waves")) {
     GAIB_CHECK(value == 1 || value == 2 || value == 4, "gat_row_waves must be 1, 2 or 4");
     ctx->gat_row_waves = (int)value;
   }

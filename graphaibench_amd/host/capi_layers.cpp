@@ -151,6 +151,128 @@ float* gaibl_layer_ptr(void* layer, int which) {
   }
 }
 
+int gaibl_parse_switch(const char* value) { return gpu_context::parse_switch(value); }
+
+// ---- measurement hook: the per-epoch span of train_main.cpp's subgraph_sampling() after vertex selection, call for call ----
+namespace {
+struct SamplingHarness {
+  Graph* full;
+  Graph* training;
+  Sampler* sampler;
+  Graph* sg;
+  size_t nv;
+  int dim, label_width;
+  const float* feats_host;
+  const uint8_t* labels_host;
+  const float* d_features;
+  const uint8_t* d_labels;
+  float* d_feats_subg;
+  uint8_t* d_labels_subg;
+  int64_t* d_rows;
+  std::vector<mask_t> subg_masks;
+  VertexSet set;
+};
+}  // namespace
+
+void* gaibl_sampling_create(uint32_t nv, uint32_t ne, const uint32_t* rowptr, const uint32_t* colidx, const uint8_t* train_masks,
+                            int dim, int label_width, const float* feats_host, const uint8_t* labels_host,
+                            const float* d_features, const uint8_t* d_labels, uint32_t max_subg) {
+  SamplingHarness* s = new SamplingHarness();
+  s->full = new Graph(true);
+  s->full->allocateFrom(nv, ne);
+  memcpy(s->full->row_host_ptr(), rowptr, sizeof(uint32_t) * ((size_t)nv + 1));
+  if (ne) memcpy(s->full->edge_host_ptr(), colidx, sizeof(uint32_t) * ne);
+  s->full->copy_to_gpu();
+  std::vector<mask_t> masks(train_masks, train_masks + nv);
+  size_t cnt = 0;
+  for (auto b : masks) cnt += b;
+  // (every vertex a training vertex: the masked graph is the full graph -- no second copy of a products-size CSR)
+  s->training = cnt == nv ? s->full : s->full->generate_masked_graph(masks.data());
+  s->sampler = new Sampler(s->full, s->training, masks.data(), cnt);
+  s->sg = new Graph(true);
+  s->nv = nv;
+  s->dim = dim;
+  s->label_width = label_width;
+  s->feats_host = feats_host;
+  s->labels_host = labels_host;
+  s->d_features = d_features;
+  s->d_labels = d_labels;
+  gaib_ctx* c = gpu_context::get();
+  GAIB_OR_DIE(gaib_malloc(c, sizeof(float) * (size_t)max_subg * dim, (void**)&s->d_feats_subg));
+  GAIB_OR_DIE(gaib_malloc(c, (size_t)max_subg * label_width, (void**)&s->d_labels_subg));
+  GAIB_OR_DIE(gaib_malloc(c, sizeof(int64_t) * (size_t)max_subg, (void**)&s->d_rows));
+  s->subg_masks.resize(nv);
+  return s;
+}
+
+uint32_t gaibl_sampling_select(void* h, uint32_t n, uint32_t m, unsigned seed) {
+  SamplingHarness* s = static_cast<SamplingHarness*>(h);
+  s->set.clear();
+  s->sampler->set_frontier_size(m);
+  return (uint32_t)s->sampler->select_vertices(n, s->set, seed);
+}
+
+void gaibl_sampling_kept(void* h, uint32_t* out) {
+  for (index_t v : static_cast<SamplingHarness*>(h)->set) *out++ = v;
+}
+
+double gaibl_sampling_build(void* h, int on_device) {
+  SamplingHarness* s = static_cast<SamplingHarness*>(h);
+  gaib_ctx* c = gpu_context::get();
+  const double t0 = omp_get_wtime();
+  if (on_device) {
+    s->sampler->generateSubgraphDevice(s->set, s->sg, s->d_rows);
+    const int64_t n = (int64_t)s->sg->size();
+    s->sg->compute_vertex_data();
+    GAIB_OR_DIE(gaib_gather_rows(c, n, s->d_rows, s->dim, s->d_features, s->d_feats_subg));
+    GAIB_OR_DIE(gaib_gather_rows_u8(c, n, s->d_rows, s->label_width, s->d_labels, s->d_labels_subg));
+  } else {
+    s->sampler->generateSubgraph(s->set, s->subg_masks.data(), s->sg);
+    s->sg->degree_counting();
+    const size_t n = s->sg->size();
+    s->sg->copy_to_gpu();
+    s->sg->compute_vertex_data();
+    const size_t dim = (size_t)s->dim, lw = (size_t)s->label_width;
+    std::vector<float> f(n * dim);
+    std::vector<label_t> lab(n * lw);
+    size_t k = 0;
+    for (size_t v = 0; v < s->nv; v++)
+      if (s->subg_masks[v] == 1) {
+        std::copy(&s->feats_host[v * dim], &s->feats_host[(v + 1) * dim], &f[k * dim]);
+        std::copy(&s->labels_host[v * lw], &s->labels_host[(v + 1) * lw], &lab[k * lw]);
+        k++;
+      }
+    GAIB_OR_DIE(gaib_memcpy_h2d(c, s->d_feats_subg, f.data(), sizeof(float) * f.size()));
+    GAIB_OR_DIE(gaib_memcpy_h2d(c, s->d_labels_subg, lab.data(), lab.size()));
+  }
+  gpu_context::sync();
+  return omp_get_wtime() - t0;
+}
+
+void* gaibl_sampling_ptr(void* h, int which) {
+  SamplingHarness* s = static_cast<SamplingHarness*>(h);
+  return which == 0 ? (void*)s->sg->device_graph() : (which == 1 ? (void*)s->d_feats_subg : (void*)s->d_labels_subg);
+}
+
+void gaibl_sampling_free(void* h) {
+  SamplingHarness* s = static_cast<SamplingHarness*>(h);
+  gaib_ctx* c = gpu_context::get();
+  gpu_context::sync();
+  gaib_free(c, s->d_feats_subg);
+  gaib_free(c, s->d_labels_subg);
+  gaib_free(c, s->d_rows);
+  delete s->sampler;
+  if (s->training != s->full) {
+    s->training->dealloc();
+    delete s->training;
+  }
+  s->full->dealloc();
+  delete s->full;
+  s->sg->dealloc();
+  delete s->sg;
+  delete s;
+}
+
 uint32_t gaibl_sample_subgraph(uint32_t nv, uint32_t ne, const uint32_t* rowptr, const uint32_t* colidx,
                                const uint8_t* train_masks, uint32_t n, uint32_t m, unsigned seed,
                                uint32_t** sub_rowptr, uint32_t** sub_colidx, uint32_t** kept_ids) {

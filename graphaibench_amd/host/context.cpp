@@ -24,6 +24,12 @@ void gpu_context::check(int status, const char* what) {
   exit(EXIT_FAILURE);
 }
 
+// "0" / "1" -> 0 / 1, anything else -> -1 (the 0|1 switches of the environment)
+int gpu_context::parse_switch(const char* value) {
+  if (!value || !value[0] || value[1]) return -1;
+  return value[0] == '0' ? 0 : (value[0] == '1' ? 1 : -1);
+}
+
 void gpu_context::set(int device, void* hip_stream) {
   if (g_ctx) {
     gaib_ctx_destroy(g_ctx);
@@ -76,6 +82,16 @@ void gpu_context::set(int device, void* hip_stream) {
       exit(EXIT_FAILURE);
     }
     check(gaib_set_option(g_ctx, "agg_zs_wide", v == "1" ? 1 : 0), "gaib_set_option (GAIB_AGG_ZS_WIDE)");
+  }
+  // sampled training (subg_size > 0): every epoch's subgraph, feature rows and label rows built on the device (option
+  // sampler_device; off by default)
+  if (const char* d = getenv("GAIB_SAMPLER_DEVICE")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_SAMPLER_DEVICE=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "sampler_device", v), "gaib_set_option (GAIB_SAMPLER_DEVICE)");
   }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {

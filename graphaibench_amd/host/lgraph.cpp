@@ -14,6 +14,15 @@ LearningGraph* LearningGraph::adopt_device(gaib_graph* g) {
   return lg;
 }
 
+void LearningGraph::adopt_device_graph(gaib_graph* g) {
+  dealloc();  // host arrays, the former device half, class graphs
+  is_device = true;
+  num_vertices_ = (index_t)gaib_graph_nv(g);
+  num_edges_ = (index_t)gaib_graph_ne(g);
+  max_degree = 0;
+  dev_ = g;
+}
+
 void LearningGraph::halo_begin(int len, const float* d_in) {
   if (halo_plan_) GAIB_OR_DIE(gaib_halo_exchange_begin(halo_plan_, len, d_in));
   else if (halo_begin_) halo_begin_(halo_user_, len, d_in);
@@ -360,6 +369,7 @@ void LearningGraph::copy_to_cpu() {
   std::vector<int64_t> rp(nv + 1);
   delete[] rowptr_;
   delete[] colidx_;
+  rowptr_ = colidx_ = NULL;
   allocateFrom((index_t)nv, (index_t)ne);
   GAIB_OR_DIE(gaib_memcpy_d2h(gpu_context::get(), rp.data(), gaib_graph_rowptr(dev_), sizeof(int64_t) * (nv + 1)));
   for (int64_t i = 0; i <= nv; i++) rowptr_[i] = (index_t)rp[i];

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <utility>
 #include "sampler.h"
+#include "gpu_context.h"
 
 Sampler::Sampler(Graph* g, Graph* tg, mask_t* masks, size_t count)
     : m(DEFAULT_SIZE_FRONTIER), count_(count), full_graph(g), masked_graph(tg) {
@@ -196,4 +197,12 @@ void Sampler::generateSubgraph(VertexSet& vertex_set, mask_t* masks, Graph* sg) 
     sg->fixEndEdge(k, off[k + 1]);
     k++;
   }
+}
+
+void Sampler::generateSubgraphDevice(const VertexSet& vertex_set, Graph* sg, int64_t* d_rows) {
+  const std::vector<index_t> kept(vertex_set.begin(), vertex_set.end());  // (std::set iterates in ascending order)
+  gaib_graph* induced = NULL;
+  GAIB_OR_DIE(gaib_graph_induce(gpu_context::get(), full_graph->device_graph(), (int64_t)kept.size(), kept.data(), 0,
+                                GAIB_INDUCE_RELABEL, &induced, d_rows));
+  sg->adopt_device_graph(induced);
 }

@@ -87,6 +87,10 @@ struct Trainer {
   int num_subgraphs = 1, subg_nv = 0;
   float* d_feats_subg = nullptr;
   label_t* d_labels_subg = nullptr;
+  // option sampler_device (GAIB_SAMPLER_DEVICE=1): the subgraph, its feature rows and its label rows are built on the device
+  bool sampler_device = false;
+  std::vector<VertexSet> subg_sets;  // the sampled vertex sets of the round (device path: the subgraph is induced per epoch)
+  int64_t* d_rows_subg = nullptr;    // [subg_size] the kept ids of the epoch's subgraph
   // network
   std::vector<gconv_t> layers;
   l2norm_layer* l2 = nullptr;
@@ -400,16 +404,26 @@ struct Trainer {
         std::cout << "disabling validation for subgraph sampling on GPU\n";
         val_interval = num_epochs;
       }
-      feats_host = feats;
-      labels_host = labels;
+      int64_t on_device = 0;
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "sampler_device", &on_device));
+      sampler_device = on_device != 0;
+      if (!sampler_device) {  // (the device path gathers from d_features / d_labels)
+        feats_host = feats;
+        labels_host = labels;
+      }
       masks_train_host = mtrain;
       num_subgraphs = num_threads > 0 ? num_threads : 1;
       sampler = new Sampler(graph, training_graph, masks_train_host.data(), train_count);
       subgs.resize(num_subgraphs);
       for (auto& g : subgs) g = new Graph(true);
-      subg_masks.resize((size_t)num_samples * num_subgraphs);
+      if (!sampler_device) subg_masks.resize((size_t)num_samples * num_subgraphs);
       float_malloc_device64((size_t)subg_size * dim_init, d_feats_subg);
       uint8_malloc_device(subg_size * label_width, d_labels_subg);
+      if (sampler_device) {
+        subg_sets.resize(num_subgraphs);
+        GAIB_OR_DIE(gaib_malloc(gpu_context::get(), sizeof(int64_t) * (size_t)subg_size, (void**)&d_rows_subg));
+        std::cout << "subgraphs: built on the device\n";
+      }
     }
   }
 
@@ -420,15 +434,23 @@ struct Trainer {
       for (int sid = 0; sid < num_subgraphs; sid++) {
         VertexSet set;
         sampler->select_vertices(subg_size, set, (unsigned)omp_get_thread_num());  // seed = thread id, as net.cpp:298
-        sampler->generateSubgraph(set, &subg_masks[(size_t)sid * num_samples], subgs[sid]);
+        if (sampler_device) subg_sets[sid].swap(set);  // (induced on the device below, one per epoch)
+        else sampler->generateSubgraph(set, &subg_masks[(size_t)sid * num_samples], subgs[sid]);
       }
       num_subg_remain = num_subgraphs;
     }
     const int sg_id = --num_subg_remain;
     Graph* sg = subgs[sg_id];
-    sg->degree_counting();
-    subg_nv = sg->size();
-    sg->copy_to_gpu();  // subgraphs of the self-looped full graph already carry their self loops
+    if (sampler_device) {
+      // one induce call (one 16-byte read-back), the normalisers, two row gathers from the tables already in HBM: no host copy
+      // of features, labels or masks; nothing reads a subgraph's max_degree, so degree_counting() is not run
+      sampler->generateSubgraphDevice(subg_sets[sg_id], sg, d_rows_subg);
+      subg_nv = sg->size();
+    } else {
+      sg->degree_counting();
+      subg_nv = sg->size();
+      sg->copy_to_gpu();  // subgraphs of the self-looped full graph already carry their self loops
+    }
     sg->compute_vertex_data();
     for (auto& l : layers) {
       l.update_dim_size(subg_nv);
@@ -437,6 +459,14 @@ struct Trainer {
     if (use_l2norm) l2->update_dim_size(subg_nv);
     if (use_dense) dense->update_dim_size(subg_nv);
     loss->update_dim_size(subg_nv);
+    if (sampler_device) {
+      gaib_ctx* c = gpu_context::get();
+      GAIB_OR_DIE(gaib_gather_rows(c, subg_nv, d_rows_subg, dim_init, d_features, d_feats_subg));
+      GAIB_OR_DIE(gaib_gather_rows_u8(c, subg_nv, d_rows_subg, label_width, d_labels, d_labels_subg));
+      layers[0].set_feat_in(d_feats_subg);
+      loss->set_labels_ptr(d_labels_subg);
+      return;
+    }
     // features / labels of the kept vertices, in subgraph order
     const mask_t* mk = &subg_masks[(size_t)sg_id * num_samples];
     std::vector<float> f((size_t)subg_nv * dim_init);
@@ -676,6 +706,7 @@ struct Trainer {
     // comparison of loss curves would otherwise see (bench.py's epoch parity holds the curve to 1e-4 relative)
     const bool exact_losses = getenv("GAIB_EPOCH_LOSSES") && atoi(getenv("GAIB_EPOCH_LOSSES")) != 0;
     std::vector<double> all_loss, all_acc;
+    std::vector<double> subgraph_s;  // (GAIB_EPOCH_TIMES with sampling) seconds per epoch in subgraph_sampling
     for (int itr = 0; itr < num_epochs; itr++) {
       if (itr == prof_from) {
         GAIB_OR_DIE(gaib_prof_reset(gpu_context::get()));
@@ -683,7 +714,17 @@ struct Trainer {
       }
       if (prof_from >= 0 && itr >= prof_from) prof_epochs++;
       const unsigned long long edges_before = gpu_context::aggregated_edges();
-      if (subg_size > 0) subgraph_sampling(num_subg_remain);
+      if (subg_size > 0) {
+        // GAIB_EPOCH_TIMES: one wall time per epoch around the subgraph's construction, its device work waited for inside
+        // the span ("[gaib prof] subgraph_seconds ...": the in-trainer measurement of option sampler_device, both settings)
+        const bool timed = et && *et && itr >= times_from;
+        const double ts = timed ? omp_get_wtime() : 0.0;
+        subgraph_sampling(num_subg_remain);
+        if (timed) {
+          gpu_context::sync();
+          subgraph_s.push_back(omp_get_wtime() - ts);
+        }
+      }
       std::cout << "Epoch " << std::setw(3) << itr << " ";
       set_phase(net_phase::TRAIN);
       acc_t train_loss = 0.0;
@@ -752,6 +793,11 @@ struct Trainer {
     if (prof_from < 0 && !prof_epoch_s.empty() && root()) {
       std::cout << "[gaib prof] epoch_seconds";
       for (double t : prof_epoch_s) std::cout << " " << std::setprecision(7) << std::fixed << t;
+      std::cout << std::setprecision(3) << "\n";
+    }
+    if (!subgraph_s.empty() && root()) {
+      std::cout << "[gaib prof] subgraph_seconds";
+      for (double t : subgraph_s) std::cout << " " << std::setprecision(7) << std::fixed << t;
       std::cout << std::setprecision(3) << "\n";
     }
     if (prof_from >= 0 && prof_epochs > 0) {

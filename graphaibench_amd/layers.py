@@ -41,6 +41,13 @@ SIGNATURES = {
     "gaibl_sample_subgraph": (C.c_uint32, [C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint,
                                            C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "gaibl_free_host": (None, [_vp]),
+    "gaibl_parse_switch": (_i, [C.c_char_p]),
+    "gaibl_sampling_create": (_vp, [C.c_uint32, C.c_uint32, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "gaibl_sampling_select": (C.c_uint32, [_vp, C.c_uint32, C.c_uint32, C.c_uint]),
+    "gaibl_sampling_kept": (None, [_vp, _vp]),
+    "gaibl_sampling_build": (C.c_double, [_vp, _i]),
+    "gaibl_sampling_ptr": (_vp, [_vp, _i]),
+    "gaibl_sampling_free": (None, [_vp]),
     "gaibl_partition_build": (_vp, [C.c_uint32, _vp, _vp, _i, _i]),
     "gaibl_partition_build_gat": (None, [_vp, _vp, _vp]),
     "gaibl_partition_array": (C.c_int64, [_vp, _i, C.POINTER(_vp)]),

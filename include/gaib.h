@@ -180,6 +180,24 @@ int gaib_graph_reorder(gaib_ctx* ctx, gaib_graph* g, int method, gaib_graph** ou
  * column ids (in place; per-edge caches are rebuilt on demand): everything runs on it, and aggregation results are then equal
  * to the original numbering's up to fp32 summation order instead of bit for bit. */
 int gaib_graph_sort_rows(gaib_ctx* ctx, gaib_graph* g);
+/* The subgraph a vertex set induces on g, built on the device -- what the sampled path of the trainer rebuilds every epoch.
+ *   kept [n_kept]: vertex ids of g, STRICTLY ASCENDING, every id < nv; host memory, or device memory with kept_on_device != 0.
+ *   GAIB_INDUCE_RELABEL : n_kept rows; row k holds the kept neighbours of kept[k], renumbered by their position in `kept`
+ *                         (Sampler::generateSubgraph, src/gnn/sampler.cpp).  n_kept == nv reproduces g's CSR.
+ *   GAIB_INDUCE_KEEP_IDS: nv rows under g's own ids; the row of a dropped vertex is empty, a kept row keeps its kept neighbours
+ *                         (LearningGraph::generate_masked_graph).
+ * *out is an ordinary square graph: every row keeps the ORDER of its surviving edges (sorted rows stay sorted), self loops
+ * survive.  d_rows_out (device int64 [n_kept], may be NULL) receives the kept ids widened: the index list gaib_gather_rows /
+ * gaib_gather_rows_u8 take for the feature / label rows.  n_kept == 0 is valid (a graph of 0 rows; nv empty rows in KEEP_IDS).
+ * Refusals create nothing and leave the graph's cached bitmap reusable: a rectangular g -> GAIB_ERR_UNSUPPORTED; a list that is
+ * not strictly ascending or holds an id >= nv -> GAIB_ERR_INVALID (found on the device; the bad id is never used as an
+ * address; d_rows_out may then be partly written); inside a recording -> GAIB_ERR_INVALID (the call allocates and waits once).
+ * Cost: one stream wait and one 16-byte read-back (edge count + flag) per call; work proportional to the kept rows' edges, plus
+ * nv / 8 bytes cleared (the membership bitmap cached on g; KEEP_IDS also writes its nv + 1 row pointers).  DESIGN.md 10. */
+#define GAIB_INDUCE_RELABEL 0
+#define GAIB_INDUCE_KEEP_IDS 1
+int gaib_graph_induce(gaib_ctx* ctx, gaib_graph* g, int64_t n_kept, const uint32_t* kept, int kept_on_device, int mode,
+                      gaib_graph** out, int64_t* d_rows_out);
 int64_t gaib_graph_nv(const gaib_graph* g);
 int64_t gaib_graph_ne(const gaib_graph* g);
 int64_t gaib_graph_nc(const gaib_graph* g); /* columns = rows of the feature table its column ids index (nv unless rectangular) */
@@ -665,6 +683,10 @@ int gaib_adam_step_dev(gaib_ctx* ctx, int64_t n, const float* d_dW, float* d_W, 
  * pack rows for the halo exchange: d_out[k,:] = d_in[d_idx[k],:] */
 int gaib_gather_rows(gaib_ctx* ctx, int64_t n_idx, const int64_t* d_idx, int len,
                      const float* d_in, float* d_out);
+/* the same for rows of width_bytes bytes (label rows: 1 byte single-class, one byte per class multi-label); any width >= 1,
+ * no alignment beyond one byte asked of d_in or d_out */
+int gaib_gather_rows_u8(gaib_ctx* ctx, int64_t n_idx, const int64_t* d_idx, int width_bytes, const uint8_t* d_in,
+                        uint8_t* d_out);
 /* out[dst_idx[k], :] = in[src_idx[k], :], dst rows distinct.  The halo plans pack with it in SOURCE order (src ascending):
  * a row that goes to several peers is read from HBM once (its repeats hit the cache) instead of once per peer. */
 int gaib_gather_scatter_rows(gaib_ctx* ctx, int64_t n_idx, const int64_t* d_src_idx, const int64_t* d_dst_idx, int len,
@@ -836,12 +858,15 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
- * kernel (row form, 8-row strip, buffer addressing, 65..128 columns): 0 = what ships, 16 / 32 = that depth.  Same bits. */
+ * kernel (row form, 8-row strip, buffer addressing, 65..128 columns): 0 = what ships, 16 / 32 = that depth.  Same bits.
+ * "sampler_device" (default 0; readable): read by the trainer, not by the library: 1 = every sampled epoch's subgraph, feature
+ * rows and label rows are built on the device (gaib_graph_induce, gaib_gather_rows, gaib_gather_rows_u8), 0 = on the host. */
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
- * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel" */
+ * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
+ * "sampler_device" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

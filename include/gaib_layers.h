@@ -91,6 +91,29 @@ uint32_t gaibl_sample_subgraph(uint32_t nv, uint32_t ne, const uint32_t* rowptr,
                                const uint8_t* train_masks, uint32_t n, uint32_t m, unsigned seed,
                                uint32_t** sub_rowptr, uint32_t** sub_colidx, uint32_t** kept_ids);
 void gaibl_free_host(void* p);
+/* host-only test hook: how the context reads a 0|1 switch of the environment (GAIB_SAMPLER_DEVICE): "0" -> 0, "1" -> 1,
+ * anything else -> -1, which the context answers with a message and exit status 1 */
+int gaibl_parse_switch(const char* value);
+
+/* measurement hook (scripts/induce_subgraph.py): what the trainer's subgraph_sampling() does per epoch AFTER vertex selection,
+ * call for call, in either setting of option sampler_device, on a graph and tables the caller brings.
+ *   create: host CSR (uint32 row pointers; uploaded once), training masks, the feature / label tables on the host
+ *           ([nv x dim] floats, [nv x label_width] bytes; borrowed: they must outlive the handle) and the same tables on the
+ *           device (borrowed), max_subg = the largest vertex set that will be selected
+ *   select: Sampler::select_vertices(n, seed) with frontier size m into the handle's vertex set; returns its size
+ *   kept  : the set's ids, ascending, into out[size]
+ *   build : on_device = 0: generateSubgraph + degree_counting + copy_to_gpu + compute_vertex_data + the host row gather of
+ *           features and labels + their upload; 1: generateSubgraphDevice + compute_vertex_data + gaib_gather_rows +
+ *           gaib_gather_rows_u8.  Waits for the stream; returns the wall seconds of the span.
+ *   ptr   : 0 = the subgraph's gaib_graph*, 1 = its feature rows (device), 2 = its label rows (device) */
+void* gaibl_sampling_create(uint32_t nv, uint32_t ne, const uint32_t* rowptr, const uint32_t* colidx, const uint8_t* train_masks,
+                            int dim, int label_width, const float* feats_host, const uint8_t* labels_host,
+                            const float* d_features, const uint8_t* d_labels, uint32_t max_subg);
+uint32_t gaibl_sampling_select(void* h, uint32_t n, uint32_t m, unsigned seed);
+void gaibl_sampling_kept(void* h, uint32_t* out);
+double gaibl_sampling_build(void* h, int on_device);
+void* gaibl_sampling_ptr(void* h, int which);
+void gaibl_sampling_free(void* h);
 
 /* row classes of a partitioned graph (LearningGraph::partition_mode, include/gnn/lgraph.h): mode 0 = column split over
  * all rows, 1 = interior rows in one pass + column split of the boundary rows, 2 = interior rows in one pass + the

@@ -90,6 +90,10 @@ class LearningGraph {
   LearningGraph() : LearningGraph(true) {}
   // wrap a graph that already lives in HBM (synthetic / partitioned graphs built on device)
   static LearningGraph* adopt_device(gaib_graph* g);
+  // the same in place (extension: a subgraph rebuilt on the device every epoch, Sampler::generateSubgraphDevice): this object
+  // takes `g` over, drops its host arrays and its former device half and takes its sizes from the handle; copy_to_cpu()
+  // brings the CSR to the host where somebody wants it there
+  void adopt_device_graph(gaib_graph* g);
 
   size_t size() { return (size_t)num_vertices_; }
   size_t sizeEdges() { return (size_t)num_edges_; }

@@ -23,6 +23,10 @@ class Sampler {
   ~Sampler() {}
   // build the subgraph induced by `vertex_set` on the full graph; masks[v] = 1 for kept vertices
   void generateSubgraph(VertexSet& vertex_set, mask_t* masks, Graph* sg);
+  // extension (no reference counterpart): the same subgraph induced on the DEVICE copy of the full graph
+  // (gaib_graph_induce on full_graph->device_graph()); sg adopts it (no host arrays), d_rows (device int64 [vertex_set.size()],
+  // may be NULL) receives the kept ids -- the index list gaib_gather_rows / gaib_gather_rows_u8 take for features and labels
+  void generateSubgraphDevice(const VertexSet& vertex_set, Graph* sg, int64_t* d_rows);
   // sample up to n vertices into vertex_set (may return fewer: repeated picks); returns its size
   size_t select_vertices(index_t n, VertexSet& vertex_set, unsigned seed);
   void set_frontier_size(index_t f) { m = f; }  // extension (tests); default DEFAULT_SIZE_FRONTIER
