@@ -107,6 +107,7 @@ struct gaib_ctx {
   int gat_bwd_pk;            // one-sweep GAT backward: 1 = the packed-math kernel over the element-interleaved table (round 6), 0 (default) = the round-5 kernel
   int gat_bf16;              // 1: the layer library's GAT aggregation runs its one-sweep forward and backward on bf16 copies of h and grad (gaib_gat_*_fused_bf16)
   int gat_interleave;        // one-sweep GAT backward: 1 = gather from ONE interleaved [h | grad | records] row per vertex (built per call), 0 = three tables
+  int gat_fused_drop;        // 1: the layer library's GAT aggregation keeps the one sweep under attention dropout (gaib_gat_*_fused_drop), 0 (default) = staged
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort
   int sampler_device;        // read by the trainer: 1 = sampled subgraphs are induced on the device (gaib_graph_induce), 0 (default) = on the host
@@ -230,6 +231,21 @@ int gaib_graph_new(int64_t nv, int64_t ne, int device, gaib_graph** out);
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// counter-based uniform in [0,1): splitmix64 of (seed, index).  The reference draws from
+// cuRAND XORWOW (GPU, math_functions.cu:123-132) or boost mt19937 (CPU, :390-429); masks are
+// therefore not comparable across implementations, only their statistics and the replay.
+// In two steps, because the key is linear in the index: a kernel that walks indices at a fixed stride (the one-sweep GAT
+// kernels under attention dropout) adds U01_GOLD * stride to the key instead of multiplying again -- the same bits mod 2^64.
+constexpr uint64_t U01_GOLD = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ uint64_t u01_key(uint64_t seed, uint64_t i) { return seed + U01_GOLD * (i + 1); }
+__device__ __forceinline__ float u01_of_key(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z = z ^ (z >> 31);
+  return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+__device__ __forceinline__ float u01(uint64_t seed, uint64_t i) { return u01_of_key(u01_key(seed, i)); }
+
 // wave-level helpers -------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -262,6 +278,19 @@ __device__ __forceinline__ float lanes_sum(float v) {
   if constexpr (LH >= 4) v += dpp_f32<0x4E>(v);    // quad_perm [2,3,0,1]
   if constexpr (LH >= 8) v += dpp_f32<0x141>(v);   // row_half_mirror: the other quad of the half row
   if constexpr (LH >= 16) v += dpp_f32<0x140>(v);  // row_mirror: the other half row
+  return v;
+}
+// bitwise OR over the aligned group of LH consecutive lanes (LH = 1 .. 32); every lane gets it
+template <int LH>
+__device__ __forceinline__ uint32_t lanes_or(uint32_t v) {
+  static_assert(LH == 1 || LH == 2 || LH == 4 || LH == 8 || LH == 16 || LH == 32, "aligned power-of-two groups of up to two 16-lane rows");
+#define GAIB_OR_DPP(CTRL) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false)
+  if constexpr (LH >= 2) GAIB_OR_DPP(0xB1);    // (the patterns of lanes_sum)
+  if constexpr (LH >= 4) GAIB_OR_DPP(0x4E);
+  if constexpr (LH >= 8) GAIB_OR_DPP(0x141);
+  if constexpr (LH >= 16) GAIB_OR_DPP(0x140);
+#undef GAIB_OR_DPP
+  if constexpr (LH >= 32) v |= (uint32_t)__shfl_xor((int)v, 16, 64);
   return v;
 }
 // lane n (0..15, a compile-time constant after unrolling) of this lane's 16-lane row

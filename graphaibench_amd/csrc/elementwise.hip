@@ -66,17 +66,7 @@ __global__ void d_relu_kernel(int64_t n, const float* in, const float* data, flo
   }
 }
 
-// counter-based uniform in [0,1): splitmix64 of (seed, index).  The reference draws from
-// cuRAND XORWOW (GPU, math_functions.cu:123-132) or boost mt19937 (CPU, :390-429); masks are
-// therefore not comparable across implementations, only their statistics and the replay.
-__device__ __forceinline__ float u01(uint64_t seed, uint64_t i) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-// dropout_kernel: mask = rand > p; out = in * mask * scale   (math_functions.cu:114-121)
+// dropout_kernel (u01: common.h): mask = rand > p; out = in * mask * scale   (math_functions.cu:114-121)
 __global__ void dropout_kernel(int64_t n, float scale, float rate, uint64_t seed, const float* in,
                                uint8_t* masks, float* out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;

@@ -1,7 +1,8 @@
 // gat_kernels.h -- the GAT kernels that more than one translation unit instantiates: the one-sweep forward and backward
 // (chunk kernels, the packed-math sweep, their reductions), the per-vertex dots and the alpha-gradient reduction, with the
 // shape rules and dispatch macros of their callers.  gat.hip instantiates them on fp32 tables, gat_bf16.hip on bf16 tables
-// (element type E = uint16_t: raw bf16 bits, loaded as they are and widened where they are consumed).
+// (element type E = uint16_t: raw bf16 bits, loaded as they are and widened where they are consumed), gat_drop.hip the DROP
+// variants of the two sweeps (attention dropout, fp32 tables).
 #pragma once
 #include "common.h"
 
@@ -217,12 +218,48 @@ __global__ __launch_bounds__(256) void gat_interleave_kernel(int64_t nv, int len
   }
 }
 
-template <int G, int H, int U, bool RECOMP, typename E>
+// ---- attention dropout inside the one-sweep kernels (DROP; gat_drop.hip) ---------------------------------------------------
+// w_(e,k) = mask . scale with mask = u01(seed, e * H + k) > rate: the mask gaib_dropout draws for element e * H + k of an
+// [ne][H] array under the same seed (e: the edge's position in the CSR, k: the head), formed here instead of read -- no edge
+// array exists.  A 64-bit splitmix per lane and step would be redundant over the LH lanes of a head and costs more than the
+// step it gates (the sweeps are VALU-bound), so a chunk's masks are formed ONCE, ahead of the edge loop: the LH lanes of a
+// head share its G steps -- lane q of the head takes steps q, q + LH, ... (H hashes per lane instead of G), one bit per
+// step, and an OR over the head's lanes (DPP) leaves all G bits in each of them.  In the loop the mask of step t is bit t.
+// IDS = false: the chunk's own edges eb + (edge of the step) -- consecutive steps of a lane are LH * NG edges apart, so the
+// key of the next step is an addition; else the ids are read from ids[] at those positions (the reverse edges).
+template <int G, int H, bool IDS>
+__device__ __forceinline__ uint32_t gat_drop_bits(int lane, int n, int64_t eb, const uint32_t* ids, uint64_t seed, float rate) {
+  constexpr int LH = G / H;
+  using CL = ChunkLanes<G>;
+  constexpr int NG = CL::NG;
+  const int sl = lane & (G - 1);
+  const int head = sl / LH, q = sl & (LH - 1);
+  const int e0 = CL::step_edge(lane, q);  // step t of this lane's group is edge e0 + (t - q) * NG
+  uint64_t z = u01_key(seed, (uint64_t)(eb + e0) * (uint64_t)H + (uint64_t)head);  // (the index in 64 bits: ne * H passes 2^32)
+  uint32_t bits = 0;
+#pragma unroll
+  for (int s = 0; s < H; ++s) {  // step s * LH + q
+    if (s * LH * NG < n) {       // (wave-uniform: else no lane's step s * LH + q has an edge)
+      if constexpr (IDS) {
+        const int ei = e0 + s * LH * NG;
+        z = u01_key(seed, (uint64_t)ids[eb + (ei < n ? ei : 0)] * (uint64_t)H + (uint64_t)head);
+      }
+      bits |= (u01_of_key(z) > rate ? 1u : 0u) << (s * LH + q);
+      if constexpr (!IDS) z += U01_GOLD * (uint64_t)(LH * NG * H);
+    }
+  }
+  return lanes_or<LH>(bits);
+}
+
+// DROP (gat_drop.hip; RECOMP form): attention dropout inside the sweep, see gat_drop_bits; rev is then read for the reverse edges' masks.
+// The three trailing arguments are the DROP form's; the others' launches leave them to their defaults.
+template <int G, int H, int U, bool RECOMP, typename E, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
     const int64_t* rowptr, const uint32_t* col, const uint32_t* rev, int len, const E* feat, const E* grad,
     const float* p, const float2* stats, const float* rowdot, const float* alpha_l, const float* alpha_r, float eps,
-    float* out_partial, float* rc_partial, const f4* rec, int phase, uint32_t own_cols, int ld, int rec_ld, int per_xcd) {
+    float* out_partial, float* rc_partial, const f4* rec, int phase, uint32_t own_cols, int ld, int rec_ld, int per_xcd,
+    float drop_rate = 0.0f, float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   // rec (RECOMP): (rowdot, row maximum, 1 / row sum) per (vertex, head) as one 16-byte record, see gat_rec_kernel
   // ld / rec_ld: row strides of the feat / grad tables (floats) and of the record table (16-byte records): len and H for
   // three separate tables; 2 len + 4 H and that / 4 when the three live INTERLEAVED, one [h | grad | records] row per vertex
@@ -265,6 +302,12 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
   if constexpr (!RECOMP) {
     rl = rev[el];
     if constexpr (G == 32) rl1 = rev[el1];
+  }
+  // DROP: the masks of the chunk's edges (-> dp_e) and of their reverse edges (-> dp_r, the weight of grad_c), one bit per step
+  uint32_t mb_e = 0, mb_r = 0;
+  if constexpr (DROP) {
+    mb_e = gat_drop_bits<G, H, false>(lane, n, eb, nullptr, drop_seed, drop_rate);
+    mb_r = gat_drop_bits<G, H, true>(lane, n, eb, rev, drop_seed, drop_rate);
   }
   const int coff = sl * 4;  // len == 4 * G
   const int head = sl / LH;
@@ -323,8 +366,14 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
     for (int u = 0; u < U; ++u) {
       const bool live = CL::step_edge(lane, j + u) < n;
       const f4 xg = R4::widen(xg_raw[u]), xh = R4::widen(xh_raw[u]);
-      const float dpe = lanes_sum_w<LH>(d4(gi, xh));
-      const float dpr = lanes_sum_w<LH>(d4(xg, hi));
+      float dpe = lanes_sum_w<LH>(d4(gi, xh));
+      float dpr = lanes_sum_w<LH>(d4(xg, hi));
+      float w_r = 1.0f;
+      if constexpr (DROP) {  // d(out_i)/d(p_e) = w_e <grad_i, h_c>; the same through the reverse edge's mask on the column side
+        dpe *= ((mb_e >> (j + u)) & 1u) ? drop_scale : 0.0f;
+        w_r = ((mb_r >> (j + u)) & 1u) ? drop_scale : 0.0f;
+        dpr *= w_r;
+      }
       const float sl_c = lanes_sum_w<LH>(d4(al4, xh));
       const float sr_c = lanes_sum_w<LH>(d4(ar4, xh));
       const float t_e = sl_i + sr_c, t_r = sl_c + sr_i;  // pre-activation scores of (i -> c) and (c -> i)
@@ -343,8 +392,14 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
       if (live) {  // (lanes past the end of a short chunk looked at the chunk's first edge: nothing of it is added)
         s_e += ge;
         s_r += gr;
+        if constexpr (DROP) {  // the gradient flows back along the DROPPED attention p_r w_r
+          const float bw = b * w_r;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(b, xg[k], acc[k]);
+          for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(bw, xg[k], acc[k]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(b, xg[k], acc[k]);
+        }
       }
     }
   }
@@ -616,11 +671,14 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_pk_kernel(int64_t n_chunks,
 // written: backward forms p again from stats[v][h] = (M, 1/S) (gat_bwd_fused_chunk_kernel<RECOMP>).
 constexpr float GAT_NEG = -1.0e30f;  // "no edge yet": finite, so exp(NEG - m) = 0 and NEG - NEG = 0 (not NaN)
 
-template <int G, int H, int U, typename E>
+// DROP (gat_drop.hip): out_i = sum_e p_e w_e h_c with w = mask . scale (gat_drop_bits); (m, ssum) and so the row statistics are the
+// undropped softmax's.  The three trailing arguments are the DROP form's.
+template <int G, int H, int U, typename E, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
     const int64_t* rowptr, const uint32_t* col, int len, const E* feat, const float* alpha_l, const float* alpha_r,
-    float eps, float* out_partial, float2* ms_partial, int phase, uint32_t own_cols, int per_xcd) {
+    float eps, float* out_partial, float2* ms_partial, int phase, uint32_t own_cols, int per_xcd, float drop_rate = 0.0f,
+    float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   constexpr int LH = G / H;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -652,6 +710,8 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
     return __builtin_fmaf(a[3], b[3], __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])));
   };
   const float sl_i = lanes_sum_w<LH>(d4(al4, hi));  // (DPP sums / broadcasts, FMA chains: see the backward kernel)
+  uint32_t mb = 0;  // DROP: the masks of the chunk's edges, one bit per step (gat_drop_bits)
+  if constexpr (DROP) mb = gat_drop_bits<G, H, false>(lane, n, eb, nullptr, drop_seed, drop_rate);
   float m = GAT_NEG, ssum = 0.f;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -676,8 +736,14 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
         const float ex = __expf(d > 0.f ? -d : d);
         const float sc = d > 0.f ? ex : 1.f, e = d > 0.f ? 1.f : ex;
         ssum = __builtin_fmaf(ssum, sc, e);
+        if constexpr (DROP) {  // the softmax (m, ssum) does not see the mask; the aggregated term does
+          const float ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(e, xh[k], acc[k] * sc);
+          for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(ew, xh[k], acc[k] * sc);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(e, xh[k], acc[k] * sc);
+        }
         m = d > 0.f ? t : m;
       }
     }

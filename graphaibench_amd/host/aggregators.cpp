@@ -126,6 +126,7 @@ struct ZsWatch {
 };
 static struct {
   gaib_ctx* ctx = nullptr;
+  unsigned gen = 0;  // gpu_context::generation() of ctx
   void* tab = nullptr;  // [cap_bytes]: rows x 384 B, or 2 x rows x 384 B for a table of 256 columns
   size_t cap_bytes = 0;
   uint32_t* d_over = nullptr;           // [ZS_SLOTS] the packs' counts of over-capacity rows ...
@@ -134,13 +135,20 @@ static struct {
   int n_watch = 0, next_evict = 0;
   std::vector<void*> retired;  // (a recorded epoch may still name a buffer that had to grow)
 } g_zs;
+// a new process context (gpu_context::set) -- told by its generation: it may sit at the address of the one it replaced, and the
+// watch list of the old one (a table that was left paused and has since been freed) would keep "agg_zs_paused" at 1 for good
+static bool zs_other_context() { return g_zs.ctx != C() || g_zs.gen != gpu_context::generation(); }
 static void* zs_table(size_t bytes) {
-  if (g_zs.ctx != C()) {  // a new process context: start over on its device (the old context's buffers went with it)
+  if (zs_other_context()) {  // start over on its device; no recorded sequence of the old context is alive (gaib_ctx_destroy)
     if (g_zs.h_over) GAIB_OR_DIE(gaib_host_free(C(), const_cast<uint32_t*>(g_zs.h_over)));
+    if (g_zs.d_over) GAIB_OR_DIE(gaib_free(C(), g_zs.d_over));
+    if (g_zs.tab) GAIB_OR_DIE(gaib_free(C(), g_zs.tab));
+    for (void* p : g_zs.retired) GAIB_OR_DIE(gaib_free(C(), p));
     g_zs.retired.clear();
     g_zs.tab = nullptr;
     g_zs.cap_bytes = 0;
     g_zs.ctx = C();
+    g_zs.gen = gpu_context::generation();
     g_zs.n_watch = g_zs.next_evict = 0;
     GAIB_OR_DIE(gaib_malloc(C(), sizeof(uint32_t) * ZS_SLOTS, (void**)&g_zs.d_over));
     void* h = nullptr;
@@ -449,7 +457,7 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     const size_t tab_bytes = rows * (size_t)(len / 128) * 384;
     int64_t capturing = 0;
     GAIB_OR_DIE(gaib_get_option(C(), "capturing", &capturing));
-    if (g_zs.ctx != C()) zs_table(0);
+    if (zs_other_context()) zs_table(0);
     // is there a packed route for this call?  Asked from the route information alone, before anything is packed or allocated (a
     // graph of short rows, a numbering with locality, a dense graph the ordered chunks take, a table of 4 GB: the dense call's
     // variants).  The query reads nothing through the image pointer: any 128-B aligned address stands for it.
@@ -571,7 +579,7 @@ void GAT_Aggregator::init(int l, int nv, int ne, float lr, float drop_rate) {
 
 // d_norm_scores (the softmax of this forward) -> p . mask . scale in a buffer of its own: backward needs both the
 // undropped attention (softmax backward) and the dropped one (d_dropout of dp, transposed aggregation)
-const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores) {
+const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores, uint64_t seed) {
   if (n_scores > drop_cap) {
     if (d_norm_scores_drop) float_free_device(d_norm_scores_drop);
     if (d_attn_masks) GAIB_OR_DIE(gaib_free(C(), d_attn_masks));
@@ -580,7 +588,7 @@ const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores) {
     drop_cap = n_scores;
   }
   OpTimer t(OP_DROPOUT);
-  GAIB_OR_DIE(gaib_dropout(C(), (int64_t)n_scores, attn_scale, attn_drop, drop_seed++, d_norm_scores, d_attn_masks,
+  GAIB_OR_DIE(gaib_dropout(C(), (int64_t)n_scores, attn_scale, attn_drop, seed, d_norm_scores, d_attn_masks,
                            d_norm_scores_drop));
   dropped_last = true;
   return d_norm_scores_drop;
@@ -602,7 +610,7 @@ void GAT_Aggregator::release() {
   hb16_elems = 0;
   fwd_bf16 = false;
   drop_cap = tbuf_floats = ptab_floats = pvec_floats = pgrad_floats = prec_floats = stats_floats = 0;
-  stats_valid = part_fused_last = dropped_last = false;
+  stats_valid = part_fused_last = dropped_last = drop_fused_last = false;
   last_graph = NULL;
   last_in = fwd_out = NULL;
   if (alpha_opt) {
@@ -661,6 +669,7 @@ void GAT_Aggregator::aggregate_partition(int len, Graph& g, const float* in, flo
   const size_t n_own = g.size(), n_halo = g.gat_n_halo();
   ensure_partition_buffers(g, len);
   dropped_last = false;
+  drop_fused_last = false;
   part_fused_last = false;
   // One sweep (gaib_gat_forward_fused_rect) where the shape allows: the chunks over owned columns run while the halo rows
   // of h are on the wire (phase 0), the rest and the per-row combination after they have arrived (phase 1); only the row
@@ -694,7 +703,7 @@ void GAT_Aggregator::aggregate_partition(int len, Graph& g, const float* in, flo
     GAIB_OR_DIE(gaib_gat_scores_mh(C(), g.gat_full_graph(), len, heads, d_ptab, d_alpha_l, d_alpha_r, epsilon,
                                    d_temp_scores, NULL, d_norm_scores));
   }
-  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads) : d_norm_scores;
+  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads, drop_seed++) : d_norm_scores;
   OpTimer t(OP_SPARSEMM);
   GAIB_OR_DIE(gaib_spmm_mh(C(), g.gat_full_graph(), GAIB_W_EDGE, attn, heads, len, d_ptab, out,
                            fuse_relu ? GAIB_RELU : 0));
@@ -775,6 +784,11 @@ void GAT_Aggregator::d_aggregate_partition(int len, Graph& g, const float* grad_
   GAIB_OR_DIE(gaib_halo_reduce(g.halo_plan(), len, d_pout + n_own * len, grad_out));
 }
 
+bool GAT_Aggregator::gat_fused_drop_option() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "gat_fused_drop", &v));
+  return v != 0;
+}
 bool GAT_Aggregator::gat_bf16_tables() {
   int64_t v = 0;
   GAIB_OR_DIE(gaib_get_option(C(), "gat_bf16", &v));
@@ -802,13 +816,35 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   // 1 / sum) are kept and backward forms the attention again -- no [ne][heads] array is written or read.  norm_scores_ptr()
   // materialises the attention on demand (tests, checkpoints).
   dropped_last = false;
-  if (!dropping()) {
+  drop_fused_last = false;
+  const bool drop_sweep = dropping() && gat_fused_drop_option();
+  if (!dropping() || drop_sweep) {
     const size_t need = (size_t)g.size() * heads * 2;
     if (need > stats_floats) {
       if (d_row_stats) float_free_device(d_row_stats);
       float_malloc_device64(need, d_row_stats);
       stats_floats = need;
     }
+  }
+  if (drop_sweep) {
+    // attention dropout inside the sweep (option gat_fused_drop): the masks of the staged path's next seed, no edge array
+    OpTimer t(OP_SPARSEMM);
+    const int rc = gaib_gat_forward_fused_drop(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0,
+                                               attn_drop, attn_scale, drop_seed, out, d_row_stats);
+    if (rc == GAIB_OK) {
+      drop_seed_last = drop_seed++;
+      drop_fused_last = drop_sweep_ran = true;
+      fuse_relu = false;
+      fwd_bf16 = false;
+      stats_valid = true;  // (the statistics are the undropped softmax's: materialise_scores() serves them as ever)
+      last_graph = &g;
+      last_in = in;
+      last_len = len;
+      return;
+    }
+    if (rc != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(rc);  // UNSUPPORTED: the staged path draws this seed itself
+  }
+  if (!dropping()) {
     OpTimer t(OP_SPARSEMM);
     fwd_bf16 = false;
     int rc = GAIB_ERR_UNSUPPORTED;
@@ -859,7 +895,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     GAIB_OR_DIE(gaib_gat_scores_mh(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, d_temp_scores,
                                    NULL, d_norm_scores));
   }
-  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads) : d_norm_scores;
+  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads, drop_seed++) : d_norm_scores;
   OpTimer t(OP_SPARSEMM);
   GAIB_OR_DIE(gaib_spmm_mh(C(), dev(g), GAIB_W_EDGE, attn, heads, len, in, out, fuse_relu ? GAIB_RELU : 0));
   fuse_relu = false;
@@ -874,6 +910,33 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
   if (g.gat_full_graph()) {
     d_aggregate_partition(len, g, grad_in, grad_out);
     return;
+  }
+  if (drop_fused_last) {
+    // forward dropped inside the sweep: backward through the same masks, formed again from the kept seed
+    drop_fused_last = false;
+    int rc = GAIB_ERR_UNSUPPORTED;
+    if (fwd_out && stats_valid && feat_in == last_in && &g == last_graph && len == last_len) {
+      OpTimer t(OP_ATTN);
+      const size_t need = (size_t)g.size() * len;
+      if (need > tbuf_floats) {
+        if (d_tbuf) float_free_device(d_tbuf);
+        float_malloc_device64(need, d_tbuf);
+        tbuf_floats = need;
+      }
+      rc = gaib_gat_backward_fused_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
+                                        epsilon, attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad, d_alpha_rgrad);
+      if (rc == GAIB_OK) {
+        fwd_out = NULL;
+        fwd_out_given = false;
+        GAIB_OR_DIE(gaib_memcpy_d2d(C(), grad_out, d_tbuf, sizeof(float) * need));
+        return;
+      }
+      if (rc != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(rc);
+    }
+    // the sweep may not run (gat_fused_bwd = 0, no forward output): the attention array, then mask and dropped attention drawn
+    // again under the kept seed -- the bits the forward sweep used -- and the staged pieces below
+    materialise_scores();
+    apply_attn_dropout((size_t)g.sizeEdges() * heads, drop_seed_last);
   }
   if (fwd_out && !dropped_last) {
     // one sweep over the edges instead of four (gaib_gat_backward_fused): needs the layer's forward output and an

@@ -10,6 +10,8 @@ std::map<char, double> time_ops;  // declared extern in include/gnn/global.h (re
 static gaib_ctx* g_ctx = nullptr;
 static bool g_sync_timers = false;
 static gaib_comm* g_comm = nullptr;
+static unsigned g_generation = 0;
+unsigned gpu_context::generation() { return g_generation; }
 
 static unsigned long long g_agg_edges = 0;
 void gpu_context::add_aggregated_edges(unsigned long long n) { g_agg_edges += n; }
@@ -36,6 +38,7 @@ void gpu_context::set(int device, void* hip_stream) {
     g_ctx = nullptr;
   }
   check(gaib_ctx_create(device, hip_stream, &g_ctx), "gaib_ctx_create");
+  g_generation++;
   const char* s = getenv("GAIB_SYNC_TIMERS");
   g_sync_timers = s && atoi(s) != 0;
   // development knobs for A/B runs of the drivers: GAIB_OPTS="key=value,key=value" -> gaib_set_option
@@ -92,6 +95,16 @@ void gpu_context::set(int device, void* hip_stream) {
       exit(EXIT_FAILURE);
     }
     check(gaib_set_option(g_ctx, "sampler_device", v), "gaib_set_option (GAIB_SAMPLER_DEVICE)");
+  }
+  // GAT with attention dropout (score_drop > 0): mask, forward and backward inside the one-sweep kernels (option gat_fused_drop;
+  // off by default)
+  if (const char* d = getenv("GAIB_GAT_FUSED_DROP")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GAT_FUSED_DROP=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gat_fused_drop", v), "gaib_set_option (GAIB_GAT_FUSED_DROP)");
   }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {

@@ -707,7 +707,23 @@ struct Trainer {
     const bool exact_losses = getenv("GAIB_EPOCH_LOSSES") && atoi(getenv("GAIB_EPOCH_LOSSES")) != 0;
     std::vector<double> all_loss, all_acc;
     std::vector<double> subgraph_s;  // (GAIB_EPOCH_TIMES with sampling) seconds per epoch in subgraph_sampling
+    // score_drop > 0 on GAT: which path the layers' training forwards of epoch 0 TOOK (asked of the aggregators, not predicted:
+    // GAIB_GAT_FUSED_DROP=1 keeps a layer in the one-sweep kernels only where they cover its shape and graph), printed once
+    bool drop_path_said = !(ARCH == gnn_arch::GAT && score_drop > 0.f && root());
+    auto say_drop_path = [&]() {
+      if (drop_path_said) return;
+      drop_path_said = true;
+#if defined(USE_GAT)
+      size_t swept = 0;
+      for (auto& l : layers) swept += l.get_aggregator().dropped_in_sweep() ? 1 : 0;
+      std::cout << "GAT attention dropout: ";
+      if (swept == layers.size()) std::cout << "one sweep\n";
+      else if (swept == 0) std::cout << "staged\n";
+      else std::cout << "one sweep in " << swept << " of " << layers.size() << " layers, staged in the others\n";
+#endif
+    };
     for (int itr = 0; itr < num_epochs; itr++) {
+      if (itr == 1) say_drop_path();
       if (itr == prof_from) {
         GAIB_OR_DIE(gaib_prof_reset(gpu_context::get()));
         GAIB_OR_DIE(gaib_prof_enable(gpu_context::get(), 1));
@@ -822,6 +838,7 @@ struct Trainer {
       }
       GAIB_OR_DIE(gaib_prof_reset(c));
     }
+    say_drop_path();  // (a run of one epoch)
     std::cout << "Average training time per epoch: " << total / (double)num_epochs << " seconds. Throughput "
               << (double)num_epochs / total << " epoch/s\n";
     // added by this backend: the hot path's own metric (edges of the graph x aggregation calls of a steady-state

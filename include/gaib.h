@@ -378,6 +378,28 @@ int gaib_gat_backward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int head
                                  const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_alpha_l,
                                  const float* d_alpha_r, const float* d_row_stats, float epsilon, float* d_grad_out,
                                  float* d_alpha_lgrad, float* d_alpha_rgrad);
+/* The one-sweep forward and backward under ATTENTION DROPOUT (layer-library option "gat_fused_drop"), fp32 tables.
+ * The weight of (edge e, head k) is w = mask * scale with mask = u01(seed, e * heads + k) > drop_rate: EXACTLY the mask
+ * gaib_dropout(n = ne * heads, scale, drop_rate, seed, ..) draws for element e * heads + k of an [ne][heads] array (e = the
+ * edge's position in the graph's CSR), formed inside the sweep -- no [ne][heads] array exists on this path either.
+ * Forward: d_out = act(sum_e p_e w_e h_c).  The softmax does not see the mask: d_row_stats are the bits gaib_gat_forward_fused
+ * writes.  Backward (row-statistics form only): dp_e = w_e <grad_i, h_c>, and through the reverse edge r = rev(e) dp_r =
+ * w_r <grad_c, h_i> and d_grad_out_i = sum_e p_r w_r grad_c; d_fwd_out is the DROPPED forward output (sum_e p_e dp_e of a row is
+ * still <grad_i, out_i>).  With drop_rate = 0 and scale = 1 every output has the bits of the undropped calls.
+ * Cover and refusals are those of gaib_gat_forward_fused / gaib_gat_backward_fused: len 32 / 64 / 128 with 1, 2, 4, 8 or 16 heads
+ * of >= 4 columns, 16-byte aligned buffers, options "gat_fused_fwd" / "gat_fused_bwd" = 0 -> GAIB_ERR_UNSUPPORTED with nothing
+ * touched; "gat_fused_unroll" and "gat_chunk_xcd" are honoured as there (same bits); "gat_bwd_pk" and "gat_interleave" are
+ * ignored; a graph without rows: forward GAIB_ERR_UNSUPPORTED, backward zero alpha gradients and GAIB_OK.  Further: a rectangular
+ * graph -> GAIB_ERR_UNSUPPORTED (a rank cannot name the reverse edge's index on another rank); a graph whose reverse-edge
+ * permutation cannot be built -> that error, from forward and backward alike; drop_rate outside [0, 1) and d_row_stats == NULL
+ * in backward -> GAIB_ERR_INVALID.  Profile keys and byte formulas: "gat_fwd_fused" / "gat_bwd_fused" of the undropped calls. */
+int gaib_gat_forward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
+                                const float* d_alpha_r, float epsilon, int relu, float drop_rate, float scale, uint64_t seed,
+                                float* d_out, float* d_row_stats);
+int gaib_gat_backward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
+                                 const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
+                                 const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
+                                 float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
 /* Test / diagnostic: d_sign_out [ne][heads] (uint8) = (t_e > 0) of every pre-activation score a_l.h[i] + a_r.h[col_e]
  * EXACTLY as the one-sweep kernels form it.  leaky_relu' jumps at 0, so a score within rounding of zero takes either
  * slope in two correct fp32 evaluations; a comparison of the alpha gradients with an fp64 evaluation imposes these signs
@@ -855,6 +877,10 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
  * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs, no
  * attention dropout); a partitioned GAT graph refuses the option;
+ * "gat_fused_drop" (default 0; readable): 1 = the layer library's GAT aggregation, on a whole graph in the training phase with
+ * attention dropout, runs gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop instead of the staged kernels and holds
+ * neither the mask nor the dropped-attention array; the masks are those of the staged path, seed for seed; partitioned graphs
+ * stay staged and bf16 tables ("gat_bf16") are not used under dropout;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
@@ -866,7 +892,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sampler_device" */
+ * "sampler_device", "gat_fused_drop" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -120,6 +120,7 @@ class GAT_Aggregator : public aggregator {
   float* norm_scores_grad_ptr() { return d_norm_scores_grad; }
   float* norm_scores_dropped_ptr() { return d_norm_scores_drop; }  // NULL unless a training forward dropped attention
   mask_t* attn_masks_ptr() { return d_attn_masks; }
+  bool dropped_in_sweep() const { return drop_sweep_ran; }  // a training forward of this layer dropped inside the one sweep
 
  private:
   // the temp_scores array is kept where re-forming the score is not a gain: 1 or 2 heads (measured on the
@@ -138,7 +139,8 @@ class GAT_Aggregator : public aggregator {
   size_t drop_cap;
   uint64_t drop_seed;
   bool dropping() const { return attn_drop > 0.f && training; }
-  const float* apply_attn_dropout(size_t n_scores);  // d_norm_scores -> d_norm_scores_drop (+ masks); returns the latter
+  // d_norm_scores -> d_norm_scores_drop (+ masks) under `seed`; returns the latter
+  const float* apply_attn_dropout(size_t n_scores, uint64_t seed);
   size_t num_edges;
   int heads;
   float *d_alpha_l, *d_alpha_r, *d_alpha_lgrad, *d_alpha_rgrad;
@@ -179,5 +181,17 @@ class GAT_Aggregator : public aggregator {
   uint16_t* d_hb16 = NULL;
   size_t hb16_elems = 0;
   bool fwd_bf16 = false;  // the last forward ran on d_hb16 = bf16(last_in) over last_graph
+  // extension: attention dropout inside the one sweep (context option "gat_fused_drop" = 1, or GAIB_GAT_FUSED_DROP=1).  On a
+  // whole graph, in the training phase with attn_drop > 0, aggregate() runs gaib_gat_forward_fused_drop under seed = drop_seed++
+  // -- the seed the staged path would have drawn, so both paths train through the same masks -- and keeps the row statistics
+  // and that seed; neither d_norm_scores_drop nor d_attn_masks is allocated.  d_aggregate() runs gaib_gat_backward_fused_drop
+  // under the kept seed when the layer's forward output is at hand and feat_in, graph and len are that forward's.  Where it
+  // may not (gat_fused_bwd = 0, no forward output), the attention is materialised, mask and dropped attention are drawn AGAIN
+  // with gaib_dropout under the kept seed -- the bits the sweep used -- and the staged pieces run.  Partitioned graphs stay
+  // staged; bf16 tables (gat_bf16) are not used under dropout, with or without this option.
+  static bool gat_fused_drop_option();
+  bool drop_fused_last = false;  // the last forward was the dropped one sweep under drop_seed_last
+  uint64_t drop_seed_last = 0;
+  bool drop_sweep_ran = false;   // ... at least once (the trainer reports it)
   optimizer* alpha_opt;
 };

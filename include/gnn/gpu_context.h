@@ -11,6 +11,7 @@ class gpu_context {
   static gaib_ctx* get();                        // lazily created
   static void set(int device, void* hip_stream); // explicit (multi-GPU launchers, tests)
   static void sync();                            // CudaTest() equivalent
+  static unsigned generation();                  // counts set(): a new context may sit at the address of the one it replaced
   static int parse_switch(const char* value);    // "0" -> 0, "1" -> 1, anything else -> -1 (GAIB_SAMPLER_DEVICE, ...)
   // side stream for independent work (gaib_side_begin/end/wait); no-ops unless GAIB_OVERLAP=1.  The layer classes
   // do not use it (measured: no gain next to an HBM-saturating aggregation); kept for drivers
