@@ -287,6 +287,7 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   a.in2 = d_in2;
   a.n_first = d_in2 ? (uint32_t)n_first : 0xffffffffu;
   a.in2_bytes = 0;
+  a.col0 = 0;
   if (!part && !bf16 && ctx->spmm_gather_mode == 3 && g->nc == g->nv && !g->col_vdata) {
     GAIB_TRY(gaib_graph_ensure_hot_flags(ctx, g, len));
     a.col_flagged = g->colidx_flagged;

@@ -32,6 +32,8 @@ struct SpmmArgs {
   int heads;                 // WMODE 3/4: edge weights are [ne][heads]; head of a column = col / dh
   int dh;
   int compact;               // heavy kernel: row k of row_list is written to out row k (fused path's scratch)
+  int col0;                  // WMODE 3/4: column of the whole row at which in / out start (a column slab of dispatch_vec; else 0)
+                             // (in what was padding ahead of row_map: no other field moves, the struct keeps its size)
   // PART kernels (row classes of a vertex-range partition, spmm_part.hip) -- ignored by the others:
   const uint32_t* row_map;   // row r of the graph is row row_map[r] of out / the continued partial sums / rows2 / y (NULL: r itself)
   const float* in2;          // column ids >= n_first index this second table (row id - n_first): the halo table behind the
@@ -389,7 +391,12 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
   int hd[CT];
   float wv[MH ? U : 1][CT];
 #pragma unroll
-  for (int ct = 0; ct < CT; ++ct) hd[ct] = MH ? (int)((voff[ct] >> 2) / (uint32_t)a.dh) : 0;
+  for (int ct = 0; ct < CT; ++ct) {
+    // the head of the lane's column IN THE WHOLE ROW: voff counts from the launch's first column, a.col0 (lanes outside
+    // the row sit at offset 0, whose head col0 / dh is a valid one)
+    if constexpr (MH) hd[ct] = (int)(((uint32_t)a.col0 + (voff[ct] >> 2)) / (uint32_t)a.dh);
+    else hd[ct] = 0;
+  }
   for (int64_t base = eb; base < ee; base += chunk_stride) {
     const int64_t rem = ee - base;
     const int n = rem < 64 ? (int)rem : 64;  // wave-uniform

@@ -306,6 +306,8 @@ int dispatch_vec(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a0, int len
     SpmmArgs a = a0;
     a.in = a0.in + c0;
     a.out = a0.out + c0;
+    a.col0 = c0;  // per-head weights: a slab's lanes find their head from the column in the whole row (cuts fall inside heads)
+    if (a.in_bytes) a.in_bytes -= (uint32_t)(c0 * 4);
     a.ncols = (len - c0 < slab) ? (len - c0) : slab;
     const int lanes = (a.ncols + vec - 1) / vec;
     int rc;

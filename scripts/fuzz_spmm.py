@@ -1,9 +1,16 @@
-"""Randomised sweep of gaib_spmm (every weight kind, multi-head weights, accumulate / relu flags, widths 1..300,
-tiny heavy thresholds) against an fp64 index_add formulation (development aid, GPU box).
+"""Randomised sweep of gaib_spmm (every weight kind, multi-head weights, accumulate / relu flags, widths 1..1028 -- the
+column slabs of rows wider than one launch included --, tiny heavy thresholds) against an fp64 index_add formulation
+(development aid, GPU box).
 
     python scripts/fuzz_spmm.py [n_cases] [seed]
+    python scripts/fuzz_spmm.py --seconds S --seed N
+
+Ends with one JSON line {"cases": .., "failures": .., "seconds": .., "seed": ..}; exit status 1 if a case failed.
 """
+import argparse
+import json
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -14,29 +21,33 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
 from graphaibench_amd import capi  # noqa: E402
 from util import random_graph  # noqa: E402
 
+DEFAULTS = {"spmm_heavy_threshold": 1024, "spmm_chunked": -1, "spmm_pad": 1}
 
-def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-    ctx = capi.Context(0)
-    worst = 0.0
-    for case in range(n_cases):
-        nv = int(rng.choice([2, 5, 64, 65, 1000, int(rng.integers(2, 8000))]))
-        rp, ci = random_graph(nv, float(rng.choice([1, 6, 25])), seed=int(rng.integers(1 << 30)), power_law=bool(rng.integers(2)),
-                              hub_deg=int(rng.choice([0, min(nv - 1, 2000)])) if nv > 2100 else 0)
-        nv = len(rp) - 1
-        ctx.set_option("spmm_heavy_threshold", int(rng.choice([1024, 1024, 32, 1])))
-        ctx.set_option("spmm_chunked", int(rng.choice([-1, 0, 1])))  # ordered-chunk path where the shape allows
-        ctx.set_option("spmm_pad", int(rng.choice([0, 1])))
-        kind = int(rng.choice([capi.W_GCN, capi.W_MEAN, capi.W_MEAN_T, capi.W_EDGE, capi.W_EDGE_T]))
-        heads = int(rng.choice([1, 1, 2, 4, 8])) if kind in (capi.W_EDGE, capi.W_EDGE_T) else 1
-        dh = int(rng.choice([1, 3, 4, 8, 16, 25, 32]))
-        D = heads * dh if heads > 1 else int(rng.choice([1, 2, 3, 7, 16, 31, 47, 64, 65, 100, 128, 129, 200, 256, 300]))
-        accumulate, relu = bool(rng.integers(2)), bool(rng.integers(2))
-        g = ctx.graph(rp, ci.view(np.int32))
+
+def one_case(ctx, rng, cfg):
+    kind = int(rng.choice([capi.W_GCN, capi.W_MEAN, capi.W_MEAN_T, capi.W_EDGE, capi.W_EDGE_T]))
+    heads = int(rng.choice([1, 1, 2, 4, 8])) if kind in (capi.W_EDGE, capi.W_EDGE_T) else 1
+    dh = int(rng.choice([1, 3, 4, 8, 16, 25, 32, 65, 128, 129]))
+    # (above 256 columns at 4-byte lanes, 512 at wider ones, a row is aggregated in column slabs)
+    D = heads * dh if heads > 1 else int(rng.choice([1, 2, 3, 7, 16, 31, 47, 64, 65, 100, 128, 129, 200, 256, 300,
+                                                     257, 513, 520, 602, 1028]))
+    nv = int(rng.choice([2, 5, 64, 65, 1000, int(rng.integers(2, 8000))]))
+    nv = max(2, min(nv, (1 << 19) // D))  # a feature table of 2 MB at the most
+    rp, ci = random_graph(nv, float(rng.choice([1, 6, 25])), seed=int(rng.integers(1 << 30)), power_law=bool(rng.integers(2)),
+                          hub_deg=int(rng.choice([0, min(nv - 1, 2000)])) if nv > 2100 else 0)
+    nv = len(rp) - 1
+    opts = {"spmm_heavy_threshold": int(rng.choice([1024, 1024, 32, 1])),
+            "spmm_chunked": int(rng.choice([-1, 0, 1])),  # ordered-chunk path where the shape allows
+            "spmm_pad": int(rng.choice([0, 1]))}
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    accumulate, relu = bool(rng.integers(2)), bool(rng.integers(2))
+    g = ctx.graph(rp, ci.view(np.int32))
+    try:
         if kind == capi.W_GCN:
             g = g.add_selfloop()
         ne = g.ne
+        cfg.update(nv=nv, ne=ne, kind=kind, heads=heads, D=D, accumulate=accumulate, relu=relu, opts=opts)
         rowptr, col = g.rowptr().long(), g.colidx().long()
         deg = (rowptr[1:] - rowptr[:-1]).double()
         rows = torch.repeat_interleave(torch.arange(nv, device="cuda"), rowptr[1:] - rowptr[:-1])
@@ -67,16 +78,41 @@ def main():
                  relu=relu, heads=heads)
         ctx.sync()
         err = (out.double() - want).abs().max().item() / max(want.abs().max().item(), 1e-6)
-        worst = max(worst, err)
         if not err < 2e-5:
-            print(f"FAIL case {case}: nv={nv} ne={ne} kind={kind} heads={heads} D={D} acc={accumulate} relu={relu} err={err:.2e}")
-            sys.exit(1)
+            raise AssertionError(f"relative error {err:.2e}")
+        return err
+    finally:
         g.close()
-    ctx.set_option("spmm_heavy_threshold", 1024)
-    ctx.set_option("spmm_chunked", -1)
-    ctx.set_option("spmm_pad", 1)
-    print(f"{n_cases} cases ok, worst relative error {worst:.2e}")
+        for k, v in DEFAULTS.items():
+            ctx.set_option(k, v)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n_cases", nargs="?", type=int, default=200)
+    ap.add_argument("seed_pos", nargs="?", type=int, default=None, metavar="seed")
+    ap.add_argument("--seconds", type=float, default=None, help="run for this long instead of n_cases cases")
+    ap.add_argument("--seed", type=int, default=None)
+    args = ap.parse_args()
+    seed = args.seed if args.seed is not None else (args.seed_pos if args.seed_pos is not None else 0)
+    rng = np.random.default_rng(seed)
+    ctx = capi.Context(0)
+    t0, n_cases, fails, worst = time.time(), 0, [], 0.0
+    while (time.time() - t0 < args.seconds) if args.seconds is not None else (n_cases < args.n_cases):
+        cfg = {"case": n_cases}
+        try:
+            worst = max(worst, one_case(ctx, rng, cfg))
+        except Exception as e:  # noqa: BLE001
+            fails.append(dict(cfg, error=f"{type(e).__name__}: {e}"[:300]))
+            print("FAIL", json.dumps(fails[-1]), flush=True)
+            if isinstance(e, capi.GaibError):  # a refused call or a device error: nothing more is started on the device
+                n_cases += 1
+                break
+        n_cases += 1
+    print(f"{n_cases} cases, {len(fails)} failures, worst relative error {worst:.2e}")
+    print(json.dumps({"cases": n_cases, "failures": len(fails), "seconds": round(time.time() - t0, 1), "seed": seed}))
+    return 1 if fails else 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
