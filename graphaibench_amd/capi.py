@@ -110,6 +110,7 @@ SIGNATURES = {
     "gaib_gat_alpha_grads": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gaib_gat_backward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "gaib_gat_fused_slabs": (_i, [_i, _i, C.POINTER(C.c_int)]),
     "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
@@ -352,6 +353,14 @@ def probe_peer_copy(src_dev: int, dst_dev: int, nbytes: int = 1 << 28, iters: in
     v = C.c_double(0.0)
     _check(load().gaib_probe_peer_copy(src_dev, dst_dev, nbytes, iters, int(bidir), C.byref(v)), "gaib_probe_peer_copy")
     return v.value
+
+
+def gat_fused_slabs(length: int, heads: int) -> tuple[int, int]:
+    """(w, S): the one-sweep GAT kernels run a row of `length` columns and `heads` heads as S column slabs of w columns and
+    heads / S heads each -- S = 1: the narrow shapes, S >= 2: with context option gat_fused_wide = 1, S = 0 (w = 0): staged"""
+    w = C.c_int(0)
+    S = load().gaib_gat_fused_slabs(length, heads, C.byref(w))
+    return w.value, S
 
 
 _lib = None

@@ -1048,6 +1048,14 @@ static int gat_forward_fused_impl(gaib_ctx* ctx, gaib_graph* g, int len, int hea
   GAIB_CHECK(d_h && d_alpha_l && d_alpha_r && d_out && d_row_stats && d_out != d_h, "%s: NULL or aliased pointer", who);
   GAIB_CHECK(phase >= -1 && phase <= 1, "%s: phase is -1, 0 or 1", who);
   GAIB_HIP(hipSetDevice(ctx->device));
+  // option gat_fused_wide: a multi-head row wider than 128 columns as S column slabs of a width the kernels cover (gat_wide.hip);
+  // whole graphs only -- the _rect calls keep today's answer
+  if (!rect && ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_forward_fused_wide(ctx, g, len, heads, w, S, d_h, d_alpha_l, d_alpha_r, epsilon, relu, d_out, d_row_stats);
+  }
   int rc = GAIB_OK;
   const bool use = gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_fwd,
                                      (uintptr_t)d_h | (uintptr_t)d_out | (uintptr_t)d_row_stats | (uintptr_t)d_alpha_l |
@@ -1123,6 +1131,14 @@ extern "C" int gaib_gat_backward_fused(gaib_ctx* ctx, gaib_graph* g, int len, in
                  d_alpha_lgrad && d_alpha_rgrad, "gaib_gat_backward_fused: NULL pointer");
   GAIB_CHECK(d_grad_out != d_feat && d_grad_out != d_grad, "gaib_gat_backward_fused: d_grad_out must not alias an input");
   GAIB_HIP(hipSetDevice(ctx->device));
+  // option gat_fused_wide (see the forward): the row-statistics form only
+  if (ctx->gat_fused_wide == 1 && d_row_stats && !gat_fused_shape(len, heads)) {
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_backward_fused_wide(ctx, g, len, heads, w, S, d_feat, d_grad, d_fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
+                                          epsilon, d_grad_out, d_alpha_lgrad, d_alpha_rgrad);
+  }
   int rc0 = GAIB_OK;
   const bool use = gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_bwd,
                                      (uintptr_t)d_feat | (uintptr_t)d_grad | (uintptr_t)d_norm_scores |

@@ -2,7 +2,10 @@
 // (chunk kernels, the packed-math sweep, their reductions), the per-vertex dots and the alpha-gradient reduction, with the
 // shape rules and dispatch macros of their callers.  gat.hip instantiates them on fp32 tables, gat_bf16.hip on bf16 tables
 // (element type E = uint16_t: raw bf16 bits, loaded as they are and widened where they are consumed), gat_drop.hip the DROP
-// variants of the two sweeps (attention dropout, fp32 tables).
+// variants of the two sweeps (attention dropout, fp32 tables), gat_wide.hip the WIDE variants (rows of a table whose row stride is
+// not the row width: one column slab of a wider multi-head row).
+// WIDE: a template flag with trailing, defaulted stride arguments read only behind `WIDE ? ld : len` -- the other instantiations
+// compile to the instructions they had (the arguments sit behind every argument those read).
 #pragma once
 #include "common.h"
 
@@ -40,10 +43,12 @@ __device__ __forceinline__ float elem_f32(uint16_t v) { return __uint_as_float((
 
 // partial[b][0][c] = sum_{v in strip b} rs[v, head(c)]*x[v][c]; partial[b][1][c] likewise with cs.
 // 256 threads: thread t owns column (t % cw) of every (256/cw)-th row of the strip.
-template <typename E>
+// WIDE: x has rows of ld elements (>= len); rs, cs and partial are the slab's own
+template <typename E, bool WIDE = false>
 __global__ __launch_bounds__(256) void alpha_partial_kernel(int64_t nv, int len, int H, const E* x,
                                                             const float* rs, const float* cs,
-                                                            int64_t rows_per_block, float* partial) {
+                                                            int64_t rows_per_block, float* partial, int ld = 0) {
+  const int xld = WIDE ? ld : len;
   extern __shared__ float sm[];  // [2][256]
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = (r0 + rows_per_block < nv) ? r0 + rows_per_block : nv;
@@ -57,7 +62,7 @@ __global__ __launch_bounds__(256) void alpha_partial_kernel(int64_t nv, int len,
     float al = 0.f, ar = 0.f;
     if (tr < rpp) {
       for (int64_t v = r0 + tr; v < r1; v += rpp) {
-        const float xv = elem_f32(x[v * (int64_t)len + c0 + tc]);
+        const float xv = elem_f32(x[v * (int64_t)xld + c0 + tc]);
         al += rs[v * H + hd] * xv;
         ar += cs[v * H + hd] * xv;
       }
@@ -91,15 +96,16 @@ __global__ __launch_bounds__(256) void alpha_final_kernel(int nblocks, int len, 
   if (lane == 0) (w < len ? lgrad : rgrad)[w < len ? w : w - len] = s;
 }
 
-// rowdot[v,h] = <a[v, slice h], b[v, slice h]>.  One wave per row.
-template <typename E>
+// rowdot[v,h] = <a[v, slice h], b[v, slice h]>.  One wave per row.  WIDE: a and b have rows of ld elements; out stays [nv][H]
+template <typename E, bool WIDE = false>
 __global__ __launch_bounds__(256) void rowdot_kernel(int64_t nv, int len, int H, const E* a,
-                                                     const float* b, float* out) {
+                                                     const float* b, float* out, int ld = 0) {
+  const int xld = WIDE ? ld : len;
   int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= nv) return;
   const int lane = threadIdx.x & 63;
-  const E* ar = a + row * (int64_t)len;
-  const float* br = b + row * (int64_t)len;
+  const E* ar = a + row * (int64_t)xld;
+  const float* br = b + row * (int64_t)xld;
   const int dh = len / H;
   if (H > 1 && dh <= 64 && (64 % dh) == 0) {  // as in vertex_dots_kernel
     for (int c0 = 0; c0 < len; c0 += 64) {
@@ -673,12 +679,14 @@ constexpr float GAT_NEG = -1.0e30f;  // "no edge yet": finite, so exp(NEG - m) =
 
 // DROP (gat_drop.hip): out_i = sum_e p_e w_e h_c with w = mask . scale (gat_drop_bits); (m, ssum) and so the row statistics are the
 // undropped softmax's.  The three trailing arguments are the DROP form's.
-template <int G, int H, int U, typename E, bool DROP = false>
+// WIDE (gat_wide.hip): feat has rows of ld elements of which this launch sweeps len = 4 G; the partials stay len wide.
+template <int G, int H, int U, typename E, bool DROP = false, bool WIDE = false>
 __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
     const int64_t* rowptr, const uint32_t* col, int len, const E* feat, const float* alpha_l, const float* alpha_r,
     float eps, float* out_partial, float2* ms_partial, int phase, uint32_t own_cols, int per_xcd, float drop_rate = 0.0f,
-    float drop_scale = 1.0f, uint64_t drop_seed = 0) {
+    float drop_scale = 1.0f, uint64_t drop_seed = 0, int ld = 0) {
+  const int fld = WIDE ? ld : len;  // row stride of feat
   constexpr int LH = G / H;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
   const int coff = sl * 4;
   const int head = sl / LH;
   using R4 = Row4<E>;
-  const f4 hi = R4::widen(load_row4(feat + row * (int64_t)len + coff));
+  const f4 hi = R4::widen(load_row4(feat + row * (int64_t)fld + coff));
   const f4 al4 = *reinterpret_cast<const f4*>(alpha_l + coff);
   const f4 ar4 = *reinterpret_cast<const f4*>(alpha_r + coff);
   auto d4 = [](const f4& a, const f4& b) {
@@ -721,7 +729,7 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t cj = (uint32_t)CL::step_value((int)cl, (int)cl1, lane, j + u);
-      xh_raw[u] = load_row4(feat + (int64_t)cj * len + coff);
+      xh_raw[u] = load_row4(feat + (int64_t)cj * fld + coff);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -769,10 +777,12 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
 // per row: combine the chunks' (m, s, acc) in chunk order; out = act(sum / S); stats[row][h] = (M, 1/S)
 // (a row is G = len / 4 lanes of 4 columns, so the wave's NG = 64 / G lane groups take the row's chunks k, k + 1, ...,
 // k + NG - 1, ... and meet at the end -- at len 64 a row with 330 chunks is 83 steps deep instead of 330, and no lane idles)
-template <int G>
+// WIDE: out has rows of ld floats and stats rows of stats_ld records (a window of H heads in each); the partials are len / H wide
+template <int G, bool WIDE = false>
 __global__ __launch_bounds__(256) void gat_fwd_reduce_kernel(int64_t nv, int len, int H, const uint32_t* chunk_start,
                                                              const float* out_partial, const float2* ms_partial, int relu,
-                                                             float* out, float2* stats) {
+                                                             float* out, float2* stats, int ld = 0, int stats_ld = 0) {
+  const int out_ld = WIDE ? ld : len, sld = WIDE ? stats_ld : H;
   constexpr int NG = 64 / G;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= nv) return;
@@ -813,15 +823,17 @@ __global__ __launch_bounds__(256) void gat_fwd_reduce_kernel(int64_t nv, int len
     s[q] *= inv;
     if (relu) s[q] = s[q] > 0.f ? s[q] : 0.f;
   }
-  *reinterpret_cast<f4*>(out + row * (int64_t)len + sl * 4) = s;
-  if ((sl * 4) % dh == 0) stats[row * H + head] = float2{M, inv};
+  *reinterpret_cast<f4*>(out + row * (int64_t)out_ld + sl * 4) = s;
+  if ((sl * 4) % dh == 0) stats[row * sld + head] = float2{M, inv};
 }
 
 // out[row] = sum of the row's chunk partials in chunk order; rs / cs [row][H] the same for the g sums
-template <int G>
+// WIDE: out has rows of ld floats; the partials, rs and cs are the slab's own
+template <int G, bool WIDE = false>
 __global__ __launch_bounds__(256) void gat_fused_reduce_kernel(int64_t nv, int len, int H, const uint32_t* chunk_start,
                                                                const float* out_partial, const float* rc_partial,
-                                                               float* out, float* rs, float* cs) {
+                                                               float* out, float* rs, float* cs, int ld = 0) {
+  const int out_ld = WIDE ? ld : len;
   constexpr int NG = 64 / G;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= nv) return;
@@ -848,7 +860,7 @@ __global__ __launch_bounds__(256) void gat_fused_reduce_kernel(int64_t nv, int l
     for (int q = 0; q < 4; ++q) s[q] += __shfl_xor(s[q], o, 64);
   }
   if (grp != 0) return;
-  *reinterpret_cast<f4*>(out + row * (int64_t)len + sl * 4) = s;
+  *reinterpret_cast<f4*>(out + row * (int64_t)out_ld + sl * 4) = s;
   // entries 0..H-1: rs, H..2H-1: cs
 #pragma unroll
   for (int q = 0; q < 4; ++q) {

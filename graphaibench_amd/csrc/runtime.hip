@@ -90,6 +90,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->comm_reserve_default = 0;
   c->gat_interleave = 0;
   c->gat_bf16 = 0;
+  c->gat_fused_wide = 0;  // (ships off: flipped by a change of its own once the layer step is measured faster)
   c->gat_fused_drop = 0;  // (measured, LEDGER 14.2; a default is flipped by a change of its own)
   c->gat_bwd_pk = 0;  // measured, round 6: the packed-math sweep saves a third of the VALU instructions and nothing at the real
                       // column ids (6.27 vs 6.25 ms at the reddit shape: the sweep is bound by the L2 -> fabric gather stream there)
@@ -536,6 +537,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
   else if (!strcmp(key, "gat_bf16")) *h_value = ctx->gat_bf16;
   else if (!strcmp(key, "gat_fused_drop")) *h_value = ctx->gat_fused_drop;
+  else if (!strcmp(key, "gat_fused_wide")) *h_value = ctx->gat_fused_wide;
   else if (!strcmp(key, "gemm_bf16")) *h_value = ctx->gemm_bf16;
   else if (!strcmp(key, "gemm_bf16_kernel")) *h_value = ctx->gemm_bf16_kernel;
   else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
@@ -607,6 +609,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "gat_fused_drop")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_fused_drop must be 0 (attention dropout staged) or 1 (in the one sweep)");
     ctx->gat_fused_drop = (int)value;
+  } else if (!strcmp(key, "gat_fused_wide")) {
+    GAIB_CHECK(value == 0 || value == 1, "gat_fused_wide must be 0 (rows wider than 128 columns staged) or 1 (one sweep per column slab)");
+    ctx->gat_fused_wide = (int)value;
   } else if (!strcmp(key, "gemm_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "gemm_bf16 must be 0 (fp32 self products) or 1 (products on the bf16 table)");
     ctx->gemm_bf16 = (int)value;

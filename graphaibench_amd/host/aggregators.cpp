@@ -635,6 +635,36 @@ void GAT_Aggregator::set_num_heads(int h) {
   // the temp_scores array only where the kernels do not form the pre-activation score again (see needs_temp)
   if (d_temp_scores) float_free_device(d_temp_scores);
   d_temp_scores = needs_temp() ? gaib_host::dmalloc<float>(num_edges * heads) : NULL;
+  if (wide_rows_expected()) {
+    // option gat_fused_wide at a shape it covers, no attention dropout: the one-sweep kernels keep row statistics only, so the
+    // [ne][heads] arrays are not held from here on; a staged piece that needs them after all (a partition, gat_fused_fwd /
+    // gat_fused_bwd = 0, norm_scores_ptr()) allocates them then (grow_edge_arrays)
+    float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t, &d_temp_scores};
+    for (float** a : arrays) float_free_device(*a);
+    num_edges = 0;
+  }
+}
+
+bool GAT_Aggregator::wide_rows_expected() const {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "gat_fused_wide", &v));
+  return v == 1 && attn_drop == 0.f && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
+}
+
+// the [ne][heads] arrays of the staged kernels, for a graph of ne edges: grown where a graph is larger than the one the layer
+// was built on (sampling -> full graph), allocated here in the first place where set_num_heads() did not (wide_rows_expected)
+void GAT_Aggregator::grow_edge_arrays(size_t ne) {
+  if (ne <= num_edges) return;
+  num_edges = ne;
+  float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t};
+  for (float** a : arrays) {
+    float_free_device(*a);
+    *a = gaib_host::dmalloc<float>(num_edges * heads);
+  }
+  if (d_temp_scores || needs_temp()) {
+    float_free_device(d_temp_scores);
+    d_temp_scores = gaib_host::dmalloc<float>(num_edges * heads);
+  }
 }
 
 // ---- GAT on a vertex-range partition ("h halo rows for the scores, g halo rows for the transposed
@@ -647,6 +677,7 @@ void GAT_Aggregator::set_num_heads(int h) {
 // for vertices of other ranks -- travel back to their owners and are added there (gaib_halo_reduce).
 void GAT_Aggregator::ensure_partition_buffers(Graph& g, int len) {
   const size_t nc = g.size() + g.gat_n_halo();
+  grow_edge_arrays(g.sizeEdges());  // (a no-op unless set_num_heads() left them to the first use)
   if (nc * len > ptab_floats) {
     if (d_ptab) float_free_device(d_ptab);
     if (d_pout) float_free_device(d_pout);
@@ -876,18 +907,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   }
   stats_valid = false;
   fwd_bf16 = false;
-  if (g.sizeEdges() > num_edges) {  // a larger graph than the one the layer was built on (sampling -> full graph)
-    num_edges = g.sizeEdges();
-    float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t};
-    for (float** a : arrays) {
-      float_free_device(*a);
-      *a = gaib_host::dmalloc<float>(num_edges * heads);
-    }
-    if (d_temp_scores) {
-      float_free_device(d_temp_scores);
-      d_temp_scores = gaib_host::dmalloc<float>(num_edges * heads);
-    }
-  }
+  grow_edge_arrays(g.sizeEdges());  // a larger graph than the one the layer was built on (sampling -> full graph)
   {
     OpTimer t(OP_SCORE);
     // the leaky-relu output itself is not materialised (NULL): nothing downstream reads it
@@ -966,6 +986,7 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
     if (rc != GAIB_ERR_UNSUPPORTED) GAIB_OR_DIE(rc);  // a real failure; UNSUPPORTED = this shape / graph takes the staged path
   }
   if (stats_valid) materialise_scores();  // (the staged kernels read the attention array)
+  grow_edge_arrays(g.sizeEdges());        // (a no-op unless set_num_heads() left the arrays to the first use)
   {
     OpTimer t(OP_SCORE);
     GAIB_OR_DIE(gaib_sddmm_mh(C(), dev(g), len, heads, grad_in, feat_in, d_norm_scores_grad));
@@ -1003,18 +1024,7 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
 void GAT_Aggregator::materialise_scores() {
   if (!stats_valid || !last_graph) return;
   Graph& g = *last_graph;
-  if (g.sizeEdges() > num_edges) {
-    num_edges = g.sizeEdges();
-    float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t};
-    for (float** a : arrays) {
-      float_free_device(*a);
-      *a = gaib_host::dmalloc<float>(num_edges * heads);
-    }
-    if (d_temp_scores) {
-      float_free_device(d_temp_scores);
-      d_temp_scores = gaib_host::dmalloc<float>(num_edges * heads);
-    }
-  }
+  grow_edge_arrays(g.sizeEdges());
   GAIB_OR_DIE(gaib_gat_scores_mh(C(), dev(g), last_len, heads, last_in, d_alpha_l, d_alpha_r, epsilon, d_temp_scores, NULL,
                                  d_norm_scores));
   stats_valid = false;

@@ -106,6 +106,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gat_fused_drop", v), "gaib_set_option (GAIB_GAT_FUSED_DROP)");
   }
+  // GAT layers with multi-head rows wider than 128 columns (8 heads x 32, 8 x 64): the one-sweep kernels per column slab (option
+  // gat_fused_wide; off by default)
+  if (const char* d = getenv("GAIB_GAT_WIDE")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GAT_WIDE=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gat_fused_wide", v), "gaib_set_option (GAIB_GAT_WIDE)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

@@ -512,6 +512,20 @@ struct Trainer {
       for (auto& l : layers) l.get_aggregator().set_num_heads(atoi(hs));
       std::cout << "GAT attention heads: " << atoi(hs) << "\n";
     }
+    {
+      // option gat_fused_wide (GAIB_GAT_WIDE=1): how the hidden layers' rows of dim_hid columns run -- the one-sweep kernels per
+      // column slab where the shape rule gives slabs (whole graphs without attention dropout: partitions and dropout stay staged at
+      // these widths), else staged
+      int64_t wide = 0;
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_wide", &wide));
+      if (wide == 1 && root()) {
+        const char* hs = getenv("GAIB_GAT_HEADS");
+        int w = 0;
+        const int S = gaib_gat_fused_slabs(dim_hid, hs ? atoi(hs) : 1, &w);
+        if (S >= 2 && score_drop == 0.f && world == 1) std::cout << "GAT wide rows: one sweep, " << S << " slabs of " << w << "\n";
+        else std::cout << "GAT wide rows: staged\n";
+      }
+    }
 #endif
     if (use_l2norm) l2 = new l2norm_layer(nv, dim_hid);
     if (use_dense) dense = new dense_layer(nv, dim_hid, num_cls, lrate);

@@ -354,6 +354,26 @@ int gaib_gat_backward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, co
  * array exists at all.  Same cover as gaib_gat_backward_fused (option "gat_fused_fwd"); GAIB_ERR_UNSUPPORTED otherwise. */
 int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
                            const float* d_alpha_r, float epsilon, int relu, float* d_out, float* d_row_stats);
+/* MULTI-HEAD ROWS WIDER THAN 128 COLUMNS (option "gat_fused_wide", default 0).  Heads are independent in everything the two
+ * sweeps compute, so a row of len = S * w columns with heads = S * Hs heads is S independent problems of w columns and Hs heads
+ * in column windows of the same tables.  gaib_gat_fused_slabs is the shape rule, a pure function (no context, no device): it
+ * returns S and writes w through `width` (which may be NULL): (len, 1) where the one-sweep kernels apply as they are; else the
+ * first w of 128, 64, 32 with len % w == 0, S = len / w >= 2, heads % S == 0 and (w, heads / S) a shape of those kernels; else
+ * 0 (w = 0).  (256, 8) -> 2 slabs of 128; (512, 8) -> 4 of 128; (256, 64) -> 4 of 64; (256, 1) -> 0: a single head wider than
+ * 128 columns stays staged.
+ * With the option at 1, gaib_gat_forward_fused and gaib_gat_backward_fused (row-statistics form: d_row_stats != NULL) accept
+ * every shape with S >= 2 on square graphs, fp32 tables, under today's other conditions (16-byte aligned buffers, "gat_fused_fwd"
+ * / "gat_fused_bwd" != 0, ne > 0; else GAIB_ERR_UNSUPPORTED with nothing touched); with the option at 0 they return what they
+ * always returned.  A wide call is a loop over the slabs on the context's stream, each slab the narrow call's own kernel sequence
+ * at (w, Hs) on strided rows: slab s covers columns [s w, (s + 1) w) of the tables and of the alpha vectors and gradients, and
+ * heads [s Hs, (s + 1) Hs) of d_row_stats, all in their full-width layouts [nv][len] / [nv][heads][2] -- so its outputs there
+ * are BIT-IDENTICAL to the narrow call at (len = w, heads = Hs) on contiguous copies of the windows, under the same options.
+ * "gat_chunk_xcd" is honoured, "gat_fused_unroll" = 8 where w == 64; "gat_bwd_pk" and "gat_interleave" are ignored (the chunk
+ * kernel over the three separate tables runs, as in the _drop calls).  Profile: one record per call under "gat_fwd_fused" /
+ * "gat_bwd_fused", the narrow byte formula at (w, Hs) times S (column ids count S times).
+ * Not covered, today's behaviour at these shapes whatever the option says: the _drop calls (the mask index needs the global
+ * head), the _bf16 calls, the _rect calls, gaib_gat_score_signs, a single head wider than 128 columns, the packed-math sweep. */
+int gaib_gat_fused_slabs(int len, int heads, int* width);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
  * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
@@ -881,6 +901,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * attention dropout, runs gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop instead of the staged kernels and holds
  * neither the mask nor the dropped-attention array; the masks are those of the staged path, seed for seed; partitioned graphs
  * stay staged and bf16 tables ("gat_bf16") are not used under dropout;
+ * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused run multi-head rows wider than 128
+ * columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); attention dropout, bf16 tables and partitions stay
+ * as they are at these widths;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
@@ -892,7 +915,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sampler_device", "gat_fused_drop" */
+ * "sampler_device", "gat_fused_drop", "gat_fused_wide" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

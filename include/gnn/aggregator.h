@@ -190,6 +190,15 @@ class GAT_Aggregator : public aggregator {
   // with gaib_dropout under the kept seed -- the bits the sweep used -- and the staged pieces run.  Partitioned graphs stay
   // staged; bf16 tables (gat_bf16) are not used under dropout, with or without this option.
   static bool gat_fused_drop_option();
+  // extension: multi-head rows wider than 128 columns in the one-sweep kernels, one column slab at a time (context option
+  // "gat_fused_wide" = 1, or GAIB_GAT_WIDE=1, set BEFORE the layer is built).  Nothing changes in aggregate() / d_aggregate():
+  // gaib_gat_forward_fused / gaib_gat_backward_fused accept the shape instead of answering GAIB_ERR_UNSUPPORTED, and every
+  // fallback (gat_fused_bwd = 0, no forward output, norm_scores_ptr()) works from the full-width row statistics as at a narrow
+  // shape.  Where the sweeps are expected to run -- the option, a shape with gaib_gat_fused_slabs >= 2, no attention dropout --
+  // set_num_heads() does not hold the [ne][heads] arrays; grow_edge_arrays() allocates them for the staged piece that first
+  // needs them.  Attention dropout, bf16 tables and partitions stay as they are at these widths.
+  bool wide_rows_expected() const;
+  void grow_edge_arrays(size_t ne);
   bool drop_fused_last = false;  // the last forward was the dropped one sweep under drop_seed_last
   uint64_t drop_seed_last = 0;
   bool drop_sweep_ran = false;   // ... at least once (the trainer reports it)

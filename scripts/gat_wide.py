@@ -1,0 +1,161 @@
+"""The one-sweep GAT on multi-head rows wider than 128 columns (option gat_fused_wide) against the staged path.
+
+Graph: the reddit-shaped graph of bench.py --workload gat-reddit (synth.make("reddit", seed=7), self loops added).  Shapes:
+8 heads x 32 (len 256: 2 slabs of 128) and 8 heads x 64 (len 512: 4 slabs of 128).  Per shape ONE child process under its own
+`timeout`; inside it the legs are interleaved (iteration i runs every leg once, so drift of the box hits all of them alike), 20
+timed iterations after warm-up, median (min - max) in ms, the stream-copy rate of the run beside them:
+  forward     option 0 = what the layer library runs there: gaib_gat_scores_mh + gaib_spmm_mh over the attention array;
+              option 1 = gaib_gat_forward_fused
+  backward    option 0 = gaib_sddmm_mh + gaib_gat_softmax_bwd_alpha_re (one-pass form, transposed attention) + gaib_spmm_mh;
+              option 1 = gaib_gat_backward_fused (row-statistics form)
+  layer step  GAT layer D -> D, no attention dropout, training forward + backward, one layer per setting, in alternating pairs
+  memory      device memory each setting holds after its first step: free memory before the layer is built and after the step
+              (as tests/test_gpu_lifecycle.py measures it), one layer per setting, built and released in turn
+A shape whose child fails or runs into its time limit ends the run: no further child is started.
+
+    python scripts/gat_wide.py OUT.json [--iters 20] [--shapes 256x8,512x8] [--timeout 600]
+"""
+import argparse
+import json
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "scripts"))
+
+
+def child(shape, iters, out_path):
+    import torch
+
+    from bf16_gat import time_legs
+    from graphaibench_amd import capi, layers as L, synth
+
+    ctx = L.init(0)
+    sg = synth.make("reddit", seed=7, device="cuda")
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    nv, ne = g.nv, g.ne
+    rp, ci = g.rowptr(), g.colidx()
+    D, H = (int(v) for v in shape.split("x"))
+    w, S = capi.gat_fused_slabs(D, H)
+    assert S >= 2, (D, H, w, S)
+    r = dict(len=D, heads=H, slab_width=w, slabs=S, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    h = torch.randn(nv, D, device="cuda", generator=gen)
+    grad = torch.randn(nv, D, device="cuda", generator=gen)
+    al = torch.randn(D, device="cuda", generator=gen) * 0.2
+    ar = torch.randn(D, device="cuda", generator=gen) * 0.2
+    out, stats = torch.empty(nv, D, device="cuda"), torch.empty(nv, H, 2, device="cuda")
+    go, lg, rg = torch.empty(nv, D, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
+    norm, dp, norm_t = (torch.empty(ne, H, device="cuda") for _ in range(3))  # the staged path's [ne][heads] arrays
+    ctx.set_option("gat_fused_wide", 1)
+    assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
+    fwd = out.clone()
+
+    def fwd_staged():
+        ctx.gat_scores(g, h, al, ar, None, None, norm, heads=H)
+        ctx.spmm(g, capi.W_EDGE, h, out, edge_w=norm, heads=H)
+
+    def fwd_sweep():
+        assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
+
+    def bwd_staged():
+        ctx.sddmm(g, grad, h, dp, heads=H)
+        ctx.gat_softmax_bwd_alpha(g, h, norm, dp, None, None, lg, rg, heads=H, grad_rows=grad, fwd_out_rows=fwd, norm_t=norm_t,
+                                  alpha=(al, ar))
+        ctx.spmm(g, capi.W_EDGE, grad, go, edge_w=norm_t, heads=H)
+
+    def bwd_sweep():
+        assert ctx.gat_backward_fused(g, h, grad, fwd, al, ar, None, go, lg, rg, heads=H, row_stats=stats)
+
+    r["calls"] = time_legs({"fwd_option_0": fwd_staged, "fwd_option_1": fwd_sweep, "bwd_option_0": bwd_staged,
+                            "bwd_option_1": bwd_sweep}, iters)
+    del out, go, fwd, norm, dp, norm_t
+    g.close()
+    torch.cuda.empty_cache()
+
+    def free_bytes():
+        L.sync()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    lout, lgo = torch.empty(nv, D, device="cuda"), torch.empty(nv, D, device="cuda")
+
+    def make_layer(option):
+        """(layer, its graph, bytes it holds after one training step)"""
+        ctx.set_option("gat_fused_wide", option)
+        before = free_bytes()
+        lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True)
+        ld.set_heads(H)
+        ld.write(L.FEAT_IN, h)
+        ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
+        ld.set_phase(0)
+        ld.forward(lout)
+        ld.backward(lout, lgo)
+        return ld, lg_graph, before - free_bytes()
+
+    def step(ld, option):
+        def run():
+            ctx.set_option("gat_fused_wide", option)
+            ld.forward(lout)
+            ld.backward(lout, lgo)
+        return run
+
+    # a throw-away layer first: the context's workspace and the allocator's caches reach their size before anything is measured
+    ld, lgr, _ = make_layer(0)
+    ld.close()
+    lgr.close()
+    r["held_bytes"] = {}
+    for option in (0, 1):
+        ld, lgr, held = make_layer(option)
+        r["held_bytes"][f"gat_fused_wide_{option}"] = held
+        ld.close()
+        lgr.close()
+    l0, g0_, _ = make_layer(0)
+    l1, g1_, _ = make_layer(1)
+    r["layer_step"] = time_legs({"gat_fused_wide_0": step(l0, 0), "gat_fused_wide_1": step(l1, 1)}, iters)
+    ctx.set_option("gat_fused_wide", 0)
+    for x in (l0, l1):
+        x.close()
+    for x in (g0_, g1_):
+        x.close()
+    r["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    Path(out_path).write_text(json.dumps(r) + "\n")
+    print(json.dumps(r), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--shapes", default="256x8,512x8")
+    ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        child(args.child, args.iters, args.out)
+        return
+    rec = dict(what="GAT rows wider than 128 columns: one-sweep kernels per column slab (gat_fused_wide = 1) against the staged path (0, the baseline)",
+               graph="reddit synth (seed 7) + self loops", shapes=[])
+    with tempfile.TemporaryDirectory() as tmp:
+        for shape in args.shapes.split(","):
+            part = Path(tmp) / f"{shape}.json"
+            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
+                   "--iters", str(args.iters)]
+            rc = subprocess.run(cmd).returncode
+            if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
+                rec["stopped"] = dict(shape=shape, exit_status=rc)
+                break
+            rec["shapes"].append(json.loads(part.read_text()))
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(rec, indent=1) + "\n")
+    sys.exit(1 if "stopped" in rec else 0)
+
+
+if __name__ == "__main__":
+    main()
