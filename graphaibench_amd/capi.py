@@ -115,6 +115,8 @@ SIGNATURES = {
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
     "gaib_gat_backward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp, _vp]),
+    "gaib_gat_forward_fused_drop_win": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _i, _i, _vp, _vp]),
+    "gaib_gat_backward_fused_drop_win": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _i, _i, _vp, _vp, _vp]),
     "gaib_edge_transpose_mh": (_i, [_vp, _vp, _i, _vp, _vp]),
     "gaib_gat_scores": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_sddmm": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -892,6 +894,39 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gat_backward_fused_drop")
+        return True
+
+    def gat_forward_fused_drop_win(self, g, h, alpha_l, alpha_r, out, row_stats, rate: float, seed: int, mask_heads: int,
+                                   mask_head0: int, scale=None, eps: float = 0.2, heads: int = 1, relu: bool = False) -> bool:
+        """gat_forward_fused_drop whose heads are heads [mask_head0, mask_head0 + heads) of a row of mask_heads heads: the mask of
+        (edge e, local head k) is the one `dropout` draws for element e * mask_heads + mask_head0 + k.  False = not applicable"""
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gat_forward_fused_drop_win(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(alpha_l), _ptr(alpha_r), eps,
+                                                      int(relu), rate, scale, seed, mask_heads, mask_head0, _ptr(out),
+                                                      _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_forward_fused_drop_win")
+        return True
+
+    def gat_backward_fused_drop_win(self, g, feat, grad, fwd_out, alpha_l, alpha_r, grad_out, lgrad, rgrad, row_stats, rate: float,
+                                    seed: int, mask_heads: int, mask_head0: int, scale=None, eps: float = 0.2,
+                                    heads: int = 1) -> bool:
+        """gat_backward_fused_drop through the masks of gat_forward_fused_drop_win with the same rate, seed and window.
+        False = not applicable (nothing touched)"""
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gat_backward_fused_drop_win(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out),
+                                                       _ptr(alpha_l), _ptr(alpha_r), _ptr(row_stats), eps, rate, scale, seed,
+                                                       mask_heads, mask_head0, _ptr(grad_out), _ptr(lgrad), _ptr(rgrad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_backward_fused_drop_win")
         return True
 
     def edge_transpose(self, g, in_e, out_e, heads: int = 1):

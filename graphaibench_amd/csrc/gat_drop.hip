@@ -8,6 +8,8 @@
 //             gaib_gat_backward_fused (row-statistics form)
 // With rate 0 and scale 1 every w is 1.0f and a product by it changes no bit: the results are the undropped calls'.
 // The reverse edge's mask needs rev(e): a graph without a reverse-edge permutation is refused by forward and backward alike.
+// With option gat_fused_wide = 1 a multi-head row wider than 128 columns goes to the slab loop of gat_wide.hip, where every slab
+// reaches its heads' masks through a window of the [ne][heads] index (gaib_gat_*_fused_drop_win).
 #include "gat_kernels.h"
 
 static int gat_drop_refuse(const char* who, int len, int heads) {
@@ -25,6 +27,14 @@ extern "C" int gaib_gat_forward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int len
   if (g->nv == 0 || g->nc != g->nv) return gat_drop_refuse(who, len, heads);  // (no rows: as gaib_gat_forward_fused; no _rect form)
   GAIB_CHECK(d_h && d_alpha_l && d_alpha_r && d_out && d_row_stats && d_out != d_h, "%s: NULL or aliased pointer", who);
   GAIB_HIP(hipSetDevice(ctx->device));
+  // option gat_fused_wide: a multi-head row wider than 128 columns as S column slabs, each with its window of the mask (gat_wide.hip)
+  if (ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_forward_fused_drop_wide(ctx, g, len, heads, w, S, d_h, d_alpha_l, d_alpha_r, epsilon, relu, drop_rate, scale, seed,
+                                              d_out, d_row_stats);
+  }
   int rc = GAIB_OK;
   const uintptr_t align_or = (uintptr_t)d_h | (uintptr_t)d_out | (uintptr_t)d_row_stats | (uintptr_t)d_alpha_l | (uintptr_t)d_alpha_r;
   if (!gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_fwd, align_or, &rc)) return gat_drop_refuse(who, len, heads);
@@ -84,6 +94,13 @@ extern "C" int gaib_gat_backward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int le
   GAIB_CHECK(d_grad_out != d_feat && d_grad_out != d_grad, "%s: d_grad_out must not alias an input", who);
   if (g->nc != g->nv) return gat_drop_refuse(who, len, heads);
   GAIB_HIP(hipSetDevice(ctx->device));
+  if (ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {  // (see the forward)
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_backward_fused_drop_wide(ctx, g, len, heads, w, S, d_feat, d_grad, d_fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
+                                               epsilon, drop_rate, scale, seed, d_grad_out, d_alpha_lgrad, d_alpha_rgrad);
+  }
   int rc0 = GAIB_OK;
   const uintptr_t align_or = (uintptr_t)d_feat | (uintptr_t)d_grad | (uintptr_t)d_row_stats | (uintptr_t)d_grad_out;
   if (!gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_bwd, align_or, &rc0)) return gat_drop_refuse(who, len, heads);

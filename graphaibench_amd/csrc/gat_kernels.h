@@ -6,6 +6,8 @@
 // not the row width: one column slab of a wider multi-head row).
 // WIDE: a template flag with trailing, defaulted stride arguments read only behind `WIDE ? ld : len` -- the other instantiations
 // compile to the instructions they had (the arguments sit behind every argument those read).
+// WIN (gat_wide.hip, the dropped sweeps on a slab): the dropout mask's index takes the FULL row's head count and the slab's first
+// head from two more trailing arguments (gat_drop_bits); forward: DROP && WIDE, backward: a template flag of its own.
 #pragma once
 #include "common.h"
 
@@ -233,25 +235,41 @@ __global__ __launch_bounds__(256) void gat_interleave_kernel(int64_t nv, int len
 // step, and an OR over the head's lanes (DPP) leaves all G bits in each of them.  In the loop the mask of step t is bit t.
 // IDS = false: the chunk's own edges eb + (edge of the step) -- consecutive steps of a lane are LH * NG edges apart, so the
 // key of the next step is an addition; else the ids are read from ids[] at those positions (the reverse edges).
-template <int G, int H, bool IDS>
-__device__ __forceinline__ uint32_t gat_drop_bits(int lane, int n, int64_t eb, const uint32_t* ids, uint64_t seed, float rate) {
+// WIN: the chunk is one column slab of a wider row -- H heads from head mask_head0 on of mask_heads: the mask is the one of element
+// e * mask_heads + mask_head0 + k of the virtual [ne][mask_heads] array (e * H + k would be another mask).  The key is linear in
+// the index, so the slab needs those two numbers and nothing else; the row side's step increment becomes one wave-uniform 64-bit
+// product per chunk, U01_GOLD (LH NG) mask_heads, where the other form folds a constant.
+// (the two arguments are read under WIN only)
+template <int G, int H, bool IDS, bool WIN>
+__device__ __forceinline__ uint32_t gat_drop_bits(int lane, int n, int64_t eb, const uint32_t* ids, uint64_t seed, float rate,
+                                                  int mask_heads, int mask_head0) {
   constexpr int LH = G / H;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
   const int sl = lane & (G - 1);
   const int head = sl / LH, q = sl & (LH - 1);
   const int e0 = CL::step_edge(lane, q);  // step t of this lane's group is edge e0 + (t - q) * NG
-  uint64_t z = u01_key(seed, (uint64_t)(eb + e0) * (uint64_t)H + (uint64_t)head);  // (the index in 64 bits: ne * H passes 2^32)
+  uint64_t z, dz, mh, hd;                 // key, its increment per step of this lane, row length and column of the mask array
+  if constexpr (WIN) {
+    mh = (uint64_t)mask_heads;
+    hd = (uint64_t)mask_head0 + (uint64_t)head;
+    dz = (U01_GOLD * (uint64_t)(LH * NG)) * mh;
+  } else {
+    mh = (uint64_t)H;
+    hd = (uint64_t)head;
+    dz = U01_GOLD * (uint64_t)(LH * NG * H);
+  }
+  z = u01_key(seed, (uint64_t)(eb + e0) * mh + hd);  // (the index in 64 bits: ne * H passes 2^32)
   uint32_t bits = 0;
 #pragma unroll
   for (int s = 0; s < H; ++s) {  // step s * LH + q
     if (s * LH * NG < n) {       // (wave-uniform: else no lane's step s * LH + q has an edge)
       if constexpr (IDS) {
         const int ei = e0 + s * LH * NG;
-        z = u01_key(seed, (uint64_t)ids[eb + (ei < n ? ei : 0)] * (uint64_t)H + (uint64_t)head);
+        z = u01_key(seed, (uint64_t)ids[eb + (ei < n ? ei : 0)] * mh + hd);
       }
       bits |= (u01_of_key(z) > rate ? 1u : 0u) << (s * LH + q);
-      if constexpr (!IDS) z += U01_GOLD * (uint64_t)(LH * NG * H);
+      if constexpr (!IDS) z += dz;
     }
   }
   return lanes_or<LH>(bits);
@@ -259,13 +277,15 @@ __device__ __forceinline__ uint32_t gat_drop_bits(int lane, int n, int64_t eb, c
 
 // DROP (gat_drop.hip; RECOMP form): attention dropout inside the sweep, see gat_drop_bits; rev is then read for the reverse edges' masks.
 // The three trailing arguments are the DROP form's; the others' launches leave them to their defaults.
-template <int G, int H, int U, bool RECOMP, typename E, bool DROP = false>
+// WIN (gat_wide.hip; DROP form): the masks' index window, see gat_drop_bits; its two arguments trail the DROP form's.
+template <int G, int H, int U, bool RECOMP, typename E, bool DROP = false, bool WIN = false>
 __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
     const int64_t* rowptr, const uint32_t* col, const uint32_t* rev, int len, const E* feat, const E* grad,
     const float* p, const float2* stats, const float* rowdot, const float* alpha_l, const float* alpha_r, float eps,
     float* out_partial, float* rc_partial, const f4* rec, int phase, uint32_t own_cols, int ld, int rec_ld, int per_xcd,
-    float drop_rate = 0.0f, float drop_scale = 1.0f, uint64_t drop_seed = 0) {
+    float drop_rate = 0.0f, float drop_scale = 1.0f, uint64_t drop_seed = 0, int mask_heads = 0, int mask_head0 = 0) {
+  static_assert(!WIN || DROP, "the head window belongs to the dropout mask");
   // rec (RECOMP): (rowdot, row maximum, 1 / row sum) per (vertex, head) as one 16-byte record, see gat_rec_kernel
   // ld / rec_ld: row strides of the feat / grad tables (floats) and of the record table (16-byte records): len and H for
   // three separate tables; 2 len + 4 H and that / 4 when the three live INTERLEAVED, one [h | grad | records] row per vertex
@@ -312,8 +332,8 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
   // DROP: the masks of the chunk's edges (-> dp_e) and of their reverse edges (-> dp_r, the weight of grad_c), one bit per step
   uint32_t mb_e = 0, mb_r = 0;
   if constexpr (DROP) {
-    mb_e = gat_drop_bits<G, H, false>(lane, n, eb, nullptr, drop_seed, drop_rate);
-    mb_r = gat_drop_bits<G, H, true>(lane, n, eb, rev, drop_seed, drop_rate);
+    mb_e = gat_drop_bits<G, H, false, WIN>(lane, n, eb, nullptr, drop_seed, drop_rate, mask_heads, mask_head0);
+    mb_r = gat_drop_bits<G, H, true, WIN>(lane, n, eb, rev, drop_seed, drop_rate, mask_heads, mask_head0);
   }
   const int coff = sl * 4;  // len == 4 * G
   const int head = sl / LH;
@@ -680,12 +700,13 @@ constexpr float GAT_NEG = -1.0e30f;  // "no edge yet": finite, so exp(NEG - m) =
 // DROP (gat_drop.hip): out_i = sum_e p_e w_e h_c with w = mask . scale (gat_drop_bits); (m, ssum) and so the row statistics are the
 // undropped softmax's.  The three trailing arguments are the DROP form's.
 // WIDE (gat_wide.hip): feat has rows of ld elements of which this launch sweeps len = 4 G; the partials stay len wide.
+// DROP && WIDE: the masks' index window (gat_drop_bits<.., WIN>) from the two arguments behind ld.
 template <int G, int H, int U, typename E, bool DROP = false, bool WIDE = false>
 __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
     const int64_t* rowptr, const uint32_t* col, int len, const E* feat, const float* alpha_l, const float* alpha_r,
     float eps, float* out_partial, float2* ms_partial, int phase, uint32_t own_cols, int per_xcd, float drop_rate = 0.0f,
-    float drop_scale = 1.0f, uint64_t drop_seed = 0, int ld = 0) {
+    float drop_scale = 1.0f, uint64_t drop_seed = 0, int ld = 0, int mask_heads = 0, int mask_head0 = 0) {
   const int fld = WIDE ? ld : len;  // row stride of feat
   constexpr int LH = G / H;
   using CL = ChunkLanes<G>;
@@ -719,7 +740,7 @@ __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
   };
   const float sl_i = lanes_sum_w<LH>(d4(al4, hi));  // (DPP sums / broadcasts, FMA chains: see the backward kernel)
   uint32_t mb = 0;  // DROP: the masks of the chunk's edges, one bit per step (gat_drop_bits)
-  if constexpr (DROP) mb = gat_drop_bits<G, H, false>(lane, n, eb, nullptr, drop_seed, drop_rate);
+  if constexpr (DROP) mb = gat_drop_bits<G, H, false, WIDE>(lane, n, eb, nullptr, drop_seed, drop_rate, mask_heads, mask_head0);
   float m = GAT_NEG, ssum = 0.f;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll

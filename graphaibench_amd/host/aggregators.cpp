@@ -636,9 +636,10 @@ void GAT_Aggregator::set_num_heads(int h) {
   if (d_temp_scores) float_free_device(d_temp_scores);
   d_temp_scores = needs_temp() ? gaib_host::dmalloc<float>(num_edges * heads) : NULL;
   if (wide_rows_expected()) {
-    // option gat_fused_wide at a shape it covers, no attention dropout: the one-sweep kernels keep row statistics only, so the
-    // [ne][heads] arrays are not held from here on; a staged piece that needs them after all (a partition, gat_fused_fwd /
-    // gat_fused_bwd = 0, norm_scores_ptr()) allocates them then (grow_edge_arrays)
+    // option gat_fused_wide at a shape it covers, without attention dropout or with it kept in the sweep (gat_fused_drop): the
+    // one-sweep kernels keep row statistics only, so the [ne][heads] arrays are not held from here on; a staged piece that needs
+    // them after all (a partition, gat_fused_fwd / gat_fused_bwd = 0, norm_scores_ptr()) allocates them then (grow_edge_arrays),
+    // mask and dropped attention likewise (apply_attn_dropout)
     float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t, &d_temp_scores};
     for (float** a : arrays) float_free_device(*a);
     num_edges = 0;
@@ -648,7 +649,7 @@ void GAT_Aggregator::set_num_heads(int h) {
 bool GAT_Aggregator::wide_rows_expected() const {
   int64_t v = 0;
   GAIB_OR_DIE(gaib_get_option(C(), "gat_fused_wide", &v));
-  return v == 1 && attn_drop == 0.f && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
+  return v == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
 }
 
 // the [ne][heads] arrays of the staged kernels, for a graph of ne edges: grown where a graph is larger than the one the layer

@@ -514,15 +514,16 @@ struct Trainer {
     }
     {
       // option gat_fused_wide (GAIB_GAT_WIDE=1): how the hidden layers' rows of dim_hid columns run -- the one-sweep kernels per
-      // column slab where the shape rule gives slabs (whole graphs without attention dropout: partitions and dropout stay staged at
-      // these widths), else staged
-      int64_t wide = 0;
+      // column slab where the shape rule gives slabs (whole graphs; under attention dropout only with option gat_fused_drop as
+      // well, GAIB_GAT_FUSED_DROP=1: partitions, and dropout without that option, stay staged at these widths), else staged
+      int64_t wide = 0, drop_sweep = 0;
       GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_wide", &wide));
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_drop", &drop_sweep));
       if (wide == 1 && root()) {
         const char* hs = getenv("GAIB_GAT_HEADS");
         int w = 0;
         const int S = gaib_gat_fused_slabs(dim_hid, hs ? atoi(hs) : 1, &w);
-        if (S >= 2 && score_drop == 0.f && world == 1) std::cout << "GAT wide rows: one sweep, " << S << " slabs of " << w << "\n";
+        if (S >= 2 && (score_drop == 0.f || drop_sweep == 1) && world == 1) std::cout << "GAT wide rows: one sweep, " << S << " slabs of " << w << "\n";
         else std::cout << "GAT wide rows: staged\n";
       }
     }

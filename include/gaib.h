@@ -371,8 +371,9 @@ int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, con
  * "gat_chunk_xcd" is honoured, "gat_fused_unroll" = 8 where w == 64; "gat_bwd_pk" and "gat_interleave" are ignored (the chunk
  * kernel over the three separate tables runs, as in the _drop calls).  Profile: one record per call under "gat_fwd_fused" /
  * "gat_bwd_fused", the narrow byte formula at (w, Hs) times S (column ids count S times).
- * Not covered, today's behaviour at these shapes whatever the option says: the _drop calls (the mask index needs the global
- * head), the _bf16 calls, the _rect calls, gaib_gat_score_signs, a single head wider than 128 columns, the packed-math sweep. */
+ * The _drop calls are covered too, see gaib_gat_forward_fused_drop_win below.  Not covered, today's behaviour at these shapes
+ * whatever the option says: the _bf16 calls, the _rect calls, gaib_gat_score_signs, a single head wider than 128 columns, the
+ * packed-math sweep. */
 int gaib_gat_fused_slabs(int len, int heads, int* width);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
@@ -420,6 +421,29 @@ int gaib_gat_backward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int len, int head
                                  const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
                                  const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
                                  float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
+/* ATTENTION DROPOUT THROUGH A HEAD WINDOW OF THE MASK, and the _drop calls on rows wider than 128 columns.
+ * The _win calls are the _drop calls at the same narrow shapes (len 32 / 64 / 128, contiguous tables [nv][len]) whose `heads`
+ * heads are heads [mask_head0, mask_head0 + heads) of a row of mask_heads heads: the mask of (edge e, local head k) is the one
+ * gaib_dropout draws for element e * mask_heads + mask_head0 + k (the index is formed in 64 bits).  With mask_heads == heads and
+ * mask_head0 == 0 every output has the bits of the _drop call.  mask_head0 < 0 or mask_head0 + heads > mask_heads ->
+ * GAIB_ERR_INVALID; cover, options, profile and every other refusal are those of the _drop calls.
+ * With option "gat_fused_wide" = 1, gaib_gat_forward_fused_drop and gaib_gat_backward_fused_drop accept every shape where
+ * gaib_gat_fused_slabs(len, heads) gives S >= 2, under the _drop calls' other conditions (square graphs, fp32 tables, 16-byte
+ * aligned buffers, "gat_fused_fwd" / "gat_fused_bwd" != 0, ne > 0, a buildable reverse-edge permutation; else the _drop calls'
+ * answer with nothing touched); with the option at 0 they answer as they always did.  The call is the slab loop of the undropped
+ * wide calls: slab s is the window sequence at (w, Hs, mask_heads = heads, mask_head0 = s * Hs) on strided rows, so in its
+ * columns and heads the outputs are BIT-IDENTICAL to the _win call on contiguous copies of the column windows, and the masks are
+ * those of the [ne][heads] array of the full row.  d_row_stats has the bits of the undropped wide call; drop_rate = 0 with
+ * scale = 1 gives the undropped wide call's bits everywhere.  "gat_chunk_xcd" is honoured, "gat_fused_unroll" = 8 where w == 64.
+ * Profile: one record per call under "gat_fwd_fused" / "gat_bwd_fused" with the wide byte formula. */
+int gaib_gat_forward_fused_drop_win(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
+                                    const float* d_alpha_r, float epsilon, int relu, float drop_rate, float scale, uint64_t seed,
+                                    int mask_heads, int mask_head0, float* d_out, float* d_row_stats);
+int gaib_gat_backward_fused_drop_win(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
+                                     const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
+                                     const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
+                                     int mask_heads, int mask_head0, float* d_grad_out, float* d_alpha_lgrad,
+                                     float* d_alpha_rgrad);
 /* Test / diagnostic: d_sign_out [ne][heads] (uint8) = (t_e > 0) of every pre-activation score a_l.h[i] + a_r.h[col_e]
  * EXACTLY as the one-sweep kernels form it.  leaky_relu' jumps at 0, so a score within rounding of zero takes either
  * slope in two correct fp32 evaluations; a comparison of the alpha gradients with an fp64 evaluation imposes these signs
@@ -901,9 +925,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * attention dropout, runs gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop instead of the staged kernels and holds
  * neither the mask nor the dropped-attention array; the masks are those of the staged path, seed for seed; partitioned graphs
  * stay staged and bf16 tables ("gat_bf16") are not used under dropout;
- * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused run multi-head rows wider than 128
- * columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); attention dropout, bf16 tables and partitions stay
- * as they are at these widths;
+ * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head
+ * rows wider than 128 columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); the layer library keeps attention
+ * dropout in the sweep there only with "gat_fused_drop" = 1 as well; bf16 tables and partitions stay as they are at these widths;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused

@@ -194,9 +194,11 @@ class GAT_Aggregator : public aggregator {
   // "gat_fused_wide" = 1, or GAIB_GAT_WIDE=1, set BEFORE the layer is built).  Nothing changes in aggregate() / d_aggregate():
   // gaib_gat_forward_fused / gaib_gat_backward_fused accept the shape instead of answering GAIB_ERR_UNSUPPORTED, and every
   // fallback (gat_fused_bwd = 0, no forward output, norm_scores_ptr()) works from the full-width row statistics as at a narrow
-  // shape.  Where the sweeps are expected to run -- the option, a shape with gaib_gat_fused_slabs >= 2, no attention dropout --
-  // set_num_heads() does not hold the [ne][heads] arrays; grow_edge_arrays() allocates them for the staged piece that first
-  // needs them.  Attention dropout, bf16 tables and partitions stay as they are at these widths.
+  // shape.  Where the sweeps are expected to run -- the option, a shape with gaib_gat_fused_slabs >= 2, and either no attention
+  // dropout or option "gat_fused_drop" = 1 as well (the _drop calls then accept the shape too) -- set_num_heads() does not hold
+  // the [ne][heads] arrays; grow_edge_arrays() allocates them for the staged piece that first needs them, apply_attn_dropout()
+  // mask and dropped attention.  Attention dropout without "gat_fused_drop", bf16 tables and partitions stay as they are at
+  // these widths.
   bool wide_rows_expected() const;
   void grow_edge_arrays(size_t ne);
   bool drop_fused_last = false;  // the last forward was the dropped one sweep under drop_seed_last

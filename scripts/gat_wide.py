@@ -13,7 +13,12 @@ timed iterations after warm-up, median (min - max) in ms, the stream-copy rate o
               (as tests/test_gpu_lifecycle.py measures it), one layer per setting, built and released in turn
 A shape whose child fails or runs into its time limit ends the run: no further child is started.
 
-    python scripts/gat_wide.py OUT.json [--iters 20] [--shapes 256x8,512x8] [--timeout 600]
+--drop RATE: the same legs under attention dropout.  Option 0 is both options 0, the staged path call for call
+(forward: + gaib_dropout over the attention array; backward: + gaib_d_dropout of dp and the transpose of the dropped attention);
+option 1 is gat_fused_wide = gat_fused_drop = 1: gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop per column slab, and
+the layer with score_drop = RATE.
+
+    python scripts/gat_wide.py OUT.json [--iters 20] [--shapes 256x8,512x8] [--timeout 600] [--drop 0.3]
 """
 import argparse
 import json
@@ -27,7 +32,10 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "scripts"))
 
 
-def child(shape, iters, out_path):
+SEED = 0x5EED0001
+
+
+def child(shape, iters, out_path, drop=0.0):
     import torch
 
     from bf16_gat import time_legs
@@ -44,6 +52,10 @@ def child(shape, iters, out_path):
     w, S = capi.gat_fused_slabs(D, H)
     assert S >= 2, (D, H, w, S)
     r = dict(len=D, heads=H, slab_width=w, slabs=S, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    options = ("gat_fused_wide", "gat_fused_drop") if drop > 0 else ("gat_fused_wide",)  # what "option 0 / 1" sets
+    tag = "_".join(options)
+    if drop > 0:
+        r["rate"] = drop
     gen = torch.Generator(device="cuda").manual_seed(1)
     h = torch.randn(nv, D, device="cuda", generator=gen)
     grad = torch.randn(nv, D, device="cuda", generator=gen)
@@ -52,29 +64,48 @@ def child(shape, iters, out_path):
     out, stats = torch.empty(nv, D, device="cuda"), torch.empty(nv, H, 2, device="cuda")
     go, lg, rg = torch.empty(nv, D, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
     norm, dp, norm_t = (torch.empty(ne, H, device="cuda") for _ in range(3))  # the staged path's [ne][heads] arrays
+    if drop > 0:  # the staged path's mask and dropped attention
+        masks, norm_drop = torch.empty(ne * H, dtype=torch.uint8, device="cuda"), torch.empty(ne, H, device="cuda")
     ctx.set_option("gat_fused_wide", 1)
-    assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
+    if drop > 0:
+        assert ctx.gat_forward_fused_drop(g, h, al, ar, out, stats, drop, SEED, heads=H)  # (builds the reverse-edge permutation)
+    else:
+        assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
     fwd = out.clone()
 
     def fwd_staged():
         ctx.gat_scores(g, h, al, ar, None, None, norm, heads=H)
-        ctx.spmm(g, capi.W_EDGE, h, out, edge_w=norm, heads=H)
+        if drop > 0:
+            ctx.dropout(norm, masks, norm_drop, drop, SEED)
+        ctx.spmm(g, capi.W_EDGE, h, out, edge_w=norm_drop if drop > 0 else norm, heads=H)
 
     def fwd_sweep():
-        assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
+        if drop > 0:
+            assert ctx.gat_forward_fused_drop(g, h, al, ar, out, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_forward_fused(g, h, al, ar, out, stats, heads=H)
 
     def bwd_staged():
         ctx.sddmm(g, grad, h, dp, heads=H)
+        if drop > 0:
+            ctx.d_dropout(dp, masks, dp, drop)
         ctx.gat_softmax_bwd_alpha(g, h, norm, dp, None, None, lg, rg, heads=H, grad_rows=grad, fwd_out_rows=fwd, norm_t=norm_t,
                                   alpha=(al, ar))
+        if drop > 0:  # the gradient flows back along the dropped attention: its transpose replaces the undropped one
+            ctx.edge_transpose(g, norm_drop, norm_t, heads=H)
         ctx.spmm(g, capi.W_EDGE, grad, go, edge_w=norm_t, heads=H)
 
     def bwd_sweep():
-        assert ctx.gat_backward_fused(g, h, grad, fwd, al, ar, None, go, lg, rg, heads=H, row_stats=stats)
+        if drop > 0:
+            assert ctx.gat_backward_fused_drop(g, h, grad, fwd, al, ar, go, lg, rg, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_backward_fused(g, h, grad, fwd, al, ar, None, go, lg, rg, heads=H, row_stats=stats)
 
     r["calls"] = time_legs({"fwd_option_0": fwd_staged, "fwd_option_1": fwd_sweep, "bwd_option_0": bwd_staged,
                             "bwd_option_1": bwd_sweep}, iters)
     del out, go, fwd, norm, dp, norm_t
+    if drop > 0:
+        del masks, norm_drop
     g.close()
     torch.cuda.empty_cache()
 
@@ -87,10 +118,11 @@ def child(shape, iters, out_path):
 
     def make_layer(option):
         """(layer, its graph, bytes it holds after one training step)"""
-        ctx.set_option("gat_fused_wide", option)
+        for key in options:
+            ctx.set_option(key, option)
         before = free_bytes()
         lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
-        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True)
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True, score_drop=drop)
         ld.set_heads(H)
         ld.write(L.FEAT_IN, h)
         ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
@@ -101,7 +133,8 @@ def child(shape, iters, out_path):
 
     def step(ld, option):
         def run():
-            ctx.set_option("gat_fused_wide", option)
+            for key in options:
+                ctx.set_option(key, option)
             ld.forward(lout)
             ld.backward(lout, lgo)
         return run
@@ -113,13 +146,14 @@ def child(shape, iters, out_path):
     r["held_bytes"] = {}
     for option in (0, 1):
         ld, lgr, held = make_layer(option)
-        r["held_bytes"][f"gat_fused_wide_{option}"] = held
+        r["held_bytes"][f"{tag}_{option}"] = held
         ld.close()
         lgr.close()
     l0, g0_, _ = make_layer(0)
     l1, g1_, _ = make_layer(1)
-    r["layer_step"] = time_legs({"gat_fused_wide_0": step(l0, 0), "gat_fused_wide_1": step(l1, 1)}, iters)
-    ctx.set_option("gat_fused_wide", 0)
+    r["layer_step"] = time_legs({f"{tag}_0": step(l0, 0), f"{tag}_1": step(l1, 1)}, iters)
+    for key in options:
+        ctx.set_option(key, 0)
     for x in (l0, l1):
         x.close()
     for x in (g0_, g1_):
@@ -135,18 +169,23 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default="256x8,512x8")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
+    ap.add_argument("--drop", type=float, default=0.0, help="attention dropout rate: the legs under dropout, both options 0 against both 1")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    assert 0.0 <= args.drop < 1.0, args.drop
     if args.child:
-        child(args.child, args.iters, args.out)
+        child(args.child, args.iters, args.out, args.drop)
         return
-    rec = dict(what="GAT rows wider than 128 columns: one-sweep kernels per column slab (gat_fused_wide = 1) against the staged path (0, the baseline)",
-               graph="reddit synth (seed 7) + self loops", shapes=[])
+    what = "GAT rows wider than 128 columns: one-sweep kernels per column slab (gat_fused_wide = 1) against the staged path (0, the baseline)"
+    if args.drop > 0:
+        what = (f"GAT rows wider than 128 columns under attention dropout {args.drop}: one-sweep kernels per column slab with the mask "
+                "formed in the sweep (gat_fused_wide = gat_fused_drop = 1) against the staged path (both 0, the baseline)")
+    rec = dict(what=what, graph="reddit synth (seed 7) + self loops", shapes=[])
     with tempfile.TemporaryDirectory() as tmp:
         for shape in args.shapes.split(","):
             part = Path(tmp) / f"{shape}.json"
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
-                   "--iters", str(args.iters)]
+                   "--iters", str(args.iters), "--drop", str(args.drop)]
             rc = subprocess.run(cmd).returncode
             if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
                 rec["stopped"] = dict(shape=shape, exit_status=rc)
