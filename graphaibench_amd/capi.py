@@ -115,6 +115,8 @@ SIGNATURES = {
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
     "gaib_gat_backward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp, _vp]),
+    "gaib_gat_forward_fused_drop_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
+    "gaib_gat_backward_fused_drop_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop_win": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _i, _i, _vp, _vp]),
     "gaib_gat_backward_fused_drop_win": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _i, _i, _vp, _vp, _vp]),
     "gaib_edge_transpose_mh": (_i, [_vp, _vp, _i, _vp, _vp]),
@@ -894,6 +896,43 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gat_backward_fused_drop")
+        return True
+
+    def gat_forward_fused_drop_bf16(self, g, h, alpha_l, alpha_r, out, row_stats, rate: float, seed: int, scale=None,
+                                    eps: float = 0.2, heads: int = 1, relu: bool = False) -> bool:
+        """gat_forward_fused_drop over a torch.bfloat16 table h [nv, len]: the bits of the fp32 _drop call on the widened table
+        (with option gat_fused_wide also on rows wider than 128 columns).  False = not applicable"""
+        import torch
+
+        assert h.dtype == torch.bfloat16 and h.dim() == 2
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gat_forward_fused_drop_bf16(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(alpha_l), _ptr(alpha_r), eps,
+                                                       int(relu), rate, scale, seed, _ptr(out), _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_forward_fused_drop_bf16")
+        return True
+
+    def gat_backward_fused_drop_bf16(self, g, feat, grad, fwd_out, alpha_l, alpha_r, grad_out, lgrad, rgrad, row_stats, rate: float,
+                                     seed: int, scale=None, eps: float = 0.2, heads: int = 1) -> bool:
+        """gat_backward_fused_drop over torch.bfloat16 tables feat and grad [nv, len], through the masks of
+        gat_forward_fused_drop_bf16 with the same rate and seed.  False = not applicable (nothing touched)"""
+        import torch
+
+        assert feat.dtype == torch.bfloat16 and grad.dtype == torch.bfloat16 and feat.dim() == 2
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gat_backward_fused_drop_bf16(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out),
+                                                        _ptr(alpha_l), _ptr(alpha_r), _ptr(row_stats), eps, rate, scale, seed,
+                                                        _ptr(grad_out), _ptr(lgrad), _ptr(rgrad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gat_backward_fused_drop_bf16")
         return True
 
     def gat_forward_fused_drop_win(self, g, h, alpha_l, alpha_r, out, row_stats, rate: float, seed: int, mask_heads: int,

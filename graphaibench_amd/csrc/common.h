@@ -246,6 +246,15 @@ int gaib_gat_backward_fused_drop_wide(gaib_ctx* ctx, gaib_graph* g, int len, int
                                       const float* d_grad, const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
                                       const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
                                       float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
+// the slab loop over bf16 tables (gat_wide_bf16.hip): called by gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 after their
+// argument checks, as the fp32 calls call the two functions above (the _drop_bf16 calls live in that file and loop there)
+int gaib_gat_forward_fused_bf16_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const uint16_t* d_h_bf16,
+                                     const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float* d_out,
+                                     float* d_row_stats);
+int gaib_gat_backward_fused_bf16_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const uint16_t* d_feat_bf16,
+                                      const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_alpha_l,
+                                      const float* d_alpha_r, const float* d_row_stats, float epsilon, float* d_grad_out,
+                                      float* d_alpha_lgrad, float* d_alpha_rgrad);
 // an empty square graph of nv rows with rowptr [nv + 1] and colidx [ne] allocated, nothing filled (graph.hip)
 int gaib_graph_new(int64_t nv, int64_t ne, int device, gaib_graph** out);
 

@@ -5,6 +5,8 @@
 // are the bits of gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) on the widened tables, under the
 // same options.  A gathered row is 2 len bytes instead of 4 len: at 8 heads x 8 the backward sweep touches three 128-byte
 // lines per edge (h, grad, records) instead of five.
+// With option gat_fused_wide = 1 a multi-head row wider than 128 columns goes to the slab loop on bf16 tables (gat_wide_bf16.hip),
+// where the calls under attention dropout (gaib_gat_*_fused_drop_bf16) live too.
 #include "gat_kernels.h"
 
 static int gat_bf16_refuse(const char* who, int len, int heads) {
@@ -22,6 +24,13 @@ extern "C" int gaib_gat_forward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int len
   GAIB_CHECK(d_h_bf16 && d_alpha_l && d_alpha_r && d_out && d_row_stats && (const void*)d_out != (const void*)d_h_bf16,
              "%s: NULL or aliased pointer", who);
   GAIB_HIP(hipSetDevice(ctx->device));
+  // option gat_fused_wide: a multi-head row wider than 128 columns as S column slabs of the bf16 table (gat_wide_bf16.hip)
+  if (ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_forward_fused_bf16_wide(ctx, g, len, heads, w, S, d_h_bf16, d_alpha_l, d_alpha_r, epsilon, relu, d_out, d_row_stats);
+  }
   int rc = GAIB_OK;
   // the bf16 table: 8-byte aligned (a lane's four columns are one 8-byte load); the fp32 buffers 16 bytes as in the fp32 call
   const uintptr_t align_or = ((uintptr_t)d_h_bf16 & 7 ? 15 : 0) | (uintptr_t)d_out | (uintptr_t)d_row_stats |
@@ -81,6 +90,13 @@ extern "C" int gaib_gat_backward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int le
   GAIB_CHECK((const void*)d_grad_out != (const void*)d_feat_bf16 && (const void*)d_grad_out != (const void*)d_grad_bf16,
              "%s: d_grad_out must not alias an input", who);
   GAIB_HIP(hipSetDevice(ctx->device));
+  if (ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {  // (see the forward)
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if (S >= 2)
+      return gaib_gat_backward_fused_bf16_wide(ctx, g, len, heads, w, S, d_feat_bf16, d_grad_bf16, d_fwd_out, d_alpha_l, d_alpha_r,
+                                               d_row_stats, epsilon, d_grad_out, d_alpha_lgrad, d_alpha_rgrad);
+  }
   int rc0 = GAIB_OK;
   const uintptr_t align_or = ((((uintptr_t)d_feat_bf16 | (uintptr_t)d_grad_bf16) & 7) ? 15 : 0) | (uintptr_t)d_row_stats |
                              (uintptr_t)d_grad_out;

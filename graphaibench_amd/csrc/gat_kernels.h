@@ -3,7 +3,7 @@
 // shape rules and dispatch macros of their callers.  gat.hip instantiates them on fp32 tables, gat_bf16.hip on bf16 tables
 // (element type E = uint16_t: raw bf16 bits, loaded as they are and widened where they are consumed), gat_drop.hip the DROP
 // variants of the two sweeps (attention dropout, fp32 tables), gat_wide.hip the WIDE variants (rows of a table whose row stride is
-// not the row width: one column slab of a wider multi-head row).
+// not the row width: one column slab of a wider multi-head row), gat_wide_bf16.hip the DROP / WIDE / WIN variants on bf16 tables.
 // WIDE: a template flag with trailing, defaulted stride arguments read only behind `WIDE ? ld : len` -- the other instantiations
 // compile to the instructions they had (the arguments sit behind every argument those read).
 // WIN (gat_wide.hip, the dropped sweeps on a slab): the dropout mask's index takes the FULL row's head count and the slab's first

@@ -833,6 +833,18 @@ static void no_gat_bf16_partition() {
   exit(EXIT_FAILURE);
 }
 
+// h as bf16 bits in the aggregator's own buffer (kept for backward), grown on demand
+const uint16_t* GAT_Aggregator::cast_hb16(size_t elems, const float* in) {
+  if (elems > hb16_elems) {
+    if (d_hb16) GAIB_OR_DIE(gaib_free(C(), d_hb16));
+    d_hb16 = NULL;
+    GAIB_OR_DIE(gaib_malloc(C(), elems * sizeof(uint16_t), (void**)&d_hb16));
+    hb16_elems = elems;
+  }
+  GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)elems, in, d_hb16));
+  return d_hb16;
+}
+
 void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   count_edges(g);
   if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
@@ -861,13 +873,23 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   if (drop_sweep) {
     // attention dropout inside the sweep (option gat_fused_drop): the masks of the staged path's next seed, no edge array
     OpTimer t(OP_SPARSEMM);
-    const int rc = gaib_gat_forward_fused_drop(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0,
-                                               attn_drop, attn_scale, drop_seed, out, d_row_stats);
+    // bf16 tables (option gat_bf16): the sweep gathers the aggregator's own bf16 copy of h; where that call does not apply the
+    // fp32 sweep runs under the same seed, which advances once either way
+    bool on_bf16 = false;
+    int rc = GAIB_ERR_UNSUPPORTED;
+    if (gat_bf16_tables()) {
+      rc = gaib_gat_forward_fused_drop_bf16(C(), dev(g), len, heads, cast_hb16((size_t)g.size() * len, in), d_alpha_l, d_alpha_r,
+                                            epsilon, fuse_relu ? 1 : 0, attn_drop, attn_scale, drop_seed, out, d_row_stats);
+      on_bf16 = rc == GAIB_OK;
+    }
+    if (rc == GAIB_ERR_UNSUPPORTED)
+      rc = gaib_gat_forward_fused_drop(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0, attn_drop,
+                                       attn_scale, drop_seed, out, d_row_stats);
     if (rc == GAIB_OK) {
       drop_seed_last = drop_seed++;
       drop_fused_last = drop_sweep_ran = true;
       fuse_relu = false;
-      fwd_bf16 = false;
+      fwd_bf16 = on_bf16;
       stats_valid = true;  // (the statistics are the undropped softmax's: materialise_scores() serves them as ever)
       last_graph = &g;
       last_in = in;
@@ -881,16 +903,8 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     fwd_bf16 = false;
     int rc = GAIB_ERR_UNSUPPORTED;
     if (gat_bf16_tables()) {
-      const size_t elems = (size_t)g.size() * len;
-      if (elems > hb16_elems) {
-        if (d_hb16) GAIB_OR_DIE(gaib_free(C(), d_hb16));
-        d_hb16 = NULL;
-        GAIB_OR_DIE(gaib_malloc(C(), elems * sizeof(uint16_t), (void**)&d_hb16));
-        hb16_elems = elems;
-      }
-      GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)elems, in, d_hb16));
-      rc = gaib_gat_forward_fused_bf16(C(), dev(g), len, heads, d_hb16, d_alpha_l, d_alpha_r, epsilon, fuse_relu ? 1 : 0, out,
-                                       d_row_stats);
+      rc = gaib_gat_forward_fused_bf16(C(), dev(g), len, heads, cast_hb16((size_t)g.size() * len, in), d_alpha_l, d_alpha_r, epsilon,
+                                       fuse_relu ? 1 : 0, out, d_row_stats);
       fwd_bf16 = rc == GAIB_OK;
     }
     if (rc == GAIB_ERR_UNSUPPORTED)
@@ -944,8 +958,14 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
         float_malloc_device64(need, d_tbuf);
         tbuf_floats = need;
       }
-      rc = gaib_gat_backward_fused_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
-                                        epsilon, attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad, d_alpha_rgrad);
+      // bf16 tables: the kept copy of h is reused, one cast (of grad_in) is made (the guard above is the bf16 call's own)
+      if (fwd_bf16)
+        rc = gaib_gat_backward_fused_drop_bf16(C(), dev(g), len, heads, d_hb16, to_bf16(g.size(), len, grad_in), fwd_out, d_alpha_l,
+                                               d_alpha_r, d_row_stats, epsilon, attn_drop, attn_scale, drop_seed_last, d_tbuf,
+                                               d_alpha_lgrad, d_alpha_rgrad);
+      if (rc == GAIB_ERR_UNSUPPORTED)
+        rc = gaib_gat_backward_fused_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
+                                          epsilon, attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad, d_alpha_rgrad);
       if (rc == GAIB_OK) {
         fwd_out = NULL;
         fwd_out_given = false;

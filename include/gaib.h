@@ -371,9 +371,9 @@ int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, con
  * "gat_chunk_xcd" is honoured, "gat_fused_unroll" = 8 where w == 64; "gat_bwd_pk" and "gat_interleave" are ignored (the chunk
  * kernel over the three separate tables runs, as in the _drop calls).  Profile: one record per call under "gat_fwd_fused" /
  * "gat_bwd_fused", the narrow byte formula at (w, Hs) times S (column ids count S times).
- * The _drop calls are covered too, see gaib_gat_forward_fused_drop_win below.  Not covered, today's behaviour at these shapes
- * whatever the option says: the _bf16 calls, the _rect calls, gaib_gat_score_signs, a single head wider than 128 columns, the
- * packed-math sweep. */
+ * The _drop calls are covered too, see gaib_gat_forward_fused_drop_win below, and so are the _bf16 and _drop_bf16 calls (see
+ * there).  Not covered, today's behaviour at these shapes whatever the option says: the _rect calls, gaib_gat_score_signs, a
+ * single head wider than 128 columns, the packed-math sweep. */
 int gaib_gat_fused_slabs(int len, int heads, int* width);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
@@ -391,7 +391,13 @@ int gaib_gat_fused_slabs(int len, int heads, int* width);
  * (forward: GAIB_ERR_UNSUPPORTED; backward: zero alpha gradients, GAIB_OK).  d_row_stats == NULL in backward is
  * GAIB_ERR_INVALID: there is no attention-array form.
  * Profile: the launches are timed under the fp32 calls' keys "gat_fwd_fused" / "gat_bwd_fused" with the fp32 byte formula, so
- * the achieved rate of such a row is a work rate in dense (fp32) bytes. */
+ * the achieved rate of such a row is a work rate in dense (fp32) bytes.
+ * WIDE ROWS: with option "gat_fused_wide" = 1 both calls also accept every shape where gaib_gat_fused_slabs(len, heads) gives
+ * S >= 2, under their other conditions, and run the slab loop of the fp32 wide calls on the bf16 tables: slab s gathers from
+ * column s * w of the tables with the row stride len (2 s w bytes: a multiple of 64, the 8-byte loads stay aligned).  Outputs:
+ * BIT-IDENTICAL to the wide gaib_gat_forward_fused / gaib_gat_backward_fused on the widened tables; "gat_chunk_xcd" is honoured,
+ * "gat_fused_unroll" = 8 where w == 64, "gat_bwd_pk" is ignored at these shapes (as by the fp32 wide calls); the profile record
+ * carries the wide byte formula.  With the option at 0 the calls answer at these shapes as they always did. */
 int gaib_gat_forward_fused_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_h_bf16,
                                 const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float* d_out,
                                 float* d_row_stats);
@@ -421,6 +427,24 @@ int gaib_gat_backward_fused_drop(gaib_ctx* ctx, gaib_graph* g, int len, int head
                                  const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
                                  const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
                                  float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
+/* The _drop calls over bf16 TABLES (layer-library options "gat_bf16" with "gat_fused_drop"): argument order of the _drop calls,
+ * the tables as in the _bf16 calls (raw bf16 bits, row-major [nv][len], 8-byte aligned); records, statistics, alpha vectors and
+ * all outputs are fp32.  Every output is BIT-IDENTICAL to gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop on the
+ * tables widened to fp32 under the same options and the same (drop_rate, scale, seed): the masks are those gaib_dropout draws
+ * over [ne][heads], d_row_stats does not see the mask, drop_rate = 0 with scale = 1 gives the bits of the undropped _bf16 calls.
+ * Cover and refusals are those of the _drop calls (square graphs, a buildable reverse-edge permutation asked for by forward and
+ * backward alike, "gat_fused_fwd" / "gat_fused_bwd" = 0 or a misaligned buffer -> GAIB_ERR_UNSUPPORTED with nothing touched;
+ * d_row_stats == NULL, drop_rate outside [0, 1), an aliased output -> GAIB_ERR_INVALID; a graph without rows as there), and with
+ * option "gat_fused_wide" = 1 the shapes with S >= 2 slabs are accepted as by the _drop calls, each slab with its head window
+ * (heads, s * Hs) of the mask.  "gat_chunk_xcd" and "gat_fused_unroll" are honoured, "gat_bwd_pk" and "gat_interleave" ignored.
+ * Profile: keys and byte formulas of the corresponding fp32 _drop call. */
+int gaib_gat_forward_fused_drop_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_h_bf16,
+                                     const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float drop_rate,
+                                     float scale, uint64_t seed, float* d_out, float* d_row_stats);
+int gaib_gat_backward_fused_drop_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_feat_bf16,
+                                      const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_alpha_l,
+                                      const float* d_alpha_r, const float* d_row_stats, float epsilon, float drop_rate, float scale,
+                                      uint64_t seed, float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
 /* ATTENTION DROPOUT THROUGH A HEAD WINDOW OF THE MASK, and the _drop calls on rows wider than 128 columns.
  * The _win calls are the _drop calls at the same narrow shapes (len 32 / 64 / 128, contiguous tables [nv][len]) whose `heads`
  * heads are heads [mask_head0, mask_head0 + heads) of a row of mask_heads heads: the mask of (edge e, local head k) is the one
@@ -919,15 +943,16 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * gaib_sgemm_ex on the fp32 rows; "gemm_bf16_kernel" (default 1): 0 = gaib_gemm_bf16 refuses every call (GAIB_ERR_UNSUPPORTED),
  * gaib_gemm_bf16_cover says 0;
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
- * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs, no
- * attention dropout); a partitioned GAT graph refuses the option;
+ * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs), and
+ * gaib_gat_forward_fused_drop_bf16 / gaib_gat_backward_fused_drop_bf16 where attention dropout stays in the sweep ("gat_fused_drop"
+ * = 1); staged attention dropout runs on the fp32 tables; a partitioned GAT graph refuses the option;
  * "gat_fused_drop" (default 0; readable): 1 = the layer library's GAT aggregation, on a whole graph in the training phase with
  * attention dropout, runs gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop instead of the staged kernels and holds
  * neither the mask nor the dropped-attention array; the masks are those of the staged path, seed for seed; partitioned graphs
- * stay staged and bf16 tables ("gat_bf16") are not used under dropout;
+ * stay staged; with "gat_bf16" = 1 the _drop_bf16 calls run first;
  * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head
  * rows wider than 128 columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); the layer library keeps attention
- * dropout in the sweep there only with "gat_fused_drop" = 1 as well; bf16 tables and partitions stay as they are at these widths;
+ * dropout in the sweep there only with "gat_fused_drop" = 1 as well; the _bf16 / _drop_bf16 calls ("gat_bf16") run the same slabs; partitions stay as they are;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused

@@ -169,7 +169,9 @@ class GAT_Aggregator : public aggregator {
   int last_len;
   void materialise_scores();
   // extension: bf16 tables (context option "gat_bf16" = 1, or GAIB_GAT_DTYPE=bf16).  On a whole graph, without attention
-  // dropout and at a shape the one-sweep kernels cover, aggregate() casts `in` into d_hb16 and runs
+  // dropout or with it kept in the sweep (gat_fused_drop: the _drop_bf16 calls under the same seeds, the fp32 _drop calls where
+  // those do not apply), at a shape the one-sweep kernels cover (with gat_fused_wide also rows wider than 128 columns),
+  // aggregate() casts `in` into d_hb16 and runs
   // gaib_gat_forward_fused_bf16; d_aggregate() then casts grad_in (process-wide scratch) and runs
   // gaib_gat_backward_fused_bf16 on the KEPT copy of h -- when that forward ran on bf16, the layer's forward output is at
   // hand and feat_in is the table that forward cast; in every other case the fp32 path runs as without the option.  The
@@ -179,6 +181,7 @@ class GAT_Aggregator : public aggregator {
   // attention array from the fp32 `in`, like the staged path it serves: within the bf16 rounding of what the sweep used.)
   static bool gat_bf16_tables();
   uint16_t* d_hb16 = NULL;
+  const uint16_t* cast_hb16(size_t elems, const float* in);
   size_t hb16_elems = 0;
   bool fwd_bf16 = false;  // the last forward ran on d_hb16 = bf16(last_in) over last_graph
   // extension: attention dropout inside the one sweep (context option "gat_fused_drop" = 1, or GAIB_GAT_FUSED_DROP=1).  On a

@@ -18,7 +18,12 @@ A shape whose child fails or runs into its time limit ends the run: no further c
 option 1 is gat_fused_wide = gat_fused_drop = 1: gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop per column slab, and
 the layer with score_drop = RATE.
 
-    python scripts/gat_wide.py OUT.json [--iters 20] [--shapes 256x8,512x8] [--timeout 600] [--drop 0.3]
+--dtype bf16: the one-sweep path on bf16 tables against the same path on fp32 tables (option gat_bf16 0 / 1), with
+gat_fused_wide = 1 in every leg and, under --drop RATE, gat_fused_drop = 1 as well -- no staged leg.  Per shape, interleaved in the
+child: the forward and backward calls on fp32 and on bf16 tables, the two casts (h in forward, grad in backward), the layer step
+with gat_bf16 0 and 1, and the device bytes each setting's layer holds after its first step.
+
+    python scripts/gat_wide.py OUT.json [--iters 20] [--shapes 256x8,512x8] [--timeout 600] [--drop 0.3] [--dtype bf16]
 """
 import argparse
 import json
@@ -163,6 +168,126 @@ def child(shape, iters, out_path, drop=0.0):
     print(json.dumps(r), flush=True)
 
 
+def child_bf16(shape, iters, out_path, drop=0.0):
+    """--dtype bf16: gat_bf16 0 against 1, both on the one-sweep path (gat_fused_wide = 1; under dropout gat_fused_drop = 1)"""
+    import torch
+
+    from bf16_gat import time_legs
+    from graphaibench_amd import capi, layers as L, synth
+
+    ctx = L.init(0)
+    sg = synth.make("reddit", seed=7, device="cuda")
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    nv, ne = g.nv, g.ne
+    rp, ci = g.rowptr(), g.colidx()
+    D, H = (int(v) for v in shape.split("x"))
+    w, S = capi.gat_fused_slabs(D, H)
+    assert S >= 2, (D, H, w, S)
+    r = dict(len=D, heads=H, slab_width=w, slabs=S, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    if drop > 0:
+        r["rate"] = drop
+    ctx.set_option("gat_fused_wide", 1)
+    ctx.set_option("gat_fused_drop", 1 if drop > 0 else 0)
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    h = torch.randn(nv, D, device="cuda", generator=gen)
+    grad = torch.randn(nv, D, device="cuda", generator=gen)
+    al = torch.randn(D, device="cuda", generator=gen) * 0.2
+    ar = torch.randn(D, device="cuda", generator=gen) * 0.2
+    hb, gb = ctx.cast_f32_bf16(h), ctx.cast_f32_bf16(grad)
+    hw, gw = ctx.cast_bf16_f32(hb), ctx.cast_bf16_f32(gb)
+    out, stats = torch.empty(nv, D, device="cuda"), torch.empty(nv, H, 2, device="cuda")
+    go, lg, rg = torch.empty(nv, D, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
+    cast_out = torch.empty(nv, D, dtype=torch.bfloat16, device="cuda")
+
+    def fwd32():
+        if drop > 0:
+            assert ctx.gat_forward_fused_drop(g, hw, al, ar, out, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_forward_fused(g, hw, al, ar, out, stats, heads=H)
+
+    def fwd16():
+        if drop > 0:
+            assert ctx.gat_forward_fused_drop_bf16(g, hb, al, ar, out, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_forward_fused_bf16(g, hb, al, ar, out, stats, heads=H)
+
+    fwd32()
+    fwd = out.clone()
+
+    def bwd32():
+        if drop > 0:
+            assert ctx.gat_backward_fused_drop(g, hw, gw, fwd, al, ar, go, lg, rg, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_backward_fused(g, hw, gw, fwd, al, ar, None, go, lg, rg, heads=H, row_stats=stats)
+
+    def bwd16():
+        if drop > 0:
+            assert ctx.gat_backward_fused_drop_bf16(g, hb, gb, fwd, al, ar, go, lg, rg, stats, drop, SEED, heads=H)
+        else:
+            assert ctx.gat_backward_fused_bf16(g, hb, gb, fwd, al, ar, go, lg, rg, stats, heads=H)
+
+    r["calls"] = time_legs({"fwd_fp32": fwd32, "fwd_bf16": fwd16, "bwd_fp32": bwd32, "bwd_bf16": bwd16,
+                            "cast_h": lambda: ctx.cast_f32_bf16(h, cast_out), "cast_grad": lambda: ctx.cast_f32_bf16(grad, cast_out)},
+                           iters)
+    del out, go, fwd, hb, gb, hw, gw, cast_out
+    g.close()
+    torch.cuda.empty_cache()
+
+    def free_bytes():
+        L.sync()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    lout, lgo = torch.empty(nv, D, device="cuda"), torch.empty(nv, D, device="cuda")
+
+    def make_layer(on):
+        """(layer, its graph, bytes it holds after one training step)"""
+        ctx.set_option("gat_bf16", on)
+        before = free_bytes()
+        lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True, score_drop=drop)
+        ld.set_heads(H)
+        ld.write(L.FEAT_IN, h)
+        ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
+        ld.set_phase(0)
+        ld.forward(lout)
+        ld.backward(lout, lgo)
+        return ld, lg_graph, before - free_bytes()
+
+    def step(ld, on):
+        def run():
+            ctx.set_option("gat_bf16", on)
+            ld.forward(lout)
+            ld.backward(lout, lgo)
+        return run
+
+    # a throw-away layer first: the workspace, the process-wide bf16 scratch and the allocator's caches reach their size
+    ld, lgr, _ = make_layer(1)
+    ld.close()
+    lgr.close()
+    r["held_bytes"] = {}
+    for on in (0, 1):
+        ld, lgr, held = make_layer(on)
+        r["held_bytes"][f"gat_bf16_{on}"] = held
+        ld.close()
+        lgr.close()
+    r["hb16_bytes"] = nv * D * 2
+    l0, g0_, _ = make_layer(0)
+    l1, g1_, _ = make_layer(1)
+    r["layer_step"] = time_legs({"gat_bf16_0": step(l0, 0), "gat_bf16_1": step(l1, 1)}, iters)
+    for key in ("gat_bf16", "gat_fused_wide", "gat_fused_drop"):
+        ctx.set_option(key, 0)
+    for x in (l0, l1):
+        x.close()
+    for x in (g0_, g1_):
+        x.close()
+    r["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    Path(out_path).write_text(json.dumps(r) + "\n")
+    print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
@@ -170,22 +295,28 @@ def main():
     ap.add_argument("--shapes", default="256x8,512x8")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
     ap.add_argument("--drop", type=float, default=0.0, help="attention dropout rate: the legs under dropout, both options 0 against both 1")
+    ap.add_argument("--dtype", default="fp32", choices=("fp32", "bf16"),
+                    help="bf16: the one-sweep path with gat_bf16 0 against 1 instead of the staged path against the one sweep")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     assert 0.0 <= args.drop < 1.0, args.drop
     if args.child:
-        child(args.child, args.iters, args.out, args.drop)
+        (child_bf16 if args.dtype == "bf16" else child)(args.child, args.iters, args.out, args.drop)
         return
     what = "GAT rows wider than 128 columns: one-sweep kernels per column slab (gat_fused_wide = 1) against the staged path (0, the baseline)"
     if args.drop > 0:
         what = (f"GAT rows wider than 128 columns under attention dropout {args.drop}: one-sweep kernels per column slab with the mask "
                 "formed in the sweep (gat_fused_wide = gat_fused_drop = 1) against the staged path (both 0, the baseline)")
+    if args.dtype == "bf16":
+        what = ("GAT rows wider than 128 columns, one-sweep kernels per column slab (gat_fused_wide = 1"
+                + (f", attention dropout {args.drop} formed in the sweep: gat_fused_drop = 1" if args.drop > 0 else "")
+                + "): bf16 tables (gat_bf16 = 1) against fp32 tables (0, the baseline)")
     rec = dict(what=what, graph="reddit synth (seed 7) + self loops", shapes=[])
     with tempfile.TemporaryDirectory() as tmp:
         for shape in args.shapes.split(","):
             part = Path(tmp) / f"{shape}.json"
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
-                   "--iters", str(args.iters), "--drop", str(args.drop)]
+                   "--iters", str(args.iters), "--drop", str(args.drop), "--dtype", args.dtype]
             rc = subprocess.run(cmd).returncode
             if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
                 rec["stopped"] = dict(shape=shape, exit_status=rc)
