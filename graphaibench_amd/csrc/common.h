@@ -46,6 +46,12 @@ void gaib_set_error(const char* fmt, ...);
 
 
 #define GAIB_FLAT_RING_DEFAULT 1  // spmm_flat_ring's default (see spmm_kernels.h RING)
+// What spmm_hot_cold = -1 (auto) resolves to where its rule holds (spmm.hip: hot_cold_cols), measured on the benchmark's graph
+// (LEDGER 15): a DENSE fp32 table gathers 0.21 ms per launch faster with a 128 MB hot set (8.81 -> 8.60 ms; slower below 96 MB),
+// a zero-suppressed table 0.7-1.3 ms SLOWER at every size -- so auto is on for dense tables only; the packed launches take the
+// hot/cold form when the option is set to 1.
+#define GAIB_HOT_COLD_AUTO 1
+#define GAIB_HOT_COLD_BYTES_DEFAULT ((int64_t)128 << 20)
 #define GAIB_BF16_FUSE_U 32       // gathers in flight per wave in the row forms of the bf16 fused aggregation (launch_fused)
 
 struct gaib_ctx {
@@ -85,7 +91,10 @@ struct gaib_ctx {
   int spmm_unroll;           // 0 = auto, 8 = cap gathers in flight per wave at 8
   int spmm_addr_mode;        // 0 = auto (buffer loads when the table is < 4 GB), 2 = force 64-bit global
   int spmm_gather_mode;      // 0/1 default cache policy, 2 = nt gathers, 3 = nt for cold columns only
-  int spmm_hot_bytes;        // L2 budget for the hot rows of gather mode 3
+  int spmm_hot_bytes;        // L2 budget for the hot rows of gather mode 3 (counted in 512-B rows: gaib_hot_rows_wanted)
+  int spmm_hot_cold;         // hot/cold gathers in the fused, heavy and packed launches of gaib_spmm_gemm(_zs): -1 = auto (dense fp32 tables under the rule of spmm.hip's hot_cold_cols), 0 = off, 1 = on wherever the form exists, packed tables included
+  int64_t spmm_hot_cold_bytes;  // Infinity Cache budget for their hot rows (counted in 512-B rows)
+  int64_t spmm_hot_cold_launches;  // read-only: fused launches so far that took the hot/cold form (a recorded one counts when it is recorded)
   int spmm_bf16_layout;      // gaib_spmm_bf16's lane layout: 0 = one row per wave (auto lane width), 4 / 8 = sub-wave rows of 4 / 8 elements per lane
   int spmm_bf16_fuse_u;      // benchmark only: gathers in flight of the bf16 fused kernel's headline variant, 0 = default (GAIB_BF16_FUSE_U), 16 / 32
   int spmm_bf16_pad;         // 1 = gaib_bf16_row_stride line-aligns odd-width bf16 rows where that saves >10 % of the gathered lines, 0 = never
@@ -225,7 +234,14 @@ int gaib_graph_ensure_w_mean_t(gaib_ctx* ctx, gaib_graph* g);
 int gaib_graph_ensure_rev(gaib_ctx* ctx, gaib_graph* g);
 int gaib_graph_ensure_heavy(gaib_ctx* ctx, gaib_graph* g, int thr);
 int gaib_graph_ensure_chunks(gaib_ctx* ctx, gaib_graph* g);
-int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int len);
+int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int64_t hot_rows);
+// the size of the graph's hot set in rows: the bytes of the option in force over 512, the row of a 128-column fp32 table -- the
+// same set for tables of every width (a packed 128-column table's hot set is 3/4 of the bytes)
+static inline int64_t gaib_hot_rows_wanted(const gaib_ctx* ctx, const gaib_graph* g) {
+  int64_t r = (ctx->spmm_gather_mode == 3 ? (int64_t)ctx->spmm_hot_bytes : ctx->spmm_hot_cold_bytes) / 512;
+  if (r > g->nv) r = g->nv;
+  return r < 1 ? 1 : r;
+}
 int gaib_graph_ensure_induce(gaib_ctx* ctx, gaib_graph* g);
 // the one-sweep GAT on S = len / w column slabs of w columns and heads / S heads (gat_wide.hip; option gat_fused_wide): called by
 // gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) after their argument checks, with (w, S) of

@@ -551,9 +551,13 @@ int gaib_graph_ensure_heavy(gaib_ctx* ctx, gaib_graph* g, int thr) {
   return GAIB_OK;
 }
 
-// gather mode 3: flag cold columns.  The hot set is the highest-degree vertices whose feature rows
-// fit `spmm_hot_bytes` (default 3 MB of the 4 MB per-XCD L2); everything else is gathered with the
-// streaming (nt) policy so it does not push the hub rows out.
+// Hot/cold gathers (spmm_gather_mode 3 in the row kernels, spmm_hot_cold in the fused, heavy and packed launches): flag cold
+// columns.  The hot set is the `hot_rows` highest-degree vertices; every other column id carries bit 31 and is gathered with
+// the streaming (nt) policy, so it does not push the hot rows out of the cache.  The set is counted in ROWS of the graph
+// (gaib_hot_rows_wanted: the option's bytes over 512, the row of a 128-column fp32 table), not in bytes of the table at hand: ONE
+// flagged array per graph, built once and shared by aggregations of every width -- a model whose layers alternate widths used to
+// rebuild it on every call (a copy of rowptr to the host, an nth_element and a stream sync each time).  It is rebuilt only
+// when the option that sizes it changes.
 __global__ void flag_cold_kernel(int64_t ne, const uint32_t* col, const int64_t* rowptr, int64_t thr,
                                  uint32_t* out) {
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -563,18 +567,18 @@ __global__ void flag_cold_kernel(int64_t ne, const uint32_t* col, const int64_t*
   out[e] = deg >= thr ? c : (c | 0x80000000u);
 }
 
-int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int len) {
-  int64_t hot_rows = (int64_t)ctx->spmm_hot_bytes / ((int64_t)len * 4);
+int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int64_t hot_rows) {
   if (hot_rows < 1) hot_rows = 1;
   if (hot_rows > g->nv) hot_rows = g->nv;
-  // threshold = degree of the hot_rows-th highest-degree vertex
   if (g->colidx_flagged && g->hot_rows == hot_rows) return GAIB_OK;
+  GAIB_CHECK(g->nc == g->nv && g->nv >= 1, "hot-column flags: a square graph (a column's degree is read from its row)");
   GAIB_NOT_WHILE_CAPTURING(ctx, "building the graph's hot-column flags");
   std::vector<int64_t> rp((size_t)g->nv + 1);
   GAIB_HIP(hipMemcpyAsync(rp.data(), g->rowptr, sizeof(int64_t) * (g->nv + 1), hipMemcpyDeviceToHost, ctx->stream));
   GAIB_HIP(hipStreamSynchronize(ctx->stream));
   std::vector<int64_t> deg((size_t)g->nv);
   for (int64_t v = 0; v < g->nv; ++v) deg[v] = rp[v + 1] - rp[v];
+  // threshold = degree of the hot_rows-th highest-degree vertex
   std::nth_element(deg.begin(), deg.begin() + (hot_rows - 1), deg.end(), std::greater<int64_t>());
   const int64_t thr = deg[hot_rows - 1];
   if (!g->colidx_flagged) {
@@ -582,6 +586,7 @@ int gaib_graph_ensure_hot_flags(gaib_ctx* ctx, gaib_graph* g, int len) {
     g->dev_bytes += sizeof(uint32_t) * g->ne;
   }
   if (g->ne > 0) {
+    ProfScope ps(ctx, "flag_cold", 16.0 * (double)g->ne);
     flag_cold_kernel<<<grid1d(g->ne, 256), 256, 0, ctx->stream>>>(g->ne, g->colidx, g->rowptr, thr, g->colidx_flagged);
     GAIB_LAUNCH_CHECK();
   }
@@ -977,12 +982,14 @@ extern "C" int gaib_graph_sort_rows(gaib_ctx* ctx, gaib_graph* g) {
   // everything laid out per edge follows the old order
   void** per_edge[] = {(void**)&g->edata, (void**)&g->w_gcn, (void**)&g->w_mean_t, (void**)&g->rev, (void**)&g->chunk_row,
                        (void**)&g->chunk_ebase, (void**)&g->chunk_start, (void**)&g->colidx_flagged};
+  if (g->colidx_flagged) g->dev_bytes -= sizeof(uint32_t) * g->ne;  // (counted where it is allocated: gaib_graph_ensure_hot_flags)
   for (void** p : per_edge) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   g->n_chunks = 0;
   g->hot_threshold = -1;
+  g->hot_rows = 0;
   g->near_frac = -1.f;
   g->rows_unsorted = 0;
   return GAIB_OK;

@@ -64,6 +64,12 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_addr_mode = 0;
   c->spmm_gather_mode = 0;
   c->spmm_hot_bytes = 3 << 20;
+  c->spmm_hot_cold = -1;
+  c->spmm_hot_cold_bytes = GAIB_HOT_COLD_BYTES_DEFAULT;
+  c->spmm_hot_cold_launches = 0;
+  // (A/B of a whole benchmark or trainer run, as GAIB_SGEMM_VARIANT below: the option and its hot set in MB from the environment)
+  if (const char* e = getenv("GAIB_SPMM_HOT_COLD")) c->spmm_hot_cold = atoi(e) > 0 ? 1 : (atoi(e) < 0 ? -1 : 0);
+  if (const char* e = getenv("GAIB_SPMM_HOT_COLD_MB")) c->spmm_hot_cold_bytes = (int64_t)std::max(0, atoi(e)) << 20;
   c->spmm_bf16_layout = 0;
   c->spmm_bf16_fuse_u = 0;
   c->spmm_bf16_pad = 1;
@@ -545,6 +551,9 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "agg_zs_wide")) *h_value = ctx->agg_zs_wide;
   else if (!strcmp(key, "agg_zs_paused")) *h_value = ctx->agg_zs_paused;
   else if (!strcmp(key, "spmm_bf16_layout")) *h_value = ctx->spmm_bf16_layout;
+  else if (!strcmp(key, "spmm_hot_cold")) *h_value = ctx->spmm_hot_cold;
+  else if (!strcmp(key, "spmm_hot_cold_bytes")) *h_value = ctx->spmm_hot_cold_bytes;
+  else if (!strcmp(key, "spmm_hot_cold_launches")) *h_value = ctx->spmm_hot_cold_launches;
   else if (!strcmp(key, "spmm_bf16_fuse_u")) *h_value = ctx->spmm_bf16_fuse_u;
   else if (!strcmp(key, "spmm_bf16_pad")) *h_value = ctx->spmm_bf16_pad;
   else if (!strcmp(key, "agg_bf16_ld_last")) *h_value = ctx->agg_bf16_ld_last;
@@ -588,7 +597,13 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
     ctx->spmm_gather_mode = (int)value;
   else if (!strcmp(key, "spmm_hot_bytes"))
     ctx->spmm_hot_bytes = (int)value;
-  else if (!strcmp(key, "spmm_bf16_layout")) {
+  else if (!strcmp(key, "spmm_hot_cold")) {
+    GAIB_CHECK(value >= -1 && value <= 1, "spmm_hot_cold must be -1 (auto), 0 (off) or 1 (on)");
+    ctx->spmm_hot_cold = (int)value;
+  } else if (!strcmp(key, "spmm_hot_cold_bytes")) {
+    GAIB_CHECK(value >= 0 && value <= ((int64_t)1 << 40), "spmm_hot_cold_bytes out of range");
+    ctx->spmm_hot_cold_bytes = value;
+  } else if (!strcmp(key, "spmm_bf16_layout")) {
     GAIB_CHECK(value == 0 || value == 4 || value == 8, "spmm_bf16_layout must be 0, 4 or 8");
     ctx->spmm_bf16_layout = (int)value;
   } else if (!strcmp(key, "spmm_bf16_fuse_u")) {

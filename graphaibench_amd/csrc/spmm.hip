@@ -288,9 +288,12 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   a.n_first = d_in2 ? (uint32_t)n_first : 0xffffffffu;
   a.in2_bytes = 0;
   a.col0 = 0;
+  // gather mode 3 (the row kernels of gaib_spmm): the graph's flagged column ids.  Never built inside a capture: a recorded call
+  // whose flags do not exist yet gathers with the default policy.
   if (!part && !bf16 && ctx->spmm_gather_mode == 3 && g->nc == g->nv && !g->col_vdata) {
-    GAIB_TRY(gaib_graph_ensure_hot_flags(ctx, g, len));
-    a.col_flagged = g->colidx_flagged;
+    const int64_t want = gaib_hot_rows_wanted(ctx, g);
+    if (!ctx->capturing) GAIB_TRY(gaib_graph_ensure_hot_flags(ctx, g, want));
+    if (g->colidx_flagged && g->hot_rows == want) a.col_flagged = g->colidx_flagged;
   }
   a.ldo = len;
   // odd-width tables: gathered from a copy re-strided to whole 64-B pieces where that saves lines (pad_stride_floats)
@@ -357,6 +360,31 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
 static bool chunk_rule(gaib_ctx* ctx, gaib_graph* g, int64_t ld) {
   if (gaib_graph_ensure_heavy(ctx, g, ctx->spmm_heavy_threshold) != GAIB_OK) return false;
   return g->nc * ld * 4 <= ((int64_t)512 << 20) && 4 * g->heavy_edges >= g->ne && g->ne > 0;
+}
+
+// Option spmm_hot_cold for the fused, heavy and packed launches of gaib_spmm_gemm / gaib_spmm_gemm_zs: the graph's flagged
+// column ids when the option resolves to on for this call, else NULL (the launch then reads the plain ids, default policy).
+//   1  on wherever the hot/cold form exists: a square graph without column normalisers (a column's degree is its row's), whole
+//      (no row classes), an fp32 or zero-suppressed table of 65 .. 128 columns; launch_fused keeps the form's own conditions
+//  -1  auto: GAIB_HOT_COLD_AUTO (common.h: what the measurement decided), a DENSE table (the packed gather measured slower
+//      with the option at every hot-set size), larger than twice the 256 MiB Infinity Cache -- a table that fits is resident
+//      whatever the policy -- and a numbering that is not local (near_frac < 0.25)
+//   0  off
+// The flags are per-graph preprocessing, built next to the heavy-row list on the first call outside a capture; inside a
+// capture nothing is built: without current flags the call runs with the default policy.
+static const uint32_t* hot_cold_cols(gaib_ctx* ctx, gaib_graph* g, int len_in, int len_out, int64_t table_bytes, bool packed) {
+  if (ctx->spmm_hot_cold == 0 || ctx->spmm_gather_mode == 3) return nullptr;  // (gather mode 3 sizes the one flagged array for the L2)
+  if (g->row_map || g->nc != g->nv || g->col_vdata || len_in <= 64 || len_in > 128 || g->ne == 0) return nullptr;
+  // launch_fused's own predicates for the forms without a hot/cold gather (2-row strip, edge stream): nothing is built for them
+  if (fuse_strip_rows(128, len_out, false) != 8 || ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv)) return nullptr;
+  if (ctx->spmm_hot_cold < 0) {
+    if (!GAIB_HOT_COLD_AUTO || packed || table_bytes <= ((int64_t)512 << 20)) return nullptr;
+    if (g->near_frac < 0.f && (ctx->capturing || gaib_graph_ensure_locality(ctx, g) != GAIB_OK)) return nullptr;
+    if (g->near_frac >= 0.25f) return nullptr;
+  }
+  const int64_t want = gaib_hot_rows_wanted(ctx, g);
+  if (!ctx->capturing && gaib_graph_ensure_hot_flags(ctx, g, want) != GAIB_OK) return nullptr;
+  return (g->colidx_flagged && g->hot_rows == want) ? g->colidx_flagged : nullptr;
 }
 
 // the row-class kernels (PART = true) live in a translation unit of their own: spmm_part.hip
@@ -554,6 +582,7 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
     SpmmArgs a0;
     int wmode = 0;
     GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode, nullptr, 0, bf16, ld_bf16));
+    a0.col_flagged = nullptr;  // (the K-slab forms have no hot/cold gather)
     const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;
     const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * len_in + 255) & ~(size_t)255;
     GAIB_TRY(gaib_ws_reserve(ctx, wt_bytes + hv_bytes + 256));
@@ -620,6 +649,9 @@ static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const f
   int wmode = 0;
   GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first, bf16, ld_bf16));
   a.accumulate = 0;  // (the fused kernel takes the partial sums through f.agg_in)
+  a.col_flagged = nullptr;  // (spmm_gather_mode 3 belongs to the row kernels of gaib_spmm)
+  if (!part && !bf16 && !dual)  // (two products: no hot/cold form, nothing to build)
+    a.col_flagged = hot_cold_cols(ctx, g, len_in, len_out, d_zs ? g->nc * (int64_t)GAIB_ZS_ROW_BYTES : g->nc * (int64_t)a.ld * 4, d_zs != nullptr);
   if (flags & GAIB_AGG_SCRATCH) a.out = nullptr;  // the caller does not read agg: skip its store
   // scratch: op(W) (and op(W2)) k-contiguous + the heavy rows' aggregates + the tile counter
   const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;

@@ -173,7 +173,10 @@ template <> struct ZsTraits<zs_wide_t> { static constexpr bool zs = true; static
 // Needs the table to be < 4 GB; larger tables use 64-bit global_load addresses.
 // GM (gather mode): 0 = 64-bit global_load; 1 = buffer_load, default cache policy; 2 = buffer_load nt
 // (streaming) for every gather; 3 = buffer_load, nt only for COLD columns (top bit of the column id
-// set by gaib_graph_ensure_hot_flags), so the few thousand hub rows keep their place in the 4 MB L2.
+// set by gaib_graph_ensure_hot_flags), so the hot rows keep their place in the caches -- the 4 MB L2 for the unfused kernels'
+// 3 MB hot set (spmm_gather_mode 3), the Infinity Cache for the fused, heavy and packed launches' (spmm_hot_cold).  Every user of
+// a column id of such a kernel masks the bit first; on a zero-suppressed table the bit chooses the policy of the packed
+// three-line load and of an over-capacity row's dense load alike.
 // PART: two tables -- column ids below n_first index `in`, the others `in2` (a rank's own rows and its halo table, which
 // live in different allocations); the choice is a scalar select on the (wave-uniform) column id.  Both tables hold the same
 // element type: fp32, or bf16 (spmm_part_bf16.hip) -- ldb, the n_first bias of inb2 and both descriptors then count bf16 bytes.
@@ -187,7 +190,7 @@ struct RowGather {
   static constexpr bool BUF = GM != 0;
   static constexpr bool ZS = ZsTraits<E>::zs;
   static_assert(!PART || !ZS, "two-table gathers: fp32 or bf16 tables");
-  static_assert(!ZS || (VEC == 2 && GM == 1), "zero-suppressed tables: 8-byte lanes (128 columns), buffer addressing");
+  static_assert(!ZS || (VEC == 2 && (GM == 1 || GM == 3)), "zero-suppressed tables: 8-byte lanes (128 columns), buffer addressing");
   __amdgpu_buffer_rsrc_t rsrc, rsrc2;
   const char *inb, *inb2;  // inb2 is biased by -n_first rows: row base = inb2 + col * ldb
   int64_t ldb;
@@ -245,8 +248,12 @@ struct RowGather {
   // of every register and mask of the group, and a wait for the dense load left to the join would drain the gathers in flight.
   __device__ __forceinline__ typename VecT<VEC>::type zs_fix(const raw_t& p, zs_mask_t m0, zs_mask_t m1, uint32_t cvec, int idx, uint32_t voff) const {
     if (zs_over(zs_over_bits(m0, m1))) {
-      const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cvec, idx);
-      const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * ZsTraits<E>::dense_row_bytes), 0);
+      const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)cvec, idx);
+      const uint32_t cj = GM == 3 ? (cf & 0x7fffffffu) : cf;
+      u2_t d;
+      if (GM == 3 && (cf & 0x80000000u))  // (wave-uniform: a cold column's dense row does not allocate either)
+        d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * ZsTraits<E>::dense_row_bytes), 2);
+      else d = __builtin_amdgcn_raw_buffer_load_b64(rsrc2, (int)voff, (int)(cj * ZsTraits<E>::dense_row_bytes), 0);
       typename VecT<VEC>::type v;
       v[0] = __uint_as_float(d[0]);
       v[1] = __uint_as_float(d[1]);
@@ -278,16 +285,22 @@ struct RowGather {
         const char* rowp = (second ? inb2 : inb) + (int64_t)cj * ldb;
         return *reinterpret_cast<const raw_t*>(rowp + voff);  // (bf16: the packed words, as from the one-table gather)
       }
+    } else if constexpr (ZS) {
+      // lanes 48 .. 63 ask for offset 0 as out-of-range lanes do: exactly the row's three lines, whatever its header says
+      const int zoff = (int)(voff < (uint32_t)GAIB_ZS_ROW_BYTES ? voff : 0u);
+      if constexpr (GM == 3) {
+        const uint32_t c = cj & 0x7fffffffu;
+        if (cj & 0x80000000u) return __builtin_amdgcn_raw_buffer_load_b64(rsrc, zoff, (int)(c * (uint32_t)GAIB_ZS_ROW_BYTES), 2);  // wave-uniform
+        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, zoff, (int)(c * (uint32_t)GAIB_ZS_ROW_BYTES), 0);
+      } else {
+        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, zoff, (int)(cj * (uint32_t)GAIB_ZS_ROW_BYTES), 0);
+      }
     } else if constexpr (GM == 3) {
       const uint32_t c = cj & 0x7fffffffu;
       if (cj & 0x80000000u) return load_buf<2>(c, voff);  // wave-uniform branch (cj is scalar)
       return load_buf<0>(c, voff);
     } else if constexpr (GM == 2) {
       return load_buf<2>(cj, voff);
-    } else if constexpr (ZS) {
-      // lanes 48 .. 63 ask for offset 0 as out-of-range lanes do: exactly the row's three lines, whatever its header says
-      return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(voff < (uint32_t)GAIB_ZS_ROW_BYTES ? voff : 0u),
-                                                  (int)(cj * (uint32_t)GAIB_ZS_ROW_BYTES), 0);
     } else if constexpr (GM == 1) {
       return load_buf<0>(cj, voff);
     } else {

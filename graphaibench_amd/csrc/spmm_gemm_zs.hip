@@ -22,6 +22,11 @@ template <int WMODE>
 int launch_fused_zs(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
   constexpr int U = 16;
   constexpr int K = 128;
+  const bool dual = f.wt2 != nullptr;
+  // hot/cold gathers (option spmm_hot_cold; a.col_flagged set by spmm_gemm_impl): the one-product form and the heavy kernel next
+  // to it; two products read the plain ids with the default policy
+  const bool hot_cold = a.col_flagged && !dual;
+  if (hot_cold) a.col = a.col_flagged;
   if (g->n_heavy > 0) {
     SpmmArgs h = a;
     h.row_list = g->heavy_rows;
@@ -34,11 +39,11 @@ int launch_fused_zs(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, 
     // (bytes and flops are priced on the dense formula under the dense keys: a work rate in dense bytes)
     ProfScope ps(ctx, "spmm_heavy", gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
-    spmm_heavy_kernel<2, 1, WMODE, U, 1, false, zs_t><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    if (hot_cold) spmm_heavy_kernel<2, 1, WMODE, U, 3, false, zs_t><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    else spmm_heavy_kernel<2, 1, WMODE, U, 1, false, zs_t><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
   f.tile_xcd = 0;
-  const bool dual = f.wt2 != nullptr;
   const int strip = dual ? 2 : 8;  // (checked by spmm_gemm_impl)
   const size_t lds = fuse_lds_bytes(K, f.n_out, dual, strip);
   const int64_t ntiles = cdiv64(a.n_rows, FUSE_ROWS);
@@ -54,6 +59,11 @@ int launch_fused_zs(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, 
     auto kern = spmm_gemm_kernel<2, WMODE, U, 1, 2, true, false, false, false, false, false, false, zs_t>;
     GAIB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     kern<<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+  } else if (hot_cold) {
+    auto kern = spmm_gemm_kernel<2, WMODE, U, 3, 8, false, false, false, false, false, false, false, zs_t>;
+    GAIB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    kern<<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+    ctx->spmm_hot_cold_launches++;
   } else {
     auto kern = spmm_gemm_kernel<2, WMODE, U, 1, 8, false, false, false, false, false, false, false, zs_t>;
     GAIB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

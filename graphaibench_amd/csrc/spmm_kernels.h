@@ -902,6 +902,20 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   constexpr int K = 64 * VEC;
   // buffer loads need every table below 4 GB
   const bool buf = a.in_bytes != 0 && ctx->spmm_addr_mode != 2 && (!PART || !a.in2 || a.in2_bytes != 0);
+  if constexpr (PART || BF) f.tile_xcd = 0;
+  const bool dual = f.wt2 != nullptr;
+  const int strip = fuse_strip_rows(K, f.n_out, dual);  // 8, 2 or 0 (does not fit: the caller checked)
+  // short rows (fewer than 12 edges per row on average: halo-column halves, citation graphs): the edge-stream form
+  // (scripts/ab_flat.py: -34 % at 3 edges per row, -20 % at 5, even at 12, +2 % at 30)
+  const bool flat = !dual && strip == 8 && !f.y_accum &&
+                    (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * (int64_t)a.n_rows));
+  // hot/cold gathers (option spmm_hot_cold; a.col_flagged is set by the caller when the option resolves to on and the graph's
+  // flagged column ids exist): compiled for ONE form only -- 8-B lanes, row form, 8-row strip, one product, global tile counter,
+  // buffer addressing -- and for the heavy kernel next to it.  Every other form reads the plain ids with the default policy.
+  bool hot_cold = false;
+  if constexpr (!PART && !BF && VEC == 2)
+    hot_cold = a.col_flagged && buf && !dual && strip == 8 && !flat && !f.y_accum && f.tile_xcd == 0;
+  if (hot_cold) a.col = a.col_flagged;
   if (g->n_heavy > 0) {
     SpmmArgs h = a;
     h.row_list = g->heavy_rows;
@@ -914,13 +928,18 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
     ProfScope ps(ctx, BF ? "spmm_bf16_heavy" : "spmm_heavy",
                  gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1, EB),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
-    if (buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    bool launched_h = false;
+    if constexpr (!PART && !BF && VEC == 2) {
+      if (hot_cold) {
+        spmm_heavy_kernel<VEC, 1, WMODE, U, 3, false, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+        launched_h = true;
+      }
+    }
+    if (launched_h) {
+    } else if (buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
     else spmm_heavy_kernel<VEC, 1, WMODE, U, 0, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
-  if constexpr (PART || BF) f.tile_xcd = 0;
-  const bool dual = f.wt2 != nullptr;
-  const int strip = fuse_strip_rows(K, f.n_out, dual);  // 8, 2 or 0 (does not fit: the caller checked)
   const size_t lds = fuse_lds_bytes(K, f.n_out, dual, strip);
   const int64_t ntiles = cdiv64(a.n_rows, FUSE_ROWS);
   int cus = ctx->spmm_fuse_cus > 0 ? ctx->spmm_fuse_cus : ctx->num_cus;
@@ -972,10 +991,6 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
   } while (0)
 #define GAIB_FUSED_LAUNCH_Y(GM, STRIP, DUAL, FLAT, YACC) GAIB_FUSED_LAUNCH_R(GM, STRIP, DUAL, FLAT, YACC, false)
 #define GAIB_FUSED_LAUNCH(GM, STRIP, DUAL, FLAT) GAIB_FUSED_LAUNCH_Y(GM, STRIP, DUAL, FLAT, false)
-  // short rows (fewer than 12 edges per row on average: halo-column halves, citation graphs): the edge-stream form
-  // (scripts/ab_flat.py: -34 % at 3 edges per row, -20 % at 5, even at 12, +2 % at 30)
-  const bool flat = !dual && strip == 8 && !f.y_accum &&
-                    (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * (int64_t)a.n_rows));
   const bool ring = flat && ctx->spmm_flat_ring != 0;  // the edge stream as a software pipeline (see RING)
   // option spmm_bf16_fuse_u (benchmark only): the other depth of the A/B, on the headline variant alone -- bf16 row form,
   // 8-row strip, buffer addressing, 8-B lanes (whole graphs)
@@ -987,6 +1002,13 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>
           <<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+      launched = true;
+    }
+  }
+  if constexpr (!PART && !BF && VEC == 2) {
+    if (hot_cold) {
+      GAIB_FUSED_LAUNCH_P(3, 8, false, false, false, false, false, false);
+      ctx->spmm_hot_cold_launches++;
       launched = true;
     }
   }
