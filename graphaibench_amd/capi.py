@@ -136,6 +136,7 @@ SIGNATURES = {
     "gaib_relu": (_i, [_vp, _i64, _vp, _vp]),
     "gaib_d_relu": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "gaib_dropout": (_i, [_vp, _i64, _f, _f, _u64, _vp, _vp, _vp]),
+    "gaib_dropout_dev": (_i, [_vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
     "gaib_d_dropout": (_i, [_vp, _i64, _f, _vp, _vp, _vp]),
     "gaib_softmax_xent": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gaib_d_softmax_xent": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
@@ -1031,6 +1032,14 @@ class Context:
         scale = 1.0 / (1.0 - rate)
         _check(self.lib.gaib_dropout(self.h, x.numel(), scale, rate, seed, _ptr(x), _ptr(masks), _ptr(out)),
                "gaib_dropout")
+
+    def dropout_dev(self, x, masks, out, rate: float, d_seed, scale=None):
+        """mask seed in device memory (d_seed: one 8-byte slot), advanced there: the recordable form; x = None: n = 0"""
+        if scale is None:
+            scale = 1.0 / (1.0 - rate)
+        n = x.numel() if x is not None else 0
+        _check(self.lib.gaib_dropout_dev(self.h, n, scale, rate, _ptr(d_seed), _ptr(x), _ptr(masks), _ptr(out)),
+               "gaib_dropout_dev")
 
     def d_dropout(self, x, masks, out, rate: float):
         scale = 1.0 / (1.0 - rate)

@@ -117,6 +117,7 @@ struct gaib_ctx {
   int gat_bf16;              // 1: the layer library's GAT aggregation runs its one-sweep forward and backward on bf16 copies of h and grad (gaib_gat_*_fused_bf16)
   int gat_interleave;        // one-sweep GAT backward: 1 = gather from ONE interleaved [h | grad | records] row per vertex (built per call), 0 = three tables
   int gat_fused_drop;        // 1: the layer library's GAT aggregation keeps the one sweep under attention dropout (gaib_gat_*_fused_drop), 0 (default) = staged
+  int drop_seed_dev;         // 1: the layer library's feature dropout and staged attention dropout read their mask seeds from device memory (gaib_dropout_dev), 0 (default) = by value
   int gat_fused_wide;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head rows wider than 128 columns as column slabs (gat_wide.hip), 0 (default) = GAIB_ERR_UNSUPPORTED there
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort

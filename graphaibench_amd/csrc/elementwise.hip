@@ -76,6 +76,44 @@ __global__ void dropout_kernel(int64_t n, float scale, float rate, uint64_t seed
     out[i] = in[i] * (float)m * scale;
   }
 }
+// The same draw with the seed in device memory (*seed_p): a recorded (HIP graph) dropout cannot take it by value.  16-B lanes:
+// a thread owns 4 consecutive elements (one 16-B load, one 16-B store, the 4 mask bytes as one 4-B store).  u01_key is linear in
+// the index, so element e + 1's key is element e's plus U01_GOLD, and the next trip's is this trip's plus U01_GOLD * 4 * stride:
+// one 64-bit add per element where dropout_kernel multiplies.  Same value expression, same bits.  vec_ok == 0 (pointers not
+// 16 / 16 / 4-B aligned) and the n % 4 tail take the scalar form.  seed_advance_kernel is the host's `seed++`.
+__global__ __launch_bounds__(256) void dropout_dev_kernel(int64_t n, float scale, float rate, const uint64_t* seed_p,
+                                                          const float* in, uint8_t* masks, float* out, int vec_ok) {
+  const uint64_t seed = *seed_p;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t tail0 = 0;
+  if (vec_ok) {
+    const int64_t n4 = n >> 2;
+    uint64_t key = u01_key(seed, (uint64_t)tid << 2);
+    const uint64_t key_step = U01_GOLD * ((uint64_t)stride << 2);
+    for (int64_t i = tid; i < n4; i += stride, key += key_step) {
+      f4 v = reinterpret_cast<const f4*>(in)[i];
+      uint32_t mw = 0;
+      uint64_t k64 = key;
+#pragma unroll
+      for (int k = 0; k < 4; ++k, k64 += U01_GOLD) {
+        const uint8_t m = u01_of_key(k64) > rate ? 1 : 0;
+        mw |= (uint32_t)m << (8 * k);
+        v[k] = v[k] * (float)m * scale;
+      }
+      reinterpret_cast<f4*>(out)[i] = v;
+      reinterpret_cast<uint32_t*>(masks)[i] = mw;
+    }
+    tail0 = n4 << 2;
+  }
+  for (int64_t i = tail0 + tid; i < n; i += stride) {
+    const uint8_t m = u01(seed, (uint64_t)i) > rate ? 1 : 0;
+    masks[i] = m;
+    out[i] = in[i] * (float)m * scale;
+  }
+}
+__global__ void seed_advance_kernel(uint64_t* seed_p) { seed_p[0] += 1; }
+
 __global__ void d_dropout_kernel(int64_t n, float scale, const float* in, const uint8_t* masks,
                                  float* out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -906,6 +944,22 @@ extern "C" int gaib_dropout(gaib_ctx* ctx, int64_t n, float scale, float drop_ra
   if (n <= 0) return GAIB_OK;
   dropout_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, scale, drop_rate, seed, d_in,
                                                                d_masks, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_dropout_dev(gaib_ctx* ctx, int64_t n, float scale, float drop_rate, uint64_t* d_seed,
+                                const float* d_in, uint8_t* d_masks, float* d_out) {
+  GAIB_CHECK(ctx && d_seed && ((d_in && d_masks && d_out) || n == 0), "gaib_dropout_dev: NULL argument");
+  GAIB_CHECK(drop_rate >= 0.f && drop_rate < 1.f, "gaib_dropout_dev: rate must be in [0,1)");
+  GAIB_CHECK(((uintptr_t)d_seed & 7) == 0, "gaib_dropout_dev: d_seed must be 8-byte aligned");
+  if (n > 0) {
+    const int vec_ok = ((((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0) && (((uintptr_t)d_masks & 3) == 0);
+    dropout_dev_kernel<<<stream_grid(n / 4 + 1, 256), 256, 0, ctx->stream>>>(n, scale, drop_rate, d_seed, d_in, d_masks,
+                                                                            d_out, vec_ok);
+    GAIB_LAUNCH_CHECK();
+  }
+  seed_advance_kernel<<<1, 1, 0, ctx->stream>>>(d_seed);  // once per call, also for n == 0 (the host's seed++ runs whatever n is)
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

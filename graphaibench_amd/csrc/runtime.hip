@@ -97,6 +97,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->gat_interleave = 0;
   c->gat_bf16 = 0;
   c->gat_fused_wide = 0;  // (ships off: flipped by a change of its own once the layer step is measured faster)
+  c->drop_seed_dev = 0;   // (not measured yet: DESIGN 3.5.3)
   c->gat_fused_drop = 0;  // (measured, LEDGER 14.2; a default is flipped by a change of its own)
   c->gat_bwd_pk = 0;  // measured, round 6: the packed-math sweep saves a third of the VALU instructions and nothing at the real
                       // column ids (6.27 vs 6.25 ms at the reddit shape: the sweep is bound by the L2 -> fabric gather stream there)
@@ -558,6 +559,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_bf16_pad")) *h_value = ctx->spmm_bf16_pad;
   else if (!strcmp(key, "agg_bf16_ld_last")) *h_value = ctx->agg_bf16_ld_last;
   else if (!strcmp(key, "sampler_device")) *h_value = ctx->sampler_device;
+  else if (!strcmp(key, "drop_seed_dev")) *h_value = ctx->drop_seed_dev;
   else {
     gaib_set_error("gaib_get_option: no readable option '%s'", key);
     return GAIB_ERR_INVALID;
@@ -624,6 +626,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "gat_fused_drop")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_fused_drop must be 0 (attention dropout staged) or 1 (in the one sweep)");
     ctx->gat_fused_drop = (int)value;
+  } else if (!strcmp(key, "drop_seed_dev")) {
+    GAIB_CHECK(value == 0 || value == 1, "drop_seed_dev must be 0 (dropout mask seeds counted on the host) or 1 (in device memory)");
+    ctx->drop_seed_dev = (int)value;
   } else if (!strcmp(key, "gat_fused_wide")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_fused_wide must be 0 (rows wider than 128 columns staged) or 1 (one sweep per column slab)");
     ctx->gat_fused_wide = (int)value;

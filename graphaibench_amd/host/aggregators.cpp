@@ -579,7 +579,7 @@ void GAT_Aggregator::init(int l, int nv, int ne, float lr, float drop_rate) {
 
 // d_norm_scores (the softmax of this forward) -> p . mask . scale in a buffer of its own: backward needs both the
 // undropped attention (softmax backward) and the dropped one (d_dropout of dp, transposed aggregation)
-const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores, uint64_t seed) {
+const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores, uint64_t seed, uint64_t* d_seed) {
   if (n_scores > drop_cap) {
     if (d_norm_scores_drop) float_free_device(d_norm_scores_drop);
     if (d_attn_masks) GAIB_OR_DIE(gaib_free(C(), d_attn_masks));
@@ -588,10 +588,29 @@ const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores, uint64_t seed) 
     drop_cap = n_scores;
   }
   OpTimer t(OP_DROPOUT);
-  GAIB_OR_DIE(gaib_dropout(C(), (int64_t)n_scores, attn_scale, attn_drop, seed, d_norm_scores, d_attn_masks,
-                           d_norm_scores_drop));
+  if (d_seed)
+    GAIB_OR_DIE(gaib_dropout_dev(C(), (int64_t)n_scores, attn_scale, attn_drop, d_seed, d_norm_scores, d_attn_masks,
+                                 d_norm_scores_drop));
+  else
+    GAIB_OR_DIE(gaib_dropout(C(), (int64_t)n_scores, attn_scale, attn_drop, seed, d_norm_scores, d_attn_masks,
+                             d_norm_scores_drop));
   dropped_last = true;
   return d_norm_scores_drop;
+}
+
+// the staged forward's draw under the aggregator's next seed.  Option drop_seed_dev with attention dropout staged (gat_fused_drop
+// = 0): the counter lives in d_drop_seed, made here on first use (outside any capture) from drop_seed, and gaib_dropout_dev
+// advances it -- the host path's seeds, call for call; drop_seed keeps step with every call that runs.  Both options are read
+// once, at that first use.
+const float* GAT_Aggregator::next_attn_dropout(size_t n_scores) {
+  if (seed_dev < 0) {
+    seed_dev = gaib_host::drop_seed_dev_option() && !gat_fused_drop_option() ? 1 : 0;
+    if (seed_dev) d_drop_seed = gaib_host::new_seed_slot(drop_seed);
+  }
+  if (!seed_dev) return apply_attn_dropout(n_scores, drop_seed++);
+  const float* attn = apply_attn_dropout(n_scores, 0, d_drop_seed);
+  if (!gaib_host::capturing()) drop_seed++;
+  return attn;
 }
 
 void GAT_Aggregator::release() {
@@ -605,6 +624,9 @@ void GAT_Aggregator::release() {
   }
   if (d_attn_masks) GAIB_OR_DIE(gaib_free(c, d_attn_masks));
   d_attn_masks = NULL;
+  if (d_drop_seed) GAIB_OR_DIE(gaib_free(c, d_drop_seed));
+  d_drop_seed = NULL;
+  seed_dev = -1;
   if (d_hb16) GAIB_OR_DIE(gaib_free(c, d_hb16));
   d_hb16 = NULL;
   hb16_elems = 0;
@@ -735,7 +757,7 @@ void GAT_Aggregator::aggregate_partition(int len, Graph& g, const float* in, flo
     GAIB_OR_DIE(gaib_gat_scores_mh(C(), g.gat_full_graph(), len, heads, d_ptab, d_alpha_l, d_alpha_r, epsilon,
                                    d_temp_scores, NULL, d_norm_scores));
   }
-  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads, drop_seed++) : d_norm_scores;
+  const float* attn = dropping() ? next_attn_dropout((size_t)g.sizeEdges() * heads) : d_norm_scores;
   OpTimer t(OP_SPARSEMM);
   GAIB_OR_DIE(gaib_spmm_mh(C(), g.gat_full_graph(), GAIB_W_EDGE, attn, heads, len, d_ptab, out,
                            fuse_relu ? GAIB_RELU : 0));
@@ -930,7 +952,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     GAIB_OR_DIE(gaib_gat_scores_mh(C(), dev(g), len, heads, in, d_alpha_l, d_alpha_r, epsilon, d_temp_scores,
                                    NULL, d_norm_scores));
   }
-  const float* attn = dropping() ? apply_attn_dropout((size_t)g.sizeEdges() * heads, drop_seed++) : d_norm_scores;
+  const float* attn = dropping() ? next_attn_dropout((size_t)g.sizeEdges() * heads) : d_norm_scores;
   OpTimer t(OP_SPARSEMM);
   GAIB_OR_DIE(gaib_spmm_mh(C(), dev(g), GAIB_W_EDGE, attn, heads, len, in, out, fuse_relu ? GAIB_RELU : 0));
   fuse_relu = false;

@@ -106,6 +106,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gat_fused_drop", v), "gaib_set_option (GAIB_GAT_FUSED_DROP)");
   }
+  // dropout mask seeds in device memory (option drop_seed_dev; off by default): feature dropout and staged attention dropout
+  // draw with gaib_dropout_dev, which lets the trainer record an epoch under dropout
+  if (const char* d = getenv("GAIB_DROP_SEED_DEV")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_DROP_SEED_DEV=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "drop_seed_dev", v), "gaib_set_option (GAIB_DROP_SEED_DEV)");
+  }
   // GAT layers with multi-head rows wider than 128 columns (8 heads x 32, 8 x 64): the one-sweep kernels per column slab (option
   // gat_fused_wide; off by default)
   if (const char* d = getenv("GAIB_GAT_WIDE")) {

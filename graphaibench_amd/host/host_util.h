@@ -20,4 +20,8 @@ inline T* dmalloc(size_t n) {
   GAIB_OR_DIE(gaib_malloc(gpu_context::get(), (n > 0 ? n : 1) * sizeof(T), &p));
   return static_cast<T*>(p);
 }
+// option drop_seed_dev (math_functions.cpp): dropout mask seeds in device memory, read and advanced by gaib_dropout_dev
+bool drop_seed_dev_option();
+bool capturing();                        // a recording is open on the process context (gaib_capture_begin)
+uint64_t* new_seed_slot(uint64_t seed);  // one 8-byte device slot holding `seed`; allocates and waits: not inside a capture
 }  // namespace gaib_host

@@ -49,8 +49,51 @@ void d_relu_gpu(const size_t n, const float_t* in_diff, const float_t* data, flo
   GAIB_OR_DIE(gaib_d_relu(C(), (int64_t)n, in_diff, data, out_diff));
 }
 static uint64_t g_dropout_seed = 0x5EED;
+// option drop_seed_dev (GAIB_DROP_SEED_DEV=1): the counter lives in one process-wide 8-byte device slot and gaib_dropout_dev reads
+// and advances it there, so that a recorded epoch draws a new mask per replay.  The slot is made where it is first needed
+// (outside any capture: it allocates), from the host counter's value, so the seeds are the host path's, call for call; the host
+// counter keeps step with every call that runs (a recorded call runs nothing).  A new process context (gpu_context::set) -- told
+// by its generation, as aggregators.cpp's g_zs tells it -- reads the option again and gets a slot of its own.
+static struct DropSeedSlot {
+  gaib_ctx* ctx = nullptr;
+  unsigned gen = 0;
+  int on = 0;  // the option, as read when this context first dropped
+  uint64_t* d_seed = nullptr;
+} g_drop_slot;
+uint64_t* gaib_host::new_seed_slot(uint64_t seed) {
+  uint64_t* d = gaib_host::dmalloc<uint64_t>(1);
+  GAIB_OR_DIE(gaib_memcpy_h2d(C(), d, &seed, sizeof(seed)));
+  return d;
+}
+bool gaib_host::capturing() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "capturing", &v));
+  return v != 0;
+}
+bool gaib_host::drop_seed_dev_option() {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(C(), "drop_seed_dev", &v));
+  return v != 0;
+}
+static uint64_t* dropout_seed_slot() {
+  DropSeedSlot& s = g_drop_slot;
+  if (s.ctx != C() || s.gen != gpu_context::generation()) {
+    if (s.d_seed) GAIB_OR_DIE(gaib_free(C(), s.d_seed));
+    s.d_seed = nullptr;
+    s.ctx = C();
+    s.gen = gpu_context::generation();
+    s.on = gaib_host::drop_seed_dev_option() ? 1 : 0;
+    if (s.on) s.d_seed = gaib_host::new_seed_slot(g_dropout_seed);
+  }
+  return s.d_seed;
+}
 void dropout_gpu(size_t n, float scale, float drop_rate, const float* in, mask_t* masks, float* out) {
   OpTimer t(OP_DROPOUT);
+  if (uint64_t* d_seed = dropout_seed_slot()) {
+    GAIB_OR_DIE(gaib_dropout_dev(C(), (int64_t)n, scale, drop_rate, d_seed, in, masks, out));
+    if (!gaib_host::capturing()) g_dropout_seed++;
+    return;
+  }
   GAIB_OR_DIE(gaib_dropout(C(), (int64_t)n, scale, drop_rate, g_dropout_seed++, in, masks, out));
 }
 void d_dropout_gpu(size_t n, float scale, const float* in, const mask_t* masks, float* out) {

@@ -642,17 +642,32 @@ struct Trainer {
 
   // GAIB_EPOCH_GRAPH = 1: record the epoch wherever the run allows it; 0: never; unset: when it allows it AND the graph
   // is small enough to be launch bound (<= 4 M edges).  Not recorded: partitioned runs (the exchange waits on peers),
-  // sampling / inductive runs (the graph changes per epoch), dropout (the mask seed is a by-value argument), per-op
-  // synchronising timers and the side-stream option.
+  // sampling / inductive runs (the graph changes per epoch), per-op synchronising timers and the side-stream option.
+  // Dropout: a mask seed passed by value would be frozen in the recording, so a run with feat_drop > 0 or score_drop > 0 is
+  // recorded only with option drop_seed_dev (GAIB_DROP_SEED_DEV=1), under which the layers keep their seeds in device memory
+  // (gaib_dropout_dev: epoch 0 makes the slots call by call, the recording advances none, every replay draws the next) --
+  // except GAT attention dropout kept in the one sweep (gat_fused_drop = 1), whose kernels take their seed by value.
   bool decide_graph_mode() const {
     const char* e = getenv("GAIB_EPOCH_GRAPH");
     if (e && atoi(e) == 0) return false;
     const char* st = getenv("GAIB_SYNC_TIMERS");
     const char* ov = getenv("GAIB_OVERLAP");
-    const bool allowed = world == 1 && subg_size == 0 && !inductive && feat_drop == 0.f && score_drop == 0.f &&
-                         !(st && atoi(st)) && !(ov && atoi(ov)) && num_epochs > 1;
-    if (e && atoi(e) != 0 && !allowed && root())
-      std::cerr << "[gaib] GAIB_EPOCH_GRAPH=1 ignored: partitioned, sampling, inductive, dropout or timer runs are not recorded\n";
+    const bool dropout = feat_drop != 0.f || score_drop != 0.f;
+    int64_t seeds_dev = 0, drop_sweep = 0;
+    if (dropout) {
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "drop_seed_dev", &seeds_dev));
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_drop", &drop_sweep));
+    }
+    const bool sweep_by_value = ARCH == gnn_arch::GAT && score_drop != 0.f && drop_sweep == 1;
+    const bool other = world == 1 && subg_size == 0 && !inductive && !(st && atoi(st)) && !(ov && atoi(ov)) && num_epochs > 1;
+    const bool allowed = other && (!dropout || (seeds_dev == 1 && !sweep_by_value));
+    if (e && atoi(e) != 0 && !allowed && root()) {
+      if (other && seeds_dev == 1)
+        std::cerr << "[gaib] GAIB_EPOCH_GRAPH=1 ignored: attention dropout in the one sweep (gat_fused_drop = 1) takes its mask "
+                     "seed by value and is not recorded\n";
+      else
+        std::cerr << "[gaib] GAIB_EPOCH_GRAPH=1 ignored: partitioned, sampling, inductive, dropout or timer runs are not recorded\n";
+    }
     if (!allowed) return false;
     return e ? true : graph->sizeEdges() <= ((size_t)1 << 22);
   }
@@ -696,6 +711,11 @@ struct Trainer {
   void train() {
     optimizer* opt = new adam(lrate);  // one instance for every layer's update_weight call (Q6)
     graph_mode = decide_graph_mode();
+    {
+      int64_t seeds_dev = 0;
+      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "drop_seed_dev", &seeds_dev));
+      if (seeds_dev == 1 && root()) std::cerr << "[gaib] dropout mask seeds: device\n";
+    }
     if (graph_mode) {
       // the null stream cannot be recorded, and the beta powers of every Adam instance have to live on the device
       GAIB_OR_DIE(gaib_ctx_own_stream(gpu_context::get()));

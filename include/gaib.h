@@ -75,7 +75,7 @@ int gaib_side_wait(gaib_ctx* ctx);
  * Inside a capture, calls that wait for the stream or allocate return GAIB_ERR_INVALID with a message (gaib_sync,
  * gaib_memcpy_h2d/d2h, metrics with host results, a workspace or lazily built graph table that does not exist
  * yet): run the sequence once eagerly first.  Pointers and by-value scalars are frozen in the recording; per-replay
- * state lives in device memory (gaib_adam_step_dev, gaib_masked_*_dev, gaib_memcpy_d2h_async).  The context must
+ * state lives in device memory (gaib_adam_step_dev, gaib_dropout_dev, gaib_masked_*_dev, gaib_memcpy_d2h_async).  The context must
  * own a real stream (not the null stream), without a side section or kernel timing switched on.
  * Scratch: a recording holds the addresses of the context's internal workspaces.  While any gaib_exec of a context
  * is alive, a workspace that has to grow (a later, larger call outside the replay) is kept allocated next to its
@@ -701,6 +701,14 @@ int gaib_dropout(gaib_ctx* ctx, int64_t n, float scale, float drop_rate, uint64_
                  const float* d_in, uint8_t* d_masks, float* d_out);
 int gaib_d_dropout(gaib_ctx* ctx, int64_t n, float scale, const float* d_in,
                    const uint8_t* d_masks, float* d_out);
+/* gaib_dropout with the mask seed in device memory: with s = *d_seed when the call's kernel runs on the context's stream, d_masks
+ * and d_out hold the bits gaib_dropout(ctx, n, scale, drop_rate, s, ..) writes; behind the draw, in stream order, *d_seed becomes
+ * s + 1 (mod 2^64) -- once per call, for n == 0 too (the host's `seed++`).  No host wait, no allocation: legal inside
+ * gaib_capture_begin/end, and every replay draws the next seed.  d_out == d_in is allowed.  d_seed is always required and
+ * 8-byte aligned (GAIB_ERR_INVALID before any launch otherwise); the rate lies in [0, 1).  d_in / d_out on 16 B and d_masks on
+ * 4 B run 16-byte lanes, any other alignment one element per lane. */
+int gaib_dropout_dev(gaib_ctx* ctx, int64_t n, float scale, float drop_rate, uint64_t* d_seed,
+                     const float* d_in, uint8_t* d_masks, float* d_out);
 
 /* bias_mv (include/utils/math_functions.hh:36; math_functions.cu:207-221): x[i, j] += b[j] for x [n x len] */
 int gaib_bias_add(gaib_ctx* ctx, int64_t n, int len, float* d_x, const float* d_b);
@@ -953,6 +961,10 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head
  * rows wider than 128 columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); the layer library keeps attention
  * dropout in the sweep there only with "gat_fused_drop" = 1 as well; the _bf16 / _drop_bf16 calls ("gat_bf16") run the same slabs; partitions stay as they are;
+ * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
+ * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
+ * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;
+ * attention dropout kept in the one sweep ("gat_fused_drop" = 1) still takes its seed by value;
  * "spmm_bf16_layout" (0): gaib_spmm_bf16's lane layout, 0 = one row per wave, 4 / 8 =
  * sub-wave rows of 4 / 8 elements per lane.  Both readable with gaib_get_option.
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
@@ -964,7 +976,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sampler_device", "gat_fused_drop", "gat_fused_wide" */
+ * "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -139,8 +139,17 @@ class GAT_Aggregator : public aggregator {
   size_t drop_cap;
   uint64_t drop_seed;
   bool dropping() const { return attn_drop > 0.f && training; }
-  // d_norm_scores -> d_norm_scores_drop (+ masks) under `seed`; returns the latter
-  const float* apply_attn_dropout(size_t n_scores, uint64_t seed);
+  // d_norm_scores -> d_norm_scores_drop (+ masks) under `seed`, or under *d_seed where that is given (gaib_dropout_dev, which
+  // advances it); returns the latter
+  const float* apply_attn_dropout(size_t n_scores, uint64_t seed, uint64_t* d_seed = NULL);
+  // extension: the mask seed in device memory (context option "drop_seed_dev" = 1, or GAIB_DROP_SEED_DEV=1, set BEFORE the first
+  // layer is built), so that a recorded epoch draws a new mask per replay.  Staged attention dropout only (gat_fused_drop = 0: the
+  // one-sweep _drop kernels take their seed by value and the aggregator stays as it is): next_attn_dropout() is the staged
+  // forward's `apply_attn_dropout(.., drop_seed++)`, with the counter in d_drop_seed -- one 8-byte slot per aggregator, made on
+  // first use from drop_seed, released with the other device buffers -- where the option was on at that first use.
+  const float* next_attn_dropout(size_t n_scores);
+  uint64_t* d_drop_seed = NULL;
+  int seed_dev = -1;  // -1: the options have not been read yet
   size_t num_edges;
   int heads;
   float *d_alpha_l, *d_alpha_r, *d_alpha_lgrad, *d_alpha_rgrad;
