@@ -21,7 +21,7 @@ INCLUDE = ROOT / "include"
 ORACLE = ROOT / "oracle"
 REFERENCE = Path("/root/reference")
 
-HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_bf16.hip", "gat_drop.hip", "gat_wide.hip", "gat_wide_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "elementwise.hip", "probe.hip", "comm.hip"]
+HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "elementwise.hip", "probe.hip", "comm.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -61,7 +61,7 @@ def build_hip(force: bool = False) -> Path:
     LIB.mkdir(exist_ok=True)
     out = LIB / "libgaib_hip.so"
     hipcc = _hipcc()
-    headers = [CSRC / "common.h", CSRC / "spmm_core.h", CSRC / "spmm_kernels.h", CSRC / "gat_kernels.h", CSRC / "gat_wide_slabs.h", INCLUDE / "gaib.h"]
+    headers = [CSRC / "common.h", CSRC / "spmm_core.h", CSRC / "spmm_kernels.h", CSRC / "gat_kernels.h", CSRC / "gat_fused_seq.h", INCLUDE / "gaib.h"]
     objs, jobs = [], []
     for src in HIP_SOURCES:
         s = CSRC / src

@@ -118,7 +118,7 @@ struct gaib_ctx {
   int gat_interleave;        // one-sweep GAT backward: 1 = gather from ONE interleaved [h | grad | records] row per vertex (built per call), 0 = three tables
   int gat_fused_drop;        // 1: the layer library's GAT aggregation keeps the one sweep under attention dropout (gaib_gat_*_fused_drop), 0 (default) = staged
   int drop_seed_dev;         // 1: the layer library's feature dropout and staged attention dropout read their mask seeds from device memory (gaib_dropout_dev), 0 (default) = by value
-  int gat_fused_wide;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head rows wider than 128 columns as column slabs (gat_wide.hip), 0 (default) = GAIB_ERR_UNSUPPORTED there
+  int gat_fused_wide;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head rows wider than 128 columns as column slabs (gat_fused_seq.h), 0 (default) = GAIB_ERR_UNSUPPORTED there
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort
   int sampler_device;        // read by the trainer: 1 = sampled subgraphs are induced on the device (gaib_graph_induce), 0 (default) = on the host
@@ -244,34 +244,6 @@ static inline int64_t gaib_hot_rows_wanted(const gaib_ctx* ctx, const gaib_graph
   return r < 1 ? 1 : r;
 }
 int gaib_graph_ensure_induce(gaib_ctx* ctx, gaib_graph* g);
-// the one-sweep GAT on S = len / w column slabs of w columns and heads / S heads (gat_wide.hip; option gat_fused_wide): called by
-// gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) after their argument checks, with (w, S) of
-// gaib_gat_fused_slabs, S >= 2.  GAIB_ERR_UNSUPPORTED with nothing touched as the narrow calls refuse.
-int gaib_gat_forward_fused_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const float* d_h,
-                                const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float* d_out,
-                                float* d_row_stats);
-int gaib_gat_backward_fused_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const float* d_feat,
-                                 const float* d_grad, const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
-                                 const float* d_row_stats, float epsilon, float* d_grad_out, float* d_alpha_lgrad,
-                                 float* d_alpha_rgrad);
-// the same under attention dropout: called by gaib_gat_forward_fused_drop / gaib_gat_backward_fused_drop after their argument
-// checks; slab s runs the window sequence (gaib_gat_*_fused_drop_win) at (w, heads / S, mask_heads = heads, mask_head0 = s heads / S)
-int gaib_gat_forward_fused_drop_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const float* d_h,
-                                     const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float drop_rate,
-                                     float scale, uint64_t seed, float* d_out, float* d_row_stats);
-int gaib_gat_backward_fused_drop_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const float* d_feat,
-                                      const float* d_grad, const float* d_fwd_out, const float* d_alpha_l, const float* d_alpha_r,
-                                      const float* d_row_stats, float epsilon, float drop_rate, float scale, uint64_t seed,
-                                      float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad);
-// the slab loop over bf16 tables (gat_wide_bf16.hip): called by gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 after their
-// argument checks, as the fp32 calls call the two functions above (the _drop_bf16 calls live in that file and loop there)
-int gaib_gat_forward_fused_bf16_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const uint16_t* d_h_bf16,
-                                     const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu, float* d_out,
-                                     float* d_row_stats);
-int gaib_gat_backward_fused_bf16_wide(gaib_ctx* ctx, gaib_graph* g, int len, int heads, int w, int S, const uint16_t* d_feat_bf16,
-                                      const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_alpha_l,
-                                      const float* d_alpha_r, const float* d_row_stats, float epsilon, float* d_grad_out,
-                                      float* d_alpha_lgrad, float* d_alpha_rgrad);
 // an empty square graph of nv rows with rowptr [nv + 1] and colidx [ne] allocated, nothing filled (graph.hip)
 int gaib_graph_new(int64_t nv, int64_t ne, int device, gaib_graph** out);
 

@@ -768,12 +768,6 @@ __global__ __launch_bounds__(256) void gat_score_sign_kernel(int64_t n_chunks, c
 // the row-owner kernels: gat_row_waves (1, 2 or 4) one-wave rows per workgroup
 inline unsigned rowgrid_w(const gaib_ctx* ctx, int64_t nv) { return (unsigned)cdiv64(nv > 0 ? nv : 1, ctx->gat_row_waves); }
 
-int check_heads(const char* who, int len, int heads) {
-  GAIB_CHECK(len > 0, "%s: len must be > 0", who);
-  GAIB_CHECK(heads >= 1 && len % heads == 0, "%s: heads (%d) must divide len (%d)", who, heads, len);
-  return GAIB_OK;
-}
-
 template <int H>
 int launch_edge_softmax(gaib_ctx* ctx, gaib_graph* g, const float* sl, const float* sr, float eps, float* temp,
                         float* scores, float* norm) {
@@ -957,9 +951,7 @@ static int softmax_bwd_alpha_impl(gaib_ctx* ctx, gaib_graph* g, int len, int hea
   GAIB_CHECK((d_grad_rows == nullptr) == (d_fwd_out_rows == nullptr),
              "gaib_gat_softmax_bwd_alpha: d_grad_rows and d_fwd_out_rows go together");
   GAIB_TRY(gaib_graph_ensure_rev(ctx, g));
-  const int nblocks = (int)(g->nv < 2048 ? cdiv64(g->nv, 8) : 1024);
-  const int64_t rows_per_block = cdiv64(g->nv, nblocks);
-  auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };  // keep every slab 16-byte aligned
+  const int nblocks = gat_alpha_blocks(g->nv);
   const size_t n_g = up4((size_t)g->ne * heads * (d_norm_scores_t ? 2 : 1)), n_v = up4((size_t)g->nv * heads);
   // graphs with a quarter of their edges in heavy rows, 1-2 heads: the column sums go chunk by chunk (reddit shape: 2.86 -> 2.67 ms single-head; at 8 heads
   // the 64-byte records gain nothing, 7.10 vs 7.11 ms).  gat_chunk_colsum: -1 = that rule, 0 never, 1 always.
@@ -1017,242 +1009,7 @@ static int softmax_bwd_alpha_impl(gaib_ctx* ctx, gaib_graph* g, int len, int hea
 #undef GAIB_SBW
   if (rc != GAIB_OK) return rc;
   GAIB_LAUNCH_CHECK();
-  alpha_partial_kernel<<<nblocks, 256, sizeof(float) * 512, ctx->stream>>>(g->nv, len, heads, d_feat, rs, cs,
-                                                                         rows_per_block, partial);
-  GAIB_LAUNCH_CHECK();
-  alpha_final_kernel<<<(unsigned)cdiv64(2 * (int64_t)len, 4), 256, 0, ctx->stream>>>(nblocks, len, partial, d_alpha_lgrad,
-                                                                                    d_alpha_rgrad);
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
-}
-
-// Forward in one sweep (gat_fwd_fused_chunk_kernel): d_out = act(P h) and d_row_stats [nv][heads][2] = (row maximum of
-// the leaky-relu'd scores, 1 / row sum of exp) -- everything backward needs to form the attention again; no [ne][heads]
-// array is written.  Same cover and auto rule as gaib_gat_backward_fused (option "gat_fused_fwd"); otherwise
-// GAIB_ERR_UNSUPPORTED, nothing touched, and the caller runs gaib_gat_scores_mh + gaib_spmm_mh.
-// phase: -1 = the whole sweep + the per-row combination (square graphs, or a rectangular one whose table is complete);
-// 0 = only the chunks over owned columns (columns < g->nv), nothing else; 1 = the remaining chunks + the combination.
-// The partial results of phase 0 live in the context's workspace until phase 1: no other call on the context in between.
-static int gat_forward_fused_impl(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
-                                  const float* d_alpha_r, float epsilon, int relu, float* d_out, float* d_row_stats, int phase,
-                                  bool rect, const char* who) {
-  GAIB_CHECK(ctx && g, "%s: NULL ctx/graph", who);
-  GAIB_TRY(check_heads(who, len, heads));
-  if (g->nv == 0) {
-    // a rank without rows (fewer vertices than ranks): nothing to write, its buffers may be NULL -- but WHICH path "ran" must be
-    // what the ranks with rows decide, from the shape and the option alone: the two paths differ in their exchanges
-    if (rect && gat_fused_shape(len, heads) && ctx->gat_fused_fwd != 0) return GAIB_OK;
-    gaib_set_error("%s: not applicable to this shape / graph (len %d, heads %d)", who, len, heads);
-    return GAIB_ERR_UNSUPPORTED;
-  }
-  GAIB_CHECK(d_h && d_alpha_l && d_alpha_r && d_out && d_row_stats && d_out != d_h, "%s: NULL or aliased pointer", who);
-  GAIB_CHECK(phase >= -1 && phase <= 1, "%s: phase is -1, 0 or 1", who);
-  GAIB_HIP(hipSetDevice(ctx->device));
-  // option gat_fused_wide: a multi-head row wider than 128 columns as S column slabs of a width the kernels cover (gat_wide.hip);
-  // whole graphs only -- the _rect calls keep today's answer
-  if (!rect && ctx->gat_fused_wide == 1 && !gat_fused_shape(len, heads)) {
-    int w = 0;
-    const int S = gaib_gat_fused_slabs(len, heads, &w);
-    if (S >= 2)
-      return gaib_gat_forward_fused_wide(ctx, g, len, heads, w, S, d_h, d_alpha_l, d_alpha_r, epsilon, relu, d_out, d_row_stats);
-  }
-  int rc = GAIB_OK;
-  const bool use = gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_fwd,
-                                     (uintptr_t)d_h | (uintptr_t)d_out | (uintptr_t)d_row_stats | (uintptr_t)d_alpha_l |
-                                         (uintptr_t)d_alpha_r, &rc, rect);
-  if (rc != GAIB_OK) return rc;
-  if (!use) {
-    gaib_set_error("%s: not applicable to this shape / graph (len %d, heads %d)", who, len, heads);
-    return GAIB_ERR_UNSUPPORTED;
-  }
-  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
-  auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-  const size_t n_op = up4((size_t)g->n_chunks * len), n_ms = up4((size_t)g->n_chunks * heads * 2);
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (n_op + n_ms)));
-  float* out_partial = (float*)ctx->ws;
-  float2* ms_partial = reinterpret_cast<float2*>(out_partial + n_op);
-  ProfScope ps(ctx, "gat_fwd_fused", (double)g->ne * (4.0 + 4.0 * len) + (double)g->n_chunks * (4.0 * len + 8.0 * heads) * 2 + (double)g->nv * (4.0 * len + 8.0 * heads),
-               4.0 * (double)g->ne * len);
-  unsigned grid = (unsigned)cdiv64(g->n_chunks, 4);  // (0 on a rank whose rows have no edges: nothing to sweep)
-  int per_xcd = 0;
-  if (ctx->gat_chunk_xcd == 1 && grid >= 64) {
-    per_xcd = (int)cdiv64(grid, 8);
-    grid = (unsigned)per_xcd * 8u;
-  }
-#define GAIB_FF(GG, HH)                                                                                                   \
-  if (grid > 0) gat_fwd_fused_chunk_kernel<GG, HH, 8, float><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase,          \
-                                                                       g->chunk_start, g->rowptr, g->colidx, len, d_h,     \
-                                                                       d_alpha_l, d_alpha_r, epsilon, out_partial, ms_partial, \
-                                                                       phase, (uint32_t)g->nv, per_xcd)
-  GAIB_GAT_DISPATCH(GAIB_FF);
-#undef GAIB_FF
-  GAIB_LAUNCH_CHECK();
-  if (phase == 0) return GAIB_OK;
-#define GAIB_FR(GG)                                                                                                        \
-  gat_fwd_reduce_kernel<GG><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, heads, g->chunk_start, out_partial, ms_partial, \
-                                                                     relu ? 1 : 0, d_out, reinterpret_cast<float2*>(d_row_stats))
-  if (len == 32) GAIB_FR(8);
-  else if (len == 64) GAIB_FR(16);
-  else GAIB_FR(32);
-#undef GAIB_FR
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
-}
-
-extern "C" int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h,
-                                      const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu,
-                                      float* d_out, float* d_row_stats) {
-  return gat_forward_fused_impl(ctx, g, len, heads, d_h, d_alpha_l, d_alpha_r, epsilon, relu, d_out, d_row_stats, -1, false,
-                                "gaib_gat_forward_fused");
-}
-
-// the same on a rank's RECTANGULAR graph (rows = owned vertices, columns = [owned | halo]): d_tab [nc x len] holds the owned
-// rows of h first, then the halo rows.  phase 0 may run while the halo rows are still arriving (it reads owned rows only).
-extern "C" int gaib_gat_forward_fused_rect(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_tab,
-                                           const float* d_alpha_l, const float* d_alpha_r, float epsilon, int relu,
-                                           float* d_out, float* d_row_stats, int phase) {
-  return gat_forward_fused_impl(ctx, g, len, heads, d_tab, d_alpha_l, d_alpha_r, epsilon, relu, d_out, d_row_stats, phase, true,
-                                "gaib_gat_forward_fused_rect");
-}
-
-extern "C" int gaib_gat_backward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat,
-                                       const float* d_grad, const float* d_fwd_out, const float* d_alpha_l,
-                                       const float* d_alpha_r, const float* d_norm_scores, const float* d_row_stats,
-                                       float epsilon, float* d_grad_out, float* d_alpha_lgrad, float* d_alpha_rgrad) {
-  GAIB_CHECK(ctx && g, "gaib_gat_backward_fused: NULL ctx/graph");
-  GAIB_TRY(check_heads("gaib_gat_backward_fused", len, heads));
-  if (g->nv == 0) {  // no rows: the alpha gradients of this graph are zero, nothing else is written
-    GAIB_HIP(hipSetDevice(ctx->device));
-    if (d_alpha_lgrad) GAIB_HIP(hipMemsetAsync(d_alpha_lgrad, 0, sizeof(float) * len, ctx->stream));
-    if (d_alpha_rgrad) GAIB_HIP(hipMemsetAsync(d_alpha_rgrad, 0, sizeof(float) * len, ctx->stream));
-    return GAIB_OK;
-  }
-  GAIB_CHECK(d_feat && d_grad && d_fwd_out && d_alpha_l && d_alpha_r && (d_norm_scores || d_row_stats) && d_grad_out &&
-                 d_alpha_lgrad && d_alpha_rgrad, "gaib_gat_backward_fused: NULL pointer");
-  GAIB_CHECK(d_grad_out != d_feat && d_grad_out != d_grad, "gaib_gat_backward_fused: d_grad_out must not alias an input");
-  GAIB_HIP(hipSetDevice(ctx->device));
-  // option gat_fused_wide (see the forward): the row-statistics form only
-  if (ctx->gat_fused_wide == 1 && d_row_stats && !gat_fused_shape(len, heads)) {
-    int w = 0;
-    const int S = gaib_gat_fused_slabs(len, heads, &w);
-    if (S >= 2)
-      return gaib_gat_backward_fused_wide(ctx, g, len, heads, w, S, d_feat, d_grad, d_fwd_out, d_alpha_l, d_alpha_r, d_row_stats,
-                                          epsilon, d_grad_out, d_alpha_lgrad, d_alpha_rgrad);
-  }
-  int rc0 = GAIB_OK;
-  const bool use = gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_bwd,
-                                     (uintptr_t)d_feat | (uintptr_t)d_grad | (uintptr_t)d_norm_scores |
-                                         (uintptr_t)d_row_stats | (uintptr_t)d_grad_out, &rc0);
-  if (rc0 != GAIB_OK) return rc0;
-  if (!use) {
-    gaib_set_error("gaib_gat_backward_fused: not applicable to this shape / graph (len %d, heads %d)", len, heads);
-    return GAIB_ERR_UNSUPPORTED;
-  }
-  if (!d_row_stats) GAIB_TRY(gaib_graph_ensure_rev(ctx, g));  // p[rev e] is read only when p is not formed again
-  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
-  const int nblocks = (int)(g->nv < 2048 ? cdiv64(g->nv, 8) : 1024);
-  const int64_t rows_per_block = cdiv64(g->nv, nblocks);
-  auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-  const size_t n_v = up4((size_t)g->nv * heads);
-  const size_t n_op = up4((size_t)g->n_chunks * len), n_rc = up4((size_t)g->n_chunks * 2 * heads);
-  // option gat_interleave: the three per-vertex tables of the sweep as one [h | grad | records] row per vertex
-  const int ldt = 2 * len + 4 * heads;
-  // round 6: the packed-math sweep (gat_bwd_fused_pk_kernel) over a table whose rows interleave h and grad element by element
-  // (option gat_bwd_pk = 1; off by default, see the kernel): attention formed again from the row statistics, heads of at most
-  // 16 lanes, a table below 4 GB (32-bit byte offsets)
-  const bool pk = d_row_stats != nullptr && ctx->gat_bwd_pk == 1 && (len / 4) / heads <= 16 &&
-                  (uint64_t)g->nv * (uint64_t)ldt * 4u < ((uint64_t)1 << 32);
-  const bool inter = !pk && ctx->gat_interleave == 1 && d_row_stats != nullptr;
-  const size_t n_t = (inter || pk) ? up4((size_t)g->nv * ldt) + 64 : 0;  // (+ 64 floats: the table starts on a 256-B boundary)
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (7 * n_v + n_op + n_rc + (size_t)nblocks * 2 * len + n_t)));
-  f4* rec = reinterpret_cast<f4*>(ctx->ws);  // [nv][H] 16-byte records (first: alignment)
-  float* rowdot = (float*)ctx->ws + 4 * n_v;
-  float* rs = rowdot + n_v;
-  float* cs = rs + n_v;
-  float* out_partial = cs + n_v;
-  float* rc_partial = out_partial + n_op;
-  float* partial = rc_partial + n_rc;
-  float* T = reinterpret_cast<float*>(((uintptr_t)(partial + (size_t)nblocks * 2 * len) + 255) & ~(uintptr_t)255);
-  ProfScope ps(ctx, "gat_bwd_fused", (double)g->ne * (4.0 + 2 * 4.0 * len + 12.0 * heads) + (double)g->n_chunks * (4.0 * len + 8.0 * heads) * 2 + (double)g->nv * 3 * 4.0 * len,
-               8.0 * (double)g->ne * len);
-  rowdot_kernel<<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, heads, d_grad, d_fwd_out, rowdot);
-  GAIB_LAUNCH_CHECK();
-  if (d_row_stats) {
-    const int64_t nrec = g->nv * (int64_t)heads;
-    gat_rec_kernel<<<(unsigned)cdiv64(nrec, 256), 256, 0, ctx->stream>>>(nrec, rowdot, reinterpret_cast<const float2*>(d_row_stats),
-                                                                        rec);
-    GAIB_LAUNCH_CHECK();
-  }
-  const float *k_feat = d_feat, *k_grad = d_grad;
-  const f4* k_rec = rec;
-  int k_ld = len, k_rec_ld = heads;
-  if (inter) {
-    const int64_t tot4 = g->nv * (int64_t)(ldt / 4);
-    gat_interleave_kernel<<<(unsigned)std::min<int64_t>(cdiv64(tot4, 256), (int64_t)ctx->num_cus * 16), 256, 0, ctx->stream>>>(
-        g->nv, len / 4, heads, reinterpret_cast<const f4*>(d_feat), reinterpret_cast<const f4*>(d_grad), rec,
-        reinterpret_cast<f4*>(T));
-    GAIB_LAUNCH_CHECK();
-    k_feat = T;
-    k_grad = T + len;
-    k_rec = reinterpret_cast<const f4*>(T + 2 * len);
-    k_ld = ldt;
-    k_rec_ld = ldt / 4;
-  }
-  unsigned grid = (unsigned)cdiv64(g->n_chunks, 4);
-  int per_xcd = 0;
-  if (ctx->gat_chunk_xcd == 1 && grid >= 64) {
-    per_xcd = (int)cdiv64(grid, 8);
-    grid = (unsigned)per_xcd * 8u;
-  }
-  if (pk) {
-    const int64_t tot4 = g->nv * (int64_t)(ldt / 4);
-    gat_interleave_pairs_kernel<<<(unsigned)std::min<int64_t>(cdiv64(tot4, 256), (int64_t)ctx->num_cus * 16), 256, 0, ctx->stream>>>(
-        g->nv, len / 4, heads, reinterpret_cast<const f4*>(d_feat), reinterpret_cast<const f4*>(d_grad), rec,
-        reinterpret_cast<f4*>(T));
-    GAIB_LAUNCH_CHECK();
-#define GAIB_FBP(GG, HH)                                                                                                        \
-  launch_bwd_pk<GG, HH, float>(grid, ctx->stream, g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, g->rowptr, g->colidx, len, T, \
-                        d_alpha_l, d_alpha_r, epsilon, out_partial, rc_partial, per_xcd)
-    GAIB_GAT_DISPATCH(GAIB_FBP);
-#undef GAIB_FBP
-    GAIB_LAUNCH_CHECK();
-  } else {
-  // edges in flight per group: 8 or 4 (option gat_fused_unroll)
-#define GAIB_FB_U(GG, HH, UU, RC)                                                                                          \
-  gat_bwd_fused_chunk_kernel<GG, HH, UU, RC, float><<<grid, 256, 0, ctx->stream>>>(                                               \
-      g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, g->rowptr, g->colidx, g->rev, len, k_feat, k_grad,        \
-      d_norm_scores, reinterpret_cast<const float2*>(d_row_stats), rowdot, d_alpha_l, d_alpha_r, epsilon, out_partial,     \
-      rc_partial, k_rec, -1, 0u, k_ld, k_rec_ld, per_xcd)
-  // (8 edges in flight per group is an option of the 64-wide form only, where it was measured)
-#define GAIB_FB(GG, HH)                                                      \
-  do {                                                                       \
-    if (d_row_stats) {                                                       \
-      if (GG == 16 && ctx->gat_fused_unroll == 8) GAIB_FB_U(16, HH, 8, true); \
-      else GAIB_FB_U(GG, HH, 4, true);                                       \
-    } else {                                                                 \
-      if (GG == 16 && ctx->gat_fused_unroll == 8) GAIB_FB_U(16, HH, 8, false); \
-      else GAIB_FB_U(GG, HH, 4, false);                                      \
-    }                                                                        \
-  } while (0)
-  GAIB_GAT_DISPATCH(GAIB_FB);
-#undef GAIB_FB
-#undef GAIB_FB_U
-  GAIB_LAUNCH_CHECK();
-  }
-#define GAIB_FRD(GG)                                                                                                   \
-  gat_fused_reduce_kernel<GG><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, heads, g->chunk_start, out_partial, \
-                                                                       rc_partial, d_grad_out, rs, cs)
-  if (len == 32) GAIB_FRD(8);
-  else if (len == 64) GAIB_FRD(16);
-  else GAIB_FRD(32);
-  GAIB_LAUNCH_CHECK();
-  alpha_partial_kernel<<<nblocks, 256, sizeof(float) * 512, ctx->stream>>>(g->nv, len, heads, d_feat, rs, cs,
-                                                                         rows_per_block, partial);
-  GAIB_LAUNCH_CHECK();
-  alpha_final_kernel<<<(unsigned)cdiv64(2 * (int64_t)len, 4), 256, 0, ctx->stream>>>(nblocks, len, partial, d_alpha_lgrad,
-                                                                                    d_alpha_rgrad);
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
+  return launch_alpha_grads(ctx, g->nv, len, heads, d_feat, rs, cs, partial, d_alpha_lgrad, d_alpha_rgrad);
 }
 
 extern "C" int gaib_gat_score_signs(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_alpha_l,
@@ -1270,105 +1027,6 @@ extern "C" int gaib_gat_score_signs(gaib_ctx* ctx, gaib_graph* g, int len, int h
                                                                g->colidx, len, d_h, d_alpha_l, d_alpha_r, d_sign_out)
   GAIB_GAT_DISPATCH(GAIB_SS);
 #undef GAIB_SS
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
-}
-
-// ---- the one-sweep backward on a rank's RECTANGULAR graph -------------------------------------------------
-// Everything row i needs about its edge (i -> c) and the reverse edge (c -> i) follows from per-VERTEX quantities of i and
-// c (h, grad, and the record (rowdot, row maximum, 1 / row sum)), and in a structurally symmetric graph the in-edges of i
-// are the reverses of its out-edges: so the rank that owns row i computes rs_i, cs_i and the aggregated gradient of i from
-// i's own edge list alone, given the halo vertices' h rows (still there from forward), grad rows and records.  No
-// transposed structure, no permuted [ne][H] copies, no reverse exchange of partial rows: two forward-direction halo
-// exchanges (grad rows, records) and one sweep.
-//   gaib_gat_backward_rec: the owned vertices' records  rec[v][h] = (<grad_v, out_v>_h, M_vh, 1/S_vh, 0)
-//   gaib_gat_backward_fused_rect: d_feat_tab / d_grad_tab [nc x len], d_rec_tab [nc][heads][4] with the owned rows first;
-//     phase as in gaib_gat_forward_fused_rect (0 reads owned rows only).  The alpha gradients cover the OWNED rows: the
-//     caller sums them over the ranks.
-extern "C" int gaib_gat_backward_rec(gaib_ctx* ctx, int64_t nv, int len, int heads, const float* d_grad, const float* d_fwd_out,
-                                     const float* d_row_stats, float* d_rec) {
-  GAIB_CHECK(ctx && (nv == 0 || (d_grad && d_fwd_out && d_row_stats && d_rec)), "gaib_gat_backward_rec: NULL argument");
-  GAIB_TRY(check_heads("gaib_gat_backward_rec", len, heads));
-  if (nv <= 0) return GAIB_OK;
-  GAIB_HIP(hipSetDevice(ctx->device));
-  const size_t n_v = ((size_t)nv * heads + 3) & ~(size_t)3;
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * n_v));
-  float* rowdot = (float*)ctx->ws;
-  rowdot_kernel<<<rowgrid(nv), 256, 0, ctx->stream>>>(nv, len, heads, d_grad, d_fwd_out, rowdot);
-  GAIB_LAUNCH_CHECK();
-  const int64_t nrec = nv * (int64_t)heads;
-  gat_rec_kernel<<<(unsigned)cdiv64(nrec, 256), 256, 0, ctx->stream>>>(nrec, rowdot, reinterpret_cast<const float2*>(d_row_stats),
-                                                                      reinterpret_cast<f4*>(d_rec));
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
-}
-
-extern "C" int gaib_gat_backward_fused_rect(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat_tab,
-                                            const float* d_grad_tab, const float* d_rec_tab, const float* d_alpha_l,
-                                            const float* d_alpha_r, float epsilon, float* d_grad_out, float* d_alpha_lgrad,
-                                            float* d_alpha_rgrad, int phase) {
-  GAIB_CHECK(ctx && g, "gaib_gat_backward_fused_rect: NULL ctx/graph");
-  GAIB_TRY(check_heads("gaib_gat_backward_fused_rect", len, heads));
-  if (g->nv == 0) {  // a rank without rows: zero alpha gradients (they are summed over the ranks afterwards), nothing else
-    GAIB_CHECK(phase >= -1 && phase <= 1, "gaib_gat_backward_fused_rect: phase is -1, 0 or 1");
-    if (!(gat_fused_shape(len, heads) && ctx->gat_fused_bwd != 0)) {
-      gaib_set_error("gaib_gat_backward_fused_rect: not applicable to this shape / graph (len %d, heads %d)", len, heads);
-      return GAIB_ERR_UNSUPPORTED;  // (the decision of the ranks WITH rows: shape and option alone, see the forward)
-    }
-    if (phase != 0) {
-      GAIB_HIP(hipSetDevice(ctx->device));
-      if (d_alpha_lgrad) GAIB_HIP(hipMemsetAsync(d_alpha_lgrad, 0, sizeof(float) * len, ctx->stream));
-      if (d_alpha_rgrad) GAIB_HIP(hipMemsetAsync(d_alpha_rgrad, 0, sizeof(float) * len, ctx->stream));
-    }
-    return GAIB_OK;
-  }
-  GAIB_CHECK(d_feat_tab && d_grad_tab && d_rec_tab && d_alpha_l && d_alpha_r && d_grad_out && d_alpha_lgrad && d_alpha_rgrad,
-             "gaib_gat_backward_fused_rect: NULL pointer");
-  GAIB_CHECK(d_grad_out != d_feat_tab && d_grad_out != d_grad_tab, "gaib_gat_backward_fused_rect: d_grad_out must not alias an input");
-  GAIB_CHECK(phase >= -1 && phase <= 1, "gaib_gat_backward_fused_rect: phase is -1, 0 or 1");
-  GAIB_HIP(hipSetDevice(ctx->device));
-  int rc0 = GAIB_OK;
-  const bool use = gat_fused_applies(ctx, g, len, heads, ctx->gat_fused_bwd,
-                                     (uintptr_t)d_feat_tab | (uintptr_t)d_grad_tab | (uintptr_t)d_rec_tab | (uintptr_t)d_grad_out,
-                                     &rc0, true);
-  if (rc0 != GAIB_OK) return rc0;
-  if (!use) {
-    gaib_set_error("gaib_gat_backward_fused_rect: not applicable to this shape / graph (len %d, heads %d)", len, heads);
-    return GAIB_ERR_UNSUPPORTED;
-  }
-  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
-  const int nblocks = (int)(g->nv < 2048 ? cdiv64(g->nv, 8) : 1024);
-  const int64_t rows_per_block = cdiv64(g->nv, nblocks);
-  auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-  const size_t n_v = up4((size_t)g->nv * heads);
-  const size_t n_op = up4((size_t)g->n_chunks * len), n_rc = up4((size_t)g->n_chunks * 2 * heads);
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (2 * n_v + n_op + n_rc + (size_t)nblocks * 2 * len)));
-  float* rs = (float*)ctx->ws;
-  float* cs = rs + n_v;
-  float* out_partial = cs + n_v;
-  float* rc_partial = out_partial + n_op;
-  float* partial = rc_partial + n_rc;
-  ProfScope ps(ctx, "gat_bwd_fused", (double)g->ne * (4.0 + 2 * 4.0 * len + 12.0 * heads) + (double)g->n_chunks * (4.0 * len + 8.0 * heads) * 2 + (double)g->nv * 3 * 4.0 * len,
-               8.0 * (double)g->ne * len);
-  const unsigned grid = (unsigned)cdiv64(g->n_chunks, 4);
-#define GAIB_FBR(GG, HH)                                                                                                   \
-  if (grid > 0) gat_bwd_fused_chunk_kernel<GG, HH, 4, true, float><<<grid, 256, 0, ctx->stream>>>(                                              \
-      g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start, g->rowptr, g->colidx, nullptr, len, d_feat_tab, d_grad_tab, \
-      nullptr, nullptr, nullptr, d_alpha_l, d_alpha_r, epsilon, out_partial, rc_partial,                                   \
-      reinterpret_cast<const f4*>(d_rec_tab), phase, (uint32_t)g->nv, len, HH, 0)
-  GAIB_GAT_DISPATCH(GAIB_FBR);
-#undef GAIB_FBR
-  GAIB_LAUNCH_CHECK();
-  if (phase == 0) return GAIB_OK;
-  if (len == 32) GAIB_FRD(8);
-  else if (len == 64) GAIB_FRD(16);
-  else GAIB_FRD(32);
-  GAIB_LAUNCH_CHECK();
-  alpha_partial_kernel<<<nblocks, 256, sizeof(float) * 512, ctx->stream>>>(g->nv, len, heads, d_feat_tab, rs, cs,
-                                                                         rows_per_block, partial);
-  GAIB_LAUNCH_CHECK();
-  alpha_final_kernel<<<(unsigned)cdiv64(2 * (int64_t)len, 4), 256, 0, ctx->stream>>>(nblocks, len, partial, d_alpha_lgrad,
-                                                                                    d_alpha_rgrad);
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }
@@ -1471,17 +1129,8 @@ extern "C" int gaib_gat_alpha_grads(gaib_ctx* ctx, int64_t nv, int len, int head
     return GAIB_OK;
   }
   GAIB_CHECK(d_x && d_rs && d_cs, "gaib_gat_alpha_grads: NULL pointer");
-  const int nblocks = (int)(nv < 2048 ? cdiv64(nv, 8) : 1024);
-  const int64_t rows_per_block = cdiv64(nv, nblocks);
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (size_t)nblocks * 2 * len));
-  float* partial = (float*)ctx->ws;
-  alpha_partial_kernel<<<nblocks, 256, sizeof(float) * 512, ctx->stream>>>(nv, len, heads, d_x, d_rs, d_cs,
-                                                                         rows_per_block, partial);
-  GAIB_LAUNCH_CHECK();
-  alpha_final_kernel<<<(unsigned)cdiv64(2 * (int64_t)len, 4), 256, 0, ctx->stream>>>(nblocks, len, partial, d_alpha_lgrad,
-                                                                                    d_alpha_rgrad);
-  GAIB_LAUNCH_CHECK();
-  return GAIB_OK;
+  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (size_t)gat_alpha_blocks(nv) * 2 * len));
+  return launch_alpha_grads(ctx, nv, len, heads, d_x, d_rs, d_cs, (float*)ctx->ws, d_alpha_lgrad, d_alpha_rgrad);
 }
 
 extern "C" int gaib_gat_softmax_bwd_alpha_ex(gaib_ctx* ctx, gaib_graph* g, int len, int heads,

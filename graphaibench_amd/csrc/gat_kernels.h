@@ -1,13 +1,14 @@
 // gat_kernels.h -- the GAT kernels that more than one translation unit instantiates: the one-sweep forward and backward
 // (chunk kernels, the packed-math sweep, their reductions), the per-vertex dots and the alpha-gradient reduction, with the
-// shape rules and dispatch macros of their callers.  gat.hip instantiates them on fp32 tables, gat_bf16.hip on bf16 tables
-// (element type E = uint16_t: raw bf16 bits, loaded as they are and widened where they are consumed), gat_drop.hip the DROP
-// variants of the two sweeps (attention dropout, fp32 tables), gat_wide.hip the WIDE variants (rows of a table whose row stride is
-// not the row width: one column slab of a wider multi-head row), gat_wide_bf16.hip the DROP / WIDE / WIN variants on bf16 tables.
-// WIDE: a template flag with trailing, defaulted stride arguments read only behind `WIDE ? ld : len` -- the other instantiations
-// compile to the instructions they had (the arguments sit behind every argument those read).
-// WIN (gat_wide.hip, the dropped sweeps on a slab): the dropout mask's index takes the FULL row's head count and the slab's first
-// head from two more trailing arguments (gat_drop_bits); forward: DROP && WIDE, backward: a template flag of its own.
+// shape rules and dispatch macros of their callers.  The host sequences that launch the one-sweep kernels are gat_fused_seq.h,
+// included by gat_fused.hip (fp32 tables: the plain, DROP, WIDE and WIN forms) and by gat_bf16.hip (element type E = uint16_t:
+// raw bf16 bits, loaded as they are and widened where they are consumed); gat.hip holds the staged path.
+// DROP: attention dropout inside the two sweeps.
+// WIDE: rows of a table whose row stride is not the row width (one column slab of a wider multi-head row) -- a template flag with
+// trailing, defaulted stride arguments read only behind `WIDE ? ld : len`: the other instantiations compile to the instructions
+// they had (the arguments sit behind every argument those read).
+// WIN (the dropped sweeps on a slab): the dropout mask's index takes the FULL row's head count and the slab's first head from
+// two more trailing arguments (gat_drop_bits); forward: DROP && WIDE, backward: a template flag of its own.
 #pragma once
 #include "common.h"
 
@@ -275,9 +276,9 @@ __device__ __forceinline__ uint32_t gat_drop_bits(int lane, int n, int64_t eb, c
   return lanes_or<LH>(bits);
 }
 
-// DROP (gat_drop.hip; RECOMP form): attention dropout inside the sweep, see gat_drop_bits; rev is then read for the reverse edges' masks.
+// DROP (RECOMP form): attention dropout inside the sweep, see gat_drop_bits; rev is then read for the reverse edges' masks.
 // The three trailing arguments are the DROP form's; the others' launches leave them to their defaults.
-// WIN (gat_wide.hip; DROP form): the masks' index window, see gat_drop_bits; its two arguments trail the DROP form's.
+// WIN (DROP form): the masks' index window, see gat_drop_bits; its two arguments trail the DROP form's.
 template <int G, int H, int U, bool RECOMP, typename E, bool DROP = false, bool WIN = false>
 __global__ __launch_bounds__(256) void gat_bwd_fused_chunk_kernel(
     int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase, const uint32_t* chunk_start,
@@ -697,9 +698,9 @@ __global__ __launch_bounds__(256) void gat_bwd_fused_pk_kernel(int64_t n_chunks,
 // written: backward forms p again from stats[v][h] = (M, 1/S) (gat_bwd_fused_chunk_kernel<RECOMP>).
 constexpr float GAT_NEG = -1.0e30f;  // "no edge yet": finite, so exp(NEG - m) = 0 and NEG - NEG = 0 (not NaN)
 
-// DROP (gat_drop.hip): out_i = sum_e p_e w_e h_c with w = mask . scale (gat_drop_bits); (m, ssum) and so the row statistics are the
+// DROP: out_i = sum_e p_e w_e h_c with w = mask . scale (gat_drop_bits); (m, ssum) and so the row statistics are the
 // undropped softmax's.  The three trailing arguments are the DROP form's.
-// WIDE (gat_wide.hip): feat has rows of ld elements of which this launch sweeps len = 4 G; the partials stay len wide.
+// WIDE: feat has rows of ld elements of which this launch sweeps len = 4 G; the partials stay len wide.
 // DROP && WIDE: the masks' index window (gat_drop_bits<.., WIN>) from the two arguments behind ld.
 template <int G, int H, int U, typename E, bool DROP = false, bool WIDE = false>
 __global__ __launch_bounds__(256) void gat_fwd_fused_chunk_kernel(
@@ -919,6 +920,14 @@ static bool gat_fused_shape(int len, int heads) {
     else { GAIB_GAT_BY_HEADS(32, M, M(32, 16)) }                \
   } while (0)
 
+static size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }  // keep every part of a workspace 16-byte aligned
+
+static int check_heads(const char* who, int len, int heads) {
+  GAIB_CHECK(len > 0, "%s: len must be > 0", who);
+  GAIB_CHECK(heads >= 1 && len % heads == 0, "%s: heads (%d) must divide len (%d)", who, heads, len);
+  return GAIB_OK;
+}
+
 // the packed-math sweep for the shapes it covers (a head of at most 16 lanes); the others never get here (see `pk` below)
 template <int G, int H, typename E>
 static void launch_bwd_pk(unsigned grid, hipStream_t st, int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
@@ -957,4 +966,19 @@ static bool gat_fused_applies(gaib_ctx* ctx, gaib_graph* g, int len, int heads, 
   // outside gat_fused_shape(), attention dropout and the explicit option.
   const bool shape_ok = heads_ok && g->nc == g->nv && g->ne > 0 && (align_or & 15) == 0;
   return shape_ok && knob != 0;
+}
+
+// alpha_l' = sum_v rs[v] x[v], alpha_r' = sum_v cs[v] x[v]: partial sums over gat_alpha_blocks(nv) strips of rows (partial:
+// [blocks][2][len] floats), then one wave per output element.  WIDE: x has rows of ld elements.
+static int gat_alpha_blocks(int64_t nv) { return (int)(nv < 2048 ? cdiv64(nv, 8) : 1024); }
+template <typename E, bool WIDE = false>
+static int launch_alpha_grads(gaib_ctx* ctx, int64_t nv, int len, int heads, const E* d_x, const float* rs, const float* cs,
+                              float* partial, float* d_alpha_lgrad, float* d_alpha_rgrad, int ld = 0) {
+  const int nblocks = gat_alpha_blocks(nv);
+  alpha_partial_kernel<E, WIDE><<<nblocks, 256, sizeof(float) * 512, ctx->stream>>>(nv, len, heads, d_x, rs, cs, cdiv64(nv, nblocks),
+                                                                                  partial, ld);
+  GAIB_LAUNCH_CHECK();
+  alpha_final_kernel<<<(unsigned)cdiv64(2 * (int64_t)len, 4), 256, 0, ctx->stream>>>(nblocks, len, partial, d_alpha_lgrad, d_alpha_rgrad);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
 }
