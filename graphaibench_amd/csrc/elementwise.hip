@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void f1_counts_kernel(int num_cls, int64_t beg
     const uint8_t y = labels[idx];
     tp += (y == 1 && hot);
     fp += (y == 0 && hot);
-    fn += (y == 1 && !hot);
+    fn += (y == 1 && preds[idx] <= 0.5f);  // (not `!hot`: a NaN prediction is neither, math_functions.cpp:596)
   }
   __shared__ unsigned s[3];
   if (threadIdx.x < 3) s[threadIdx.x] = 0;
@@ -334,6 +334,13 @@ __global__ __launch_bounds__(256) void d_l2norm_kernel(int64_t n, int dim, const
   s2 = wave_sum(s2);
   c0 = wave_sum(c0);
   s2 = s2 < 1.0e-12f ? 1.0e-12f : s2;
+  if (s2 > 1.0e25f) {
+    // s2^-1.5 is below the smallest normal fp32 from 1.9e25 on and below the smallest subnormal from 8e29 on: the row's
+    // gradient (about g / |x|, an ordinary number) came out as 0.  The same expression with the coefficient in two factors.
+    const float rs = 1.0f / sqrtf(s2), q = c0 / s2;
+    for (int c = lane; c < dim; c += 64) gout[i * (int64_t)dim + c] = (x[c] * q + g[c]) * rs;
+    return;
+  }
   const float c1 = powf(s2, -1.5f);
   for (int c = lane; c < dim; c += 64)
     gout[i * (int64_t)dim + c] = x[c] * c0 * c1 + g[c] * s2 * c1;
