@@ -628,7 +628,13 @@ __global__ __launch_bounds__(256, 1) void sgemm_tn_glds_kernel(GemmArgs g) {
   auto finish_pair = [&](int t, int s, f4 (&fa)[NS], f4 (&fb)[NS], f4 (&mk)[NS]) {
     const int64_t k = ((int64_t)t * W + team) * TG_R + 2 * s + h;
     const bool live = t < mine && k < g.K;
-    fa[s] = live ? fa[s] : zero4;  // rows past K (the matrix's last set) and stages past the team's end contribute nothing
+    // rows past K (the matrix's last set, which is its team's last) and stages past the team's end contribute nothing.  BOTH
+    // operands are selected: row K - 1 of B, read again for them, may hold an Inf, and 0 * Inf = NaN.  Every stage before the
+    // team's last holds whole sets: the test is scalar and the selects stay out of their MFMA shadow
+    if (t >= mine - 1) {
+      fa[s] = live ? fa[s] : zero4;
+      fb[s] = live ? fb[s] : zero4;
+    }
     if constexpr (BMASK) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) fb[s][e] = mk[s][e] > 0.f ? fb[s][e] : 0.f;  // d_relu (math_functions.cu:258-268)

@@ -53,8 +53,8 @@ __device__ __forceinline__ f4 mfma16(float a, float b, f4 c) { return __builtin_
 // 16-byte load, and the four MFMA steps (g, t) pair element t of it with op(B)[4 (4g + q) + t][:] -- held in registers.  E: one
 // more step whose lanes take ONE column each (k = 16 G + q; K = 100 = 6 groups + 1 step).  A chunk that would straddle the end
 // of a row (K = 47: chunk 11) starts 4 - K % 4 columns further left instead; the columns it then shares with its neighbour
-// meet zeros in the B registers.  Chunks past the row likewise re-read the row's first chunk against zeros.  No load ever
-// leaves its row.
+// meet zeros in the B registers and are themselves selected to zero (RAGGED below).  Chunks past the row likewise re-read the
+// row's first chunk, selected to zero against zeros.  No load ever leaves its row.
 // MFMA operands: a = op(B) fragment (i = column 16 ct + j of the output), b = A fragment (j = row of the tile)
 //   => D[i][j] in lane (j, q), register r = C[row j][16 ct + 4 q + r].
 // Epilogue, two forms, both with a FIXED number of memory instructions per tile (a store under a branch makes the compiler wait
@@ -73,6 +73,12 @@ __global__ __launch_bounds__(256, WPS) void skinny_rows_kernel(SkinnyArgs g) {
   int kb[G > 0 ? G : 1];
   float breg[G > 0 ? G : 1][4][CT];
   float bx[E ? CT : 1];
+  // RAGGED: the 33 .. 48-column forms (G = 3), the only ones whose K need not be 16 G + 4 E.  Their shifted and re-read chunks
+  // carry elements of A that belong to no step of this lane: bit 4 gg + t of `alive` says whether element t of chunk gg does, and
+  // the element is SELECTED before the MFMA -- against the zero in breg alone an Inf in the row's first or last columns would
+  // come out as NaN (0 * Inf) where the product is Inf
+  constexpr bool RAGGED = G == 3;
+  unsigned alive = 0;
 #pragma unroll
   for (int gg = 0; gg < G; ++gg) {
     const int c = 4 * gg + q;
@@ -83,6 +89,7 @@ __global__ __launch_bounds__(256, WPS) void skinny_rows_kernel(SkinnyArgs g) {
     for (int t = 0; t < 4; ++t) {
       const int k = base + t;
       const bool live = valid && k >= 4 * c;
+      alive |= live ? 1u << (4 * gg + t) : 0u;
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         const int n = 16 * ct + j;
@@ -179,9 +186,12 @@ __global__ __launch_bounds__(256, WPS) void skinny_rows_kernel(SkinnyArgs g) {
 #pragma unroll
       for (int gg = 0; gg < G; ++gg)
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t) {
+          float av = buf[s][rt][gg][t];
+          if constexpr (RAGGED) av = (alive >> (4 * gg + t)) & 1u ? av : 0.f;
 #pragma unroll
-          for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma16(breg[gg][t][ct], buf[s][rt][gg][t], acc[ct]);
+          for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma16(breg[gg][t][ct], av, acc[ct]);
+        }
       if constexpr (E) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc[ct] = mfma16(bx[ct], bufx[s][rt], acc[ct]);
