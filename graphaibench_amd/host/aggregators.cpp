@@ -13,18 +13,20 @@ static gaib_graph* dev(Graph& g) {
   if (!g.device_graph()) g.copy_to_gpu();
   return g.device_graph();
 }
+// a device buffer of the aggregator that only grows: `need` elements above `cap` -> free, allocate, remember (contents are lost).
+// Returns whether it did.  (Two buffers that share one capacity: the first grows against a copy of it.)
+template <class T>
+static bool grow(T*& p, size_t& cap, size_t need) {
+  if (need <= cap) return false;
+  if (p) GAIB_OR_DIE(gaib_free(C(), p));
+  p = gaib_host::dmalloc<T>(need);
+  cap = need;
+  return true;
+}
 
 // ---- bf16 feature tables (option agg_bf16) ------------------------------------------------------------------------------
-bool aggregator::bf16_tables() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "agg_bf16", &v));
-  return v != 0;
-}
-bool aggregator::gemm_bf16_products() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "gemm_bf16", &v));
-  return v != 0;
-}
+bool aggregator::bf16_tables() { return gaib_host::option("agg_bf16") != 0; }
+bool aggregator::gemm_bf16_products() { return gaib_host::option("gemm_bf16") != 0; }
 // One process-wide scratch.  A buffer that has to grow is kept, not freed: a recorded epoch (gaib_exec) may still name it.
 static uint16_t* g_bf16_tab = nullptr;
 static size_t g_bf16_cap = 0;
@@ -100,21 +102,9 @@ static const unsigned ZS_PROBE_EVERY = 8;
 // kernel level (8.83 -> 8.14 ms at 50 % kept, pack included; LEDGER 10.4), but it has not been measured on the SAGE layer step in
 // alternating pairs, and tests/test_gpu_zs.py holds SAGE to the dense gather: until both are settled SAGE gathers dense.
 static const bool ZS_TWO_PRODUCTS = false;
-bool aggregator::zs_tables() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs", &v));
-  return v != 0;
-}
-bool aggregator::zs_wide_tables() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs_wide", &v));
-  return v != 0;
-}
-bool aggregator::zs_paused() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "agg_zs_paused", &v));
-  return v != 0;
-}
+bool aggregator::zs_tables() { return gaib_host::option("agg_zs") != 0; }
+bool aggregator::zs_wide_tables() { return gaib_host::option("agg_zs_wide") != 0; }
+bool aggregator::zs_paused() { return gaib_host::option("agg_zs_paused") != 0; }
 // The guard's state is kept PER GATHERED TABLE (the layer's grad_in buffer): in a model, the count one layer's pack left behind
 // says nothing about the next layer's gradient.  Each table has its own device counter and pinned host word.
 static const int ZS_SLOTS = 16;  // tables watched at a time (a deeper model shares slots round robin: counts then mix)
@@ -199,17 +189,50 @@ static void zs_set_paused(int slot, bool p) {
   GAIB_OR_DIE(gaib_set_option(C(), "agg_zs_paused", any ? 1 : 0));
 }
 
-// The halo-column half of a partitioned aggregation over `whole` (the mode's halo-column graph): in one pass after the whole
-// exchange -- last(whole, table) --, or, where the exchange travels in K > 1 time slices (gaib_halo_set_pieces), piece by piece
-// as the slices land: plain(piece k, table) in accumulate mode for every piece but the last non-empty one, which takes last()
-// (the pass that carries the activation / the dense product).  Same terms per row, added piece by piece.  Ends the exchange.
-// T: element type of the exchanged table (float, or uint16_t = bf16 bits: the exchange was begun with halo_begin_bf16).
+// ---- aggregation on a vertex-range partition ---------------------------------------------------------------------------------
+// Written once on T, the element type of the gathered and exchanged table: float, or uint16_t = bf16 bits (agg_bf16, even len).
+// What differs by type is this set of functions and nothing else: the exchange calls, the plain gather and the gather with the
+// dense product(s) riding on it.  Both gathers run `dg` over `tab`, or -- tab2 given -- in one pass over [tab (n_first rows) | tab2].
+static void halo_begin_t(Graph& g, int len, const float* tab) { g.halo_begin(len, tab); }
+static void halo_begin_t(Graph& g, int len, const uint16_t* tab) { g.halo_begin_bf16(len, tab); }
 static const float* halo_end_t(Graph& g, int len, const float*) { return g.halo_end(len); }
 static const uint16_t* halo_end_t(Graph& g, int len, const uint16_t*) { return g.halo_end_bf16(len); }
 static const float* halo_wait_t(Graph& g, int k, const float*) { return g.halo_wait_piece(k); }
 static const uint16_t* halo_wait_t(Graph& g, int k, const uint16_t*) { return g.halo_wait_piece_bf16(k); }
+static void gather_t(gaib_graph* dg, int kind, int len, const float* tab, const float* tab2, int64_t n_first, float* out, int fl) {
+  if (tab2 || n_first > 0) GAIB_OR_DIE(gaib_spmm_2t(C(), dg, kind, NULL, len, tab, tab2, n_first, out, fl));
+  else GAIB_OR_DIE(gaib_spmm_ex(C(), dg, kind, NULL, len, tab, out, fl));
+}
+static void gather_t(gaib_graph* dg, int kind, int len, const uint16_t* tab, const uint16_t* tab2, int64_t n_first, float* out, int fl) {
+  GAIB_OR_DIE(gaib_spmm_part_bf16(C(), dg, kind, NULL, len, tab, tab2, n_first, out, fl));
+}
+// the dense half of aggregate_then_matmul: out = act(agg . op(W) [+ rows2 . op(W2)]), len_out columns
+struct Product {
+  float* agg;
+  const float* W;
+  int transW;
+  const float *rows2, *W2;
+  int len_out;
+  float* out;
+};
+static void fused_t(gaib_graph* dg, int kind, int len, const float* tab, const float* tab2, int64_t n_first, const Product& p, int fl) {
+  if (tab2 || n_first > 0)
+    GAIB_OR_DIE(gaib_spmm_gemm_2t(C(), dg, kind, NULL, len, tab, tab2, n_first, p.agg, p.W, p.transW, p.rows2, p.W2, p.len_out, p.out, fl));
+  else if (p.rows2)
+    GAIB_OR_DIE(gaib_spmm_gemm2(C(), dg, kind, NULL, len, tab, p.agg, p.W, p.transW, p.rows2, p.W2, p.len_out, p.out, fl));
+  else
+    GAIB_OR_DIE(gaib_spmm_gemm(C(), dg, kind, NULL, len, tab, p.agg, p.W, p.transW, p.len_out, p.out, fl));
+}
+static void fused_t(gaib_graph* dg, int kind, int len, const uint16_t* tab, const uint16_t* tab2, int64_t n_first, const Product& p, int fl) {
+  GAIB_OR_DIE(gaib_spmm_gemm_part_bf16(C(), dg, kind, NULL, len, tab, tab2, n_first, p.agg, p.W, p.transW, p.rows2, p.W2, p.len_out, p.out, fl));
+}
+
+// The halo-column half of a partitioned aggregation over `whole` (the mode's halo-column graph): in one pass after the whole
+// exchange -- last(whole, table) --, or, where the exchange travels in K > 1 time slices (gaib_halo_set_pieces), piece by piece
+// as the slices land: plain(piece k, table) in accumulate mode for every piece but the last non-empty one, which takes last()
+// (the pass that carries the activation / the dense product).  Same terms per row, added piece by piece.  Ends the exchange.
 template <class T, class Plain, class Last>
-static void halo_half_t(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
+static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
   const int K = g.halo_pieces(len);
   if (K <= 1) {
     last(whole, halo_end_t(g, len, (const T*)NULL));
@@ -222,99 +245,72 @@ static void halo_half_t(Graph& g, gaib_graph* whole, int len, Plain plain, Last 
     if (gaib_graph_ne(g.halo_piece_graph(k)) > 0) plain(g.halo_piece_graph(k), halo_wait_t(g, k, (const T*)NULL));
   last(g.halo_piece_graph(last_k), halo_end_t(g, len, (const T*)NULL));  // (pieces behind last_k are empty: waiting for all of them costs nothing)
 }
-template <class Plain, class Last>
-static void halo_half(Graph& g, gaib_graph* whole, int len, Plain plain, Last last) {
-  halo_half_t<float>(g, whole, len, plain, last);
-}
 
-// aggregate_rows on a partition with bf16 tables (agg_bf16, even len): the branch below with the same call structure and flags.
-// The owned rows are cast into the bf16 scratch ONCE -- the owned-column pass gathers from it -- and the exchange is begun FROM
-// that scratch (half the bytes packed and on the wire; over RCCL a contiguous send list is read straight from it), which no other
-// cast touches before the exchange has ended: every path below ends it before it returns.
-static void aggregate_rows_bf16_part(Graph& g, int kind, int len, const float* in, float* out, int act) {
-  gaib_graph* own = dev(g);
-  const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(own), len, in);
-  auto ex = [&](gaib_graph* gg, const uint16_t* t, int fl) {
-    GAIB_OR_DIE(gaib_spmm_part_bf16(C(), gg, kind, NULL, len, t, NULL, 0, out, fl));
-  };
-  auto acc = [&](gaib_graph* gh, const uint16_t* halo) { ex(gh, halo, GAIB_ACCUMULATE); };
-  auto acc_act = [&](gaib_graph* gh, const uint16_t* halo) { ex(gh, halo, GAIB_ACCUMULATE | act); };
-  const int mode = g.partition_mode(len);
-  g.halo_begin_bf16(len, tab);
-  if (mode != Graph::PART_SPLIT) {
-    ex(g.class_interior(), tab, act);
-    if (mode == Graph::PART_CLASSES) {
-      const bool have_halo_edges = gaib_graph_ne(g.class_boundary_halo()) > 0;  // (else: no boundary row either)
-      ex(g.class_boundary_own(), tab, have_halo_edges ? 0 : act);
-      if (have_halo_edges) halo_half_t<uint16_t>(g, g.class_boundary_halo(), len, acc, acc_act);
-      else g.halo_end_bf16(len);
-    } else {
-      const uint16_t* halo = g.halo_end_bf16(len);
-      GAIB_OR_DIE(gaib_spmm_part_bf16(C(), g.class_boundary_full(), kind, NULL, len, tab, halo, (int64_t)g.size(), out, act));
-    }
-    return;
-  }
-  const bool have_halo_edges = gaib_graph_ne(g.halo_graph()) > 0;
-  ex(own, tab, have_halo_edges ? 0 : act);
-  if (!have_halo_edges) {
-    g.halo_end_bf16(len);
-    return;
-  }
-  halo_half_t<uint16_t>(g, g.halo_graph(), len, acc, acc_act);
-}
-
-// One aggregation.  On a vertex-range partition the work that needs no halo row runs while the halo rows are in flight
-// (separate RCCL stream), the rest after they have arrived -- by row class (LearningGraph::partition_mode):
+// One partitioned aggregation of the owned rows over `tab` (the owned table; the exchange is begun from it, so with bf16 tables
+// nothing else may be cast into the scratch before it has ended: every path below ends it before it returns).  The work that needs
+// no halo row runs while the halo rows are in flight (separate RCCL stream), the rest after they have arrived -- by row class
+// (LearningGraph::partition_mode):
 //   PART_SPLIT    owned-column edges of all rows meanwhile, halo-column edges added to the same rows after
 //   PART_CLASSES  interior rows complete + the boundary rows' owned-column edges meanwhile, their halo-column edges after
 //   PART_ONEPASS  interior rows complete meanwhile, the boundary rows in one pass over [owned | halo] after
+// Partial sums go to `sums` through the plain gather.  final(graph, tab, tab2, n_first, extra) is the caller's pass that completes
+// rows (it carries the activation / the dense product); extra = GAIB_ACCUMULATE where it continues partial sums,
+// GAIB_OVERLAPS_TRANSFER while rows are on the wire.  Without halo-column edges the rows that could have had some are completed in
+// flight: all owned rows (split), or -- classes, only if empty_boundary_class -- the boundary class, which is then empty.
+template <class T, class Final>
+static void partitioned(Graph& g, int kind, int len, const T* tab, float* sums, bool empty_boundary_class, Final final) {
+  const T* const none = NULL;
+  const int mode = g.partition_mode(len);
+  halo_begin_t(g, len, tab);  // every rank joins every exchange, also one without halo edges
+  if (mode != Graph::PART_SPLIT) {
+    final(g.class_interior(), tab, none, 0, GAIB_OVERLAPS_TRANSFER);  // (the exchange is in flight: RCCL's kernels need CUs)
+    if (mode != Graph::PART_CLASSES) {
+      const T* halo = halo_end_t(g, len, none);
+      final(g.class_boundary_full(), tab, halo, (int64_t)g.size(), 0);
+      return;
+    }
+  }
+  gaib_graph* half = mode == Graph::PART_SPLIT ? g.halo_graph() : g.class_boundary_halo();
+  gaib_graph* meanwhile = mode == Graph::PART_SPLIT ? dev(g) : g.class_boundary_own();
+  if (gaib_graph_ne(half) == 0) {  // (classes: no boundary row either)
+    if (mode == Graph::PART_SPLIT || empty_boundary_class) final(meanwhile, tab, none, 0, GAIB_OVERLAPS_TRANSFER);
+    halo_end_t(g, len, none);
+    return;
+  }
+  // owned-column edges while the halo rows travel; the halo-column edges then continue the sums
+  gather_t(meanwhile, kind, len, tab, none, 0, sums, 0);
+  halo_half<T>(g, half, len, [&](gaib_graph* gh, const T* halo) { gather_t(gh, kind, len, halo, none, 0, sums, GAIB_ACCUMULATE); },
+               [&](gaib_graph* gh, const T* halo) { final(gh, halo, none, 0, GAIB_ACCUMULATE); });
+}
+
+// the owned rows of a partitioned graph cast into the bf16 scratch ONCE: the owned-column passes gather from it and the exchange is
+// begun FROM it (half the bytes packed and on the wire; over RCCL a contiguous send list is read straight from it)
+static const uint16_t* owned_bf16(Graph& g, int len, const float* in) { return to_bf16((size_t)gaib_graph_nc(dev(g)), len, in); }
+
+// One aggregation.  On a partition every pass is the plain gather: the final one adds the activation (it runs no kernel that
+// yields CUs to the transport, so of `extra` it takes the accumulate bit alone), and an empty boundary class is still launched.
 static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* out, bool relu = false, bool count = true) {
   if (count) count_edges(g);
   const int act = relu ? GAIB_RELU : 0;
-  if (bf16_for(g, len)) {
-    if (g.has_halo()) {
-      aggregate_rows_bf16_part(g, kind, len, in, out, act);
-      return;
-    }
+  const bool bf16 = bf16_for(g, len);
+  if (g.has_halo()) {
+    auto run = [&](auto tab) {
+      partitioned(g, kind, len, tab, out, true, [&](gaib_graph* dg, decltype(tab) t, decltype(tab) t2, int64_t n_first, int extra) {
+        gather_t(dg, kind, len, t, t2, n_first, out, act | (extra & GAIB_ACCUMULATE));
+      });
+    };
+    if (bf16) run(owned_bf16(g, len, in));
+    else run(in);
+    return;
+  }
+  if (bf16) {
     gaib_graph* dg = dev(g);
     int64_t ld = len;
     const uint16_t* tab = to_bf16(dg, len, in, &ld);
     GAIB_OR_DIE(gaib_spmm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, out, act));
     return;
   }
-  if (!g.has_halo()) {
-    GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, out, act));
-    return;
-  }
-  const int mode = g.partition_mode(len);
-  auto acc = [&](gaib_graph* gh, const float* halo) {
-    GAIB_OR_DIE(gaib_spmm_ex(C(), gh, kind, NULL, len, halo, out, GAIB_ACCUMULATE));
-  };
-  auto acc_act = [&](gaib_graph* gh, const float* halo) {
-    GAIB_OR_DIE(gaib_spmm_ex(C(), gh, kind, NULL, len, halo, out, GAIB_ACCUMULATE | act));
-  };
-  if (mode != Graph::PART_SPLIT) {
-    g.halo_begin(len, in);
-    GAIB_OR_DIE(gaib_spmm_ex(C(), g.class_interior(), kind, NULL, len, in, out, act));
-    if (mode == Graph::PART_CLASSES) {
-      const bool have_halo_edges = gaib_graph_ne(g.class_boundary_halo()) > 0;  // (else: no boundary row either)
-      GAIB_OR_DIE(gaib_spmm_ex(C(), g.class_boundary_own(), kind, NULL, len, in, out, have_halo_edges ? 0 : act));
-      if (have_halo_edges) halo_half(g, g.class_boundary_halo(), len, acc, acc_act);
-      else g.halo_end(len);
-    } else {
-      const float* halo = g.halo_end(len);
-      GAIB_OR_DIE(gaib_spmm_2t(C(), g.class_boundary_full(), kind, NULL, len, in, halo, (int64_t)g.size(), out, act));
-    }
-    return;
-  }
-  g.halo_begin(len, in);
-  const bool have_halo_edges = gaib_graph_ne(g.halo_graph()) > 0;
-  GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, out, have_halo_edges ? 0 : act));
-  if (!have_halo_edges) {
-    g.halo_end(len);
-    return;
-  }
-  halo_half(g, g.halo_graph(), len, acc, acc_act);
+  GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, out, act));
 }
 
 void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float* in, float* agg, bool keep_agg,
@@ -322,59 +318,33 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
                                        const float* rows2, const float* W2, bool relu_masked) {
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
-  if (bf16_for(g, len) && g.has_halo()) {
-    // bf16 tables on a partition: the fp32 branch further down with the same call structure and flags, the owned table cast once
-    // into the scratch, the exchange begun from it (see aggregate_rows_bf16_part) and every kernel gathering bf16
-    const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
-    const int mode = g.partition_mode(len);
-    if (mode != Graph::PART_SPLIT && !gaib_spmm_gemm_fusable(C(), kind, len, len_out, rows2 ? 1 : 0)) {
+  const bool bf16 = bf16_for(g, len);
+  const int act = relu ? GAIB_RELU : 0;
+  const int flags = act | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
+  const Product prod{agg, W, transW ? 1 : 0, rows2, W2, len_out, out};
+  if (g.has_halo()) {
+    // the classes fill disjoint rows of ONE output: all of them take the fused kernel, or -- a shape it does not cover --
+    // the aggregation runs class by class and the product(s) once over all rows
+    if (g.partition_mode(len) != Graph::PART_SPLIT && !gaib_spmm_gemm_fusable(C(), kind, len, len_out, rows2 ? 1 : 0)) {
       aggregate_rows(g, kind, len, in, agg, false, false);
-      const int act = relu ? GAIB_RELU : 0;
       GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, agg, W, rows2 ? 0 : act, out));
       if (rows2)
         GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, rows2, W2, GAIB_ACCUMULATE | act, out));
       return;
     }
-    gaib_graph* own = dev(g);
-    const uint16_t* tab = to_bf16((size_t)gaib_graph_nc(own), len, in);
-    auto fused16 = [&](gaib_graph* dg, const uint16_t* src, int fl) {
-      GAIB_OR_DIE(gaib_spmm_gemm_part_bf16(C(), dg, kind, NULL, len, src, NULL, 0, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
+    // every pass that completes rows carries the dense product(s); the partial sums continue in agg.  No boundary row: no launch.
+    auto run = [&](auto tab) {
+      partitioned(g, kind, len, tab, agg, false, [&](gaib_graph* dg, decltype(tab) t, decltype(tab) t2, int64_t n_first, int extra) {
+        fused_t(dg, kind, len, t, t2, n_first, prod, flags | extra);
+      });
     };
-    auto plain16 = [&](gaib_graph* gh, const uint16_t* t, int fl) {
-      GAIB_OR_DIE(gaib_spmm_part_bf16(C(), gh, kind, NULL, len, t, NULL, 0, agg, fl));
-    };
-    auto plain_acc16 = [&](gaib_graph* gh, const uint16_t* halo) { plain16(gh, halo, GAIB_ACCUMULATE); };
-    auto fused_acc16 = [&](gaib_graph* gh, const uint16_t* halo) { fused16(gh, halo, flags | GAIB_ACCUMULATE); };
-    g.halo_begin_bf16(len, tab);  // every rank joins every exchange, also one without halo edges
-    if (mode != Graph::PART_SPLIT) {
-      fused16(g.class_interior(), tab, flags | GAIB_OVERLAPS_TRANSFER);
-      if (mode == Graph::PART_CLASSES) {
-        if (gaib_graph_ne(g.class_boundary_halo()) == 0) {  // no boundary row
-          g.halo_end_bf16(len);
-          return;
-        }
-        plain16(g.class_boundary_own(), tab, 0);
-        halo_half_t<uint16_t>(g, g.class_boundary_halo(), len, plain_acc16, fused_acc16);
-      } else {
-        const uint16_t* halo = g.halo_end_bf16(len);
-        GAIB_OR_DIE(gaib_spmm_gemm_part_bf16(C(), g.class_boundary_full(), kind, NULL, len, tab, halo, (int64_t)g.size(), agg, W,
-                                             transW ? 1 : 0, rows2, W2, len_out, out, flags));
-      }
-      return;
-    }
-    if (gaib_graph_ne(g.halo_graph()) == 0) {
-      fused16(own, tab, flags | GAIB_OVERLAPS_TRANSFER);
-      g.halo_end_bf16(len);
-      return;
-    }
-    plain16(own, tab, 0);
-    halo_half_t<uint16_t>(g, g.halo_graph(), len, plain_acc16, fused_acc16);
+    if (bf16) run(owned_bf16(g, len, in));
+    else run(in);
     return;
   }
-  if (bf16_for(g, len)) {
+  if (bf16) {
     // bf16 table: the fused kernel gathers from it -- the route (and the bits) of the fp32 branch below on the rounded table
     gaib_graph* dg = dev(g);
-    const int fl = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
     int64_t ld = len;
     const uint16_t* tab = to_bf16(dg, len, in, &ld);
     // option gemm_bf16: the self rows ARE the table just cast and every dense route runs the self term as a separate
@@ -383,69 +353,14 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     // "the fp32 layer on the rounded table"
     if (rows2 == in && gemm_bf16_products() && gaib_spmm_gemm_fusable(C(), kind, len, len_out, 1) == 0 &&
         gaib_gemm_bf16_cover(C(), transW ? 1 : 0, len_out, len, ld) == 1) {
-      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, fl & ~GAIB_RELU));
-      GAIB_OR_DIE(gaib_gemm_bf16(C(), transW ? 1 : 0, (int64_t)g.size(), len_out, len, ld, tab, W2,
-                                 GAIB_ACCUMULATE | (relu ? GAIB_RELU : 0), out));
+      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, flags & ~GAIB_RELU));
+      GAIB_OR_DIE(gaib_gemm_bf16(C(), transW ? 1 : 0, (int64_t)g.size(), len_out, len, ld, tab, W2, GAIB_ACCUMULATE | act, out));
       return;
     }
     if (rows2)
-      GAIB_OR_DIE(gaib_spmm_gemm2_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
+      GAIB_OR_DIE(gaib_spmm_gemm2_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, flags));
     else
-      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, fl));
-    return;
-  }
-  const int flags = (relu ? GAIB_RELU : 0) | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
-  auto fused = [&](gaib_graph* dg, const float* src, int fl) {
-    if (rows2)
-      GAIB_OR_DIE(gaib_spmm_gemm2(C(), dg, kind, NULL, len, src, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, fl));
-    else
-      GAIB_OR_DIE(gaib_spmm_gemm(C(), dg, kind, NULL, len, src, agg, W, transW ? 1 : 0, len_out, out, fl));
-  };
-  // a piece of the halo-column half that is not the last: the partial sums continue in agg, no product yet
-  auto plain_acc = [&](gaib_graph* gh, const float* halo) {
-    GAIB_OR_DIE(gaib_spmm_ex(C(), gh, kind, NULL, len, halo, agg, GAIB_ACCUMULATE));
-  };
-  const int mode = g.has_halo() ? g.partition_mode(len) : Graph::PART_SPLIT;
-  if (mode != Graph::PART_SPLIT) {
-    // the classes fill disjoint rows of ONE output: all of them take the fused kernel, or -- a shape it does not cover --
-    // the aggregation runs class by class and the product(s) once over all rows
-    if (!gaib_spmm_gemm_fusable(C(), kind, len, len_out, rows2 ? 1 : 0)) {
-      aggregate_rows(g, kind, len, in, agg, false, false);
-      const int act = relu ? GAIB_RELU : 0;
-      GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, agg, W, rows2 ? 0 : act, out));
-      if (rows2)
-        GAIB_OR_DIE(gaib_sgemm_ex(C(), 0, transW ? 1 : 0, (int64_t)g.size(), len_out, len, rows2, W2, GAIB_ACCUMULATE | act, out));
-      return;
-    }
-    g.halo_begin(len, in);
-    fused(g.class_interior(), in, flags | GAIB_OVERLAPS_TRANSFER);  // (the exchange is in flight: RCCL's kernels need CUs)
-    if (mode == Graph::PART_CLASSES) {
-      if (gaib_graph_ne(g.class_boundary_halo()) == 0) {  // no boundary row
-        g.halo_end(len);
-        return;
-      }
-      GAIB_OR_DIE(gaib_spmm_ex(C(), g.class_boundary_own(), kind, NULL, len, in, agg, 0));
-      halo_half(g, g.class_boundary_halo(), len, plain_acc,
-                [&](gaib_graph* gh, const float* halo) { fused(gh, halo, flags | GAIB_ACCUMULATE); });
-    } else {
-      const float* halo = g.halo_end(len);
-      GAIB_OR_DIE(gaib_spmm_gemm_2t(C(), g.class_boundary_full(), kind, NULL, len, in, halo, (int64_t)g.size(), agg, W,
-                                    transW ? 1 : 0, rows2, W2, len_out, out, flags));
-    }
-    return;
-  }
-  if (g.has_halo()) {
-    // owned-column edges while the halo rows travel; the halo-column edges then continue the sums and
-    // carry the dense product(s)
-    g.halo_begin(len, in);  // every rank joins every exchange, also one without halo edges
-    if (gaib_graph_ne(g.halo_graph()) == 0) {
-      fused(dev(g), in, flags | GAIB_OVERLAPS_TRANSFER);
-      g.halo_end(len);
-      return;
-    }
-    GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, agg, 0));
-    halo_half(g, g.halo_graph(), len, plain_acc,
-              [&](gaib_graph* gh, const float* halo) { fused(gh, halo, flags | GAIB_ACCUMULATE); });
+      GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, flags));
     return;
   }
   // (256 columns, option agg_zs_wide: the K-slab route, whose launches are one-product ones -- ZS_TWO_PRODUCTS concerns the
@@ -455,8 +370,7 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
     gaib_graph* dg = dev(g);
     const size_t rows = (size_t)gaib_graph_nc(dg);
     const size_t tab_bytes = rows * (size_t)(len / 128) * 384;
-    int64_t capturing = 0;
-    GAIB_OR_DIE(gaib_get_option(C(), "capturing", &capturing));
+    const bool capturing = gaib_host::capturing();
     if (zs_other_context()) zs_table(0);
     // is there a packed route for this call?  Asked from the route information alone, before anything is packed or allocated (a
     // graph of short rows, a numbering with locality, a dense graph the ordered chunks take, a table of 4 GB: the dense call's
@@ -486,7 +400,7 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
       }
     }
   }
-  fused(dev(g), in, flags);
+  fused_t(dev(g), kind, len, in, (const float*)NULL, 0, prod, flags);
 }
 
 // ---- GCN ---------------------------------------------------------------------------------------
@@ -580,13 +494,9 @@ void GAT_Aggregator::init(int l, int nv, int ne, float lr, float drop_rate) {
 // d_norm_scores (the softmax of this forward) -> p . mask . scale in a buffer of its own: backward needs both the
 // undropped attention (softmax backward) and the dropped one (d_dropout of dp, transposed aggregation)
 const float* GAT_Aggregator::apply_attn_dropout(size_t n_scores, uint64_t seed, uint64_t* d_seed) {
-  if (n_scores > drop_cap) {
-    if (d_norm_scores_drop) float_free_device(d_norm_scores_drop);
-    if (d_attn_masks) GAIB_OR_DIE(gaib_free(C(), d_attn_masks));
-    float_malloc_device64(n_scores, d_norm_scores_drop);
-    d_attn_masks = gaib_host::dmalloc<mask_t>(n_scores);
-    drop_cap = n_scores;
-  }
+  size_t masks_cap = drop_cap;  // (the pair shares one capacity)
+  grow(d_attn_masks, masks_cap, n_scores);
+  grow(d_norm_scores_drop, drop_cap, n_scores);
   OpTimer t(OP_DROPOUT);
   if (d_seed)
     GAIB_OR_DIE(gaib_dropout_dev(C(), (int64_t)n_scores, attn_scale, attn_drop, d_seed, d_norm_scores, d_attn_masks,
@@ -669,9 +579,7 @@ void GAT_Aggregator::set_num_heads(int h) {
 }
 
 bool GAT_Aggregator::wide_rows_expected() const {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "gat_fused_wide", &v));
-  return v == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
+  return gaib_host::option("gat_fused_wide") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
 }
 
 // the [ne][heads] arrays of the staged kernels, for a graph of ne edges: grown where a graph is larger than the one the layer
@@ -701,21 +609,12 @@ void GAT_Aggregator::grow_edge_arrays(size_t ne) {
 void GAT_Aggregator::ensure_partition_buffers(Graph& g, int len) {
   const size_t nc = g.size() + g.gat_n_halo();
   grow_edge_arrays(g.sizeEdges());  // (a no-op unless set_num_heads() left them to the first use)
-  if (nc * len > ptab_floats) {
-    if (d_ptab) float_free_device(d_ptab);
-    if (d_pout) float_free_device(d_pout);
-    float_malloc_device64(nc * len, d_ptab);
-    float_malloc_device64(nc * len, d_pout);
-    ptab_floats = nc * len;
-  }
-  if (nc * heads > pvec_floats) {
-    if (d_prs) float_free_device(d_prs);
-    if (d_pcs) float_free_device(d_pcs);
-    float_malloc_device64(nc * heads, d_prs);
-    float_malloc_device64(nc * heads, d_pcs);
+  size_t pout_cap = ptab_floats, pcs_cap = pvec_floats;  // (each pair shares one capacity)
+  grow(d_pout, pout_cap, nc * len);
+  grow(d_ptab, ptab_floats, nc * len);
+  grow(d_pcs, pcs_cap, nc * heads);
+  if (grow(d_prs, pvec_floats, nc * heads))
     GAIB_OR_DIE(gaib_fill_f32(C(), (int64_t)(nc * heads), 0.f, d_prs));  // rows of halo vertices stay 0
-    pvec_floats = nc * heads;
-  }
   if (!d_temp_scores) d_temp_scores = gaib_host::dmalloc<float>(num_edges * heads);  // the row-side backward reads it
 }
 
@@ -734,12 +633,7 @@ void GAT_Aggregator::aggregate_partition(int len, Graph& g, const float* in, flo
     g.halo_begin(len, in);
     GAIB_OR_DIE(gaib_memcpy_d2d(C(), d_ptab, in, sizeof(float) * n_own * len));
     if (!dropping() && g.gat_symmetric()) {  // (an asymmetric graph: the staged path, which walks the transposed structure)
-      const size_t need = n_own * heads * 2;
-      if (need > stats_floats) {
-        if (d_row_stats) float_free_device(d_row_stats);
-        float_malloc_device64(need, d_row_stats);
-        stats_floats = need;
-      }
+      grow(d_row_stats, stats_floats, n_own * heads * 2);
       const int rc = gaib_gat_forward_fused_rect(C(), g.gat_full_graph(), len, heads, d_ptab, d_alpha_l, d_alpha_r, epsilon,
                                                  fuse_relu ? 1 : 0, out, d_row_stats, 0);
       if (rc == GAIB_OK) fused = true;
@@ -779,16 +673,8 @@ void GAT_Aggregator::d_aggregate_partition(int len, Graph& g, const float* grad_
     // forward-direction exchanges, no transposed structure, no reverse exchange.  The chunks over owned columns run while
     // the grad rows are on the wire.
     OpTimer t(OP_ATTN);
-    if (nc * len > pgrad_floats) {
-      if (d_pgrad) float_free_device(d_pgrad);
-      float_malloc_device64(nc * len, d_pgrad);
-      pgrad_floats = nc * len;
-    }
-    if (nc * heads * 4 > prec_floats) {
-      if (d_prec) float_free_device(d_prec);
-      float_malloc_device64(nc * heads * 4, d_prec);
-      prec_floats = nc * heads * 4;
-    }
+    grow(d_pgrad, pgrad_floats, nc * len);
+    grow(d_prec, prec_floats, nc * heads * 4);
     GAIB_OR_DIE(gaib_gat_backward_rec(C(), (int64_t)n_own, len, heads, grad_in, fwd, d_row_stats, d_prec));
     GAIB_OR_DIE(gaib_memcpy_d2d(C(), d_pgrad, grad_in, sizeof(float) * n_own * len));
     g.halo_begin(len, grad_in);
@@ -838,16 +724,8 @@ void GAT_Aggregator::d_aggregate_partition(int len, Graph& g, const float* grad_
   GAIB_OR_DIE(gaib_halo_reduce(g.halo_plan(), len, d_pout + n_own * len, grad_out));
 }
 
-bool GAT_Aggregator::gat_fused_drop_option() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "gat_fused_drop", &v));
-  return v != 0;
-}
-bool GAT_Aggregator::gat_bf16_tables() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "gat_bf16", &v));
-  return v != 0;
-}
+bool GAT_Aggregator::gat_fused_drop_option() { return gaib_host::option("gat_fused_drop") != 0; }
+bool GAT_Aggregator::gat_bf16_tables() { return gaib_host::option("gat_bf16") != 0; }
 // bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32
 static void no_gat_bf16_partition() {
   fprintf(stderr, "GPU error: gat_bf16 (GAIB_GAT_DTYPE=bf16) on a partitioned GAT graph: the one-sweep kernels over bf16 tables "
@@ -857,12 +735,7 @@ static void no_gat_bf16_partition() {
 
 // h as bf16 bits in the aggregator's own buffer (kept for backward), grown on demand
 const uint16_t* GAT_Aggregator::cast_hb16(size_t elems, const float* in) {
-  if (elems > hb16_elems) {
-    if (d_hb16) GAIB_OR_DIE(gaib_free(C(), d_hb16));
-    d_hb16 = NULL;
-    GAIB_OR_DIE(gaib_malloc(C(), elems * sizeof(uint16_t), (void**)&d_hb16));
-    hb16_elems = elems;
-  }
+  grow(d_hb16, hb16_elems, elems);
   GAIB_OR_DIE(gaib_cast_f32_bf16(C(), (int64_t)elems, in, d_hb16));
   return d_hb16;
 }
@@ -884,14 +757,7 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   dropped_last = false;
   drop_fused_last = false;
   const bool drop_sweep = dropping() && gat_fused_drop_option();
-  if (!dropping() || drop_sweep) {
-    const size_t need = (size_t)g.size() * heads * 2;
-    if (need > stats_floats) {
-      if (d_row_stats) float_free_device(d_row_stats);
-      float_malloc_device64(need, d_row_stats);
-      stats_floats = need;
-    }
-  }
+  if (!dropping() || drop_sweep) grow(d_row_stats, stats_floats, (size_t)g.size() * heads * 2);
   if (drop_sweep) {
     // attention dropout inside the sweep (option gat_fused_drop): the masks of the staged path's next seed, no edge array
     OpTimer t(OP_SPARSEMM);
@@ -975,11 +841,7 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
     if (fwd_out && stats_valid && feat_in == last_in && &g == last_graph && len == last_len) {
       OpTimer t(OP_ATTN);
       const size_t need = (size_t)g.size() * len;
-      if (need > tbuf_floats) {
-        if (d_tbuf) float_free_device(d_tbuf);
-        float_malloc_device64(need, d_tbuf);
-        tbuf_floats = need;
-      }
+      grow(d_tbuf, tbuf_floats, need);
       // bf16 tables: the kept copy of h is reused, one cast (of grad_in) is made (the guard above is the bf16 call's own)
       if (fwd_bf16)
         rc = gaib_gat_backward_fused_drop_bf16(C(), dev(g), len, heads, d_hb16, to_bf16(g.size(), len, grad_in), fwd_out, d_alpha_l,
@@ -1006,11 +868,7 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
     // output that does not alias feat_in (GAT_layer::backward passes out_temp for both) -> a scratch of its own
     OpTimer t(OP_ATTN);
     const size_t need = (size_t)g.size() * len;
-    if (need > tbuf_floats) {
-      if (d_tbuf) float_free_device(d_tbuf);
-      float_malloc_device64(need, d_tbuf);
-      tbuf_floats = need;
-    }
+    grow(d_tbuf, tbuf_floats, need);
     int rc = GAIB_ERR_UNSUPPORTED;
     // bf16 tables: the kept copy of h is reused, one cast (of grad_in) is made
     if (fwd_bf16 && stats_valid && feat_in == last_in && &g == last_graph && len == last_len)

@@ -20,8 +20,14 @@ inline T* dmalloc(size_t n) {
   GAIB_OR_DIE(gaib_malloc(gpu_context::get(), (n > 0 ? n : 1) * sizeof(T), &p));
   return static_cast<T*>(p);
 }
+// the value of option `name` on the process context (gaib_get_option)
+inline int64_t option(const char* name) {
+  int64_t v = 0;
+  GAIB_OR_DIE(gaib_get_option(gpu_context::get(), name, &v));
+  return v;
+}
 // option drop_seed_dev (math_functions.cpp): dropout mask seeds in device memory, read and advanced by gaib_dropout_dev
-bool drop_seed_dev_option();
-bool capturing();                        // a recording is open on the process context (gaib_capture_begin)
+inline bool drop_seed_dev_option() { return option("drop_seed_dev") != 0; }
+inline bool capturing() { return option("capturing") != 0; }  // a recording is open on the process context (gaib_capture_begin)
 uint64_t* new_seed_slot(uint64_t seed);  // one 8-byte device slot holding `seed`; allocates and waits: not inside a capture
 }  // namespace gaib_host

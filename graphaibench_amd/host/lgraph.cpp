@@ -34,9 +34,7 @@ void LearningGraph::halo_begin(int len, const float* d_in) {
 }
 int LearningGraph::halo_elem_bytes(int len) const {
   if (!has_halo() || !halo_carries_bf16() || len % 2 != 0) return 4;
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "agg_bf16", &v));
-  return v != 0 ? 2 : 4;
+  return gaib_host::option("agg_bf16") != 0 ? 2 : 4;
 }
 void LearningGraph::halo_begin_bf16(int len, const uint16_t* d_in) {
   if (halo_plan_) GAIB_OR_DIE(gaib_halo_exchange_begin_bf16(halo_plan_, len, d_in));

@@ -65,16 +65,6 @@ uint64_t* gaib_host::new_seed_slot(uint64_t seed) {
   GAIB_OR_DIE(gaib_memcpy_h2d(C(), d, &seed, sizeof(seed)));
   return d;
 }
-bool gaib_host::capturing() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "capturing", &v));
-  return v != 0;
-}
-bool gaib_host::drop_seed_dev_option() {
-  int64_t v = 0;
-  GAIB_OR_DIE(gaib_get_option(C(), "drop_seed_dev", &v));
-  return v != 0;
-}
 static uint64_t* dropout_seed_slot() {
   DropSeedSlot& s = g_drop_slot;
   if (s.ctx != C() || s.gen != gpu_context::generation()) {

@@ -39,6 +39,7 @@
 #include "cutils.h"
 #include "dense_layer.h"
 #include "graph_conv_layer.h"
+#include "host_util.h"
 #include "l2norm_layer.h"
 #include "math_functions.hh"
 #include "reader.h"
@@ -205,8 +206,7 @@ struct Trainer {
     init_comm();
     if (ARCH == gnn_arch::GAT) {
       // GAT's own tables: fp32, or bf16 with GAIB_GAT_DTYPE=bf16 (context option gat_bf16; whole graphs only)
-      int64_t gat16 = 0;
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_bf16", &gat16));
+      const int64_t gat16 = gaib_host::option("gat_bf16");
       if (gat16 && world > 1) {  // (every rank reads the same environment: refused before any collective)
         std::cerr << "GAIB_GAT_DTYPE=bf16 (gat_bf16) runs on one GPU only: the one-sweep GAT kernels over bf16 tables take whole graphs\n";
         exit(EXIT_FAILURE);
@@ -404,9 +404,7 @@ struct Trainer {
         std::cout << "disabling validation for subgraph sampling on GPU\n";
         val_interval = num_epochs;
       }
-      int64_t on_device = 0;
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "sampler_device", &on_device));
-      sampler_device = on_device != 0;
+      sampler_device = gaib_host::option("sampler_device") != 0;
       if (!sampler_device) {  // (the device path gathers from d_features / d_labels)
         feats_host = feats;
         labels_host = labels;
@@ -516,9 +514,7 @@ struct Trainer {
       // option gat_fused_wide (GAIB_GAT_WIDE=1): how the hidden layers' rows of dim_hid columns run -- the one-sweep kernels per
       // column slab where the shape rule gives slabs (whole graphs; under attention dropout only with option gat_fused_drop as
       // well, GAIB_GAT_FUSED_DROP=1: partitions, and dropout without that option, stay staged at these widths), else staged
-      int64_t wide = 0, drop_sweep = 0;
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_wide", &wide));
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_drop", &drop_sweep));
+      const int64_t wide = gaib_host::option("gat_fused_wide"), drop_sweep = gaib_host::option("gat_fused_drop");
       if (wide == 1 && root()) {
         const char* hs = getenv("GAIB_GAT_HEADS");
         int w = 0;
@@ -653,11 +649,7 @@ struct Trainer {
     const char* st = getenv("GAIB_SYNC_TIMERS");
     const char* ov = getenv("GAIB_OVERLAP");
     const bool dropout = feat_drop != 0.f || score_drop != 0.f;
-    int64_t seeds_dev = 0, drop_sweep = 0;
-    if (dropout) {
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "drop_seed_dev", &seeds_dev));
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "gat_fused_drop", &drop_sweep));
-    }
+    const int64_t seeds_dev = dropout ? gaib_host::option("drop_seed_dev") : 0, drop_sweep = dropout ? gaib_host::option("gat_fused_drop") : 0;
     const bool sweep_by_value = ARCH == gnn_arch::GAT && score_drop != 0.f && drop_sweep == 1;
     const bool other = world == 1 && subg_size == 0 && !inductive && !(st && atoi(st)) && !(ov && atoi(ov)) && num_epochs > 1;
     const bool allowed = other && (!dropout || (seeds_dev == 1 && !sweep_by_value));
@@ -711,11 +703,7 @@ struct Trainer {
   void train() {
     optimizer* opt = new adam(lrate);  // one instance for every layer's update_weight call (Q6)
     graph_mode = decide_graph_mode();
-    {
-      int64_t seeds_dev = 0;
-      GAIB_OR_DIE(gaib_get_option(gpu_context::get(), "drop_seed_dev", &seeds_dev));
-      if (seeds_dev == 1 && root()) std::cerr << "[gaib] dropout mask seeds: device\n";
-    }
+    if (gaib_host::option("drop_seed_dev") == 1 && root()) std::cerr << "[gaib] dropout mask seeds: device\n";
     if (graph_mode) {
       // the null stream cannot be recorded, and the beta powers of every Adam instance have to live on the device
       GAIB_OR_DIE(gaib_ctx_own_stream(gpu_context::get()));

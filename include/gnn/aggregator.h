@@ -15,7 +15,8 @@ class aggregator {
   // allocated on first use, which has to lie outside a capture (gaib_capture_*: the trainer records epoch 1 after running
   // epoch 0 eagerly).  GAT ignores the option (it has "gat_bf16", see GAT_Aggregator).  On a partitioned graph (halo) whose exchange can carry bf16 rows -- a halo plan,
   // or set_halo_bf16's callbacks -- the aggregations of even width run on bf16 tables too: the owned rows are cast once, the
-  // exchange is begun from the scratch and the class kernels gather bf16 (gaib_spmm_part_bf16, gaib_spmm_gemm_part_bf16); odd
+  // exchange is begun from the scratch and the class kernels gather bf16 (gaib_spmm_part_bf16, gaib_spmm_gemm_part_bf16) -- the
+  // one partition sequence of host/aggregators.cpp (partitioned<T>), which fp32 tables run through as well; odd
   // widths run in fp32 there; a halo with fp32 callbacks only refuses the option.
   static bool bf16_tables();
   // extension: dense self products on that bf16 table (context option "gemm_bf16" = 1, or GAIB_GEMM_DTYPE=bf16; only under
