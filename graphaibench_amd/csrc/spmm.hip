@@ -246,6 +246,20 @@ extern "C" int gaib_bf16_row_stride(gaib_ctx* ctx, gaib_graph* g, int len, int64
   return GAIB_OK;
 }
 
+// size of a table of `rows` rows of `ld` elements as the buffer-descriptor path sees it: 0 where it reaches 4 GB (64-bit addresses then)
+static uint32_t buf_bytes(int64_t rows, int64_t ld, bool bf16) {
+  const int64_t b = rows * ld * (bf16 ? 2 : 4);
+  return b < ((int64_t)1 << 32) ? (uint32_t)b : 0u;
+}
+
+// row stride (elements) the gather reads the table at: a bf16 table's own (ld_bf16 > 0: the caller cast it that way), an fp32
+// table's re-strided copy where pad_stride_floats makes one
+static int64_t gather_ld(const gaib_ctx* ctx, const gaib_graph* g, int len, bool part, bool bf16, int64_t ld_bf16) {
+  if (bf16) return ld_bf16 > 0 ? ld_bf16 : len;
+  const int64_t lp = pad_stride_floats(ctx, g, len, part);
+  return lp > 0 ? lp : len;
+}
+
 // fills the launch arguments shared by every aggregation path; *wmode = kernel weight mode
 // d_in2 / n_first: column ids >= n_first index the second table d_in2 (row id - n_first) -- NULL: one table
 // bf16: d_in (and d_in2) hold bf16 bits (gaib_spmm_bf16, gaib_spmm_part_bf16): gathered as they are (no re-strided copy, no
@@ -312,12 +326,8 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   }
   if (bf16 && ld_bf16 > 0) a.ld = ld_bf16;
   // feature table = nc rows of a.ld elements (4 B, or 2 B in bf16); the 32-bit buffer path needs it below 4 GB
-  const int64_t table_bytes = (d_in2 ? n_first : g->nc) * a.ld * (bf16 ? 2 : 4);
-  a.in_bytes = table_bytes < ((int64_t)1 << 32) ? (uint32_t)table_bytes : 0u;
-  if (d_in2) {
-    const int64_t t2 = (g->nc - n_first) * a.ld * (bf16 ? 2 : 4);
-    a.in2_bytes = t2 < ((int64_t)1 << 32) ? (uint32_t)t2 : 0u;
-  }
+  a.in_bytes = buf_bytes(d_in2 ? n_first : g->nc, a.ld, bf16);
+  if (d_in2) a.in2_bytes = buf_bytes(g->nc - n_first, a.ld, bf16);
   switch (weight_kind) {
     case GAIB_W_GCN:
       GAIB_TRY(gaib_graph_ensure_w_gcn(ctx, g));
@@ -362,49 +372,6 @@ static bool chunk_rule(gaib_ctx* ctx, gaib_graph* g, int64_t ld) {
   return g->nc * ld * 4 <= ((int64_t)512 << 20) && 4 * g->heavy_edges >= g->ne && g->ne > 0;
 }
 
-// Option spmm_hot_cold for the fused, heavy and packed launches of gaib_spmm_gemm / gaib_spmm_gemm_zs: the graph's flagged
-// column ids when the option resolves to on for this call, else NULL (the launch then reads the plain ids, default policy).
-//   1  on wherever the hot/cold form exists: a square graph without column normalisers (a column's degree is its row's), whole
-//      (no row classes), an fp32 or zero-suppressed table of 65 .. 128 columns; launch_fused keeps the form's own conditions
-//  -1  auto: GAIB_HOT_COLD_AUTO (common.h: what the measurement decided), a DENSE table (the packed gather measured slower
-//      with the option at every hot-set size), larger than twice the 256 MiB Infinity Cache -- a table that fits is resident
-//      whatever the policy -- and a numbering that is not local (near_frac < 0.25)
-//   0  off
-// The flags are per-graph preprocessing, built next to the heavy-row list on the first call outside a capture; inside a
-// capture nothing is built: without current flags the call runs with the default policy.
-static const uint32_t* hot_cold_cols(gaib_ctx* ctx, gaib_graph* g, int len_in, int len_out, int64_t table_bytes, bool packed) {
-  if (ctx->spmm_hot_cold == 0 || ctx->spmm_gather_mode == 3) return nullptr;  // (gather mode 3 sizes the one flagged array for the L2)
-  if (g->row_map || g->nc != g->nv || g->col_vdata || len_in <= 64 || len_in > 128 || g->ne == 0) return nullptr;
-  // launch_fused's own predicates for the forms without a hot/cold gather (2-row strip, edge stream): nothing is built for them
-  if (fuse_strip_rows(128, len_out, false) != 8 || ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv)) return nullptr;
-  if (ctx->spmm_hot_cold < 0) {
-    if (!GAIB_HOT_COLD_AUTO || packed || table_bytes <= ((int64_t)512 << 20)) return nullptr;
-    if (g->near_frac < 0.f && (ctx->capturing || gaib_graph_ensure_locality(ctx, g) != GAIB_OK)) return nullptr;
-    if (g->near_frac >= 0.25f) return nullptr;
-  }
-  const int64_t want = gaib_hot_rows_wanted(ctx, g);
-  if (!ctx->capturing && gaib_graph_ensure_hot_flags(ctx, g, want) != GAIB_OK) return nullptr;
-  return (g->colidx_flagged && g->hot_rows == want) ? g->colidx_flagged : nullptr;
-}
-
-// the row-class kernels (PART = true) live in a translation unit of their own: spmm_part.hip
-int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len);
-int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                         int vec, int wmode);
-// ... and over bf16 tables: spmm_part_bf16.hip
-int gaib_spmm_part_plain_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len);
-int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                              int vec, int wmode);
-// ... and so do the fused kernels over a bf16 table: spmm_gemm_bf16.hip
-int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                         int vec, int wmode);
-// ... and over a zero-suppressed table: spmm_gemm_zs.hip
-int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                       int wmode);
-// ... one K-slab of a 256-column aggregation over its slab of a wide zero-suppressed table
-int gaib_spmm_kslab_zs(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                       int wmode);
-
 static int spmm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                      const float* d_in, float* d_out, int flags, int heads = 1, const float* d_in2 = nullptr,
                      int64_t n_first = 0) {
@@ -422,7 +389,7 @@ static int spmm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float*
     GAIB_CHECK(d_in2 != d_out, "gaib_spmm: in2 and out must not alias");
     GAIB_CHECK(heads == 1 && wmode <= 1, "gaib_spmm: a row class of a partition aggregates with GAIB_W_GCN / _MEAN / _MEAN_T / "
                                           "single-head _EDGE weights (got kind %d, %d heads)", weight_kind, heads);
-    return gaib_spmm_part_plain(ctx, g, &a, wmode, len);
+    return gaib_spmm_part_plain(ctx, g, a, wmode, len);
   }
   // dense graphs over a table that fits the Infinity Cache: ordered chunks (see spmm_chunk_kernel)
   const bool chunk_shape = len % 4 == 0 && len <= 256 && a.ld % 4 == 0 && a.ldo % 4 == 0 && g->ne > 0 &&
@@ -468,266 +435,369 @@ extern "C" int gaib_spmm_2t(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const
   return spmm_impl(ctx, g, weight_kind, d_edge_w, len, d_in, d_out, flags, 1, d_in2, n_first);
 }
 
-// agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]).  Fused on the matrix cores when the shape allows,
-// otherwise gaib_spmm followed by gaib_sgemm (same results up to summation order).
-// shape-only part of the "can the product ride on the aggregation" decision (what the row classes of a partition must
-// agree on: they share one output matrix, so either every class runs the fused kernel or none does)
-static bool fuse_shape_ok(gaib_ctx* ctx, int weight_kind, int len_in, int len_out, bool dual) {
-  if (!ctx->spmm_fuse || len_in < 1 || len_in > 128 || len_out < 1) return false;
-  if (len_in > 64 && len_in % 2 != 0) return false;
-  if (!(weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN || weight_kind == GAIB_W_MEAN_T || weight_kind == GAIB_W_EDGE))
-    return false;
-  return fuse_strip_rows(len_in <= 64 ? 64 : 128, len_out, dual) != 0;
+// ---- the fused aggregation: agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]) ----------------------------------------------
+// Fused on the matrix cores when the shape allows, otherwise gaib_spmm followed by gaib_sgemm (same results up to summation
+// order).  Every gaib_spmm_gemm* entry fills ONE description of its call (GemmCall), ONE function decides the route and the form
+// of the fused launch (gemm_route), and each route has ONE executor (spmm_gemm_run).
+struct GemmCall {
+  int weight_kind;
+  const float* d_edge_w;
+  int len_in;
+  const float* d_in;  // the table: fp32, or bf16 bits (bf16)
+  float* d_agg;
+  const float* d_W;
+  int transW;
+  const float *d_rows2, *d_W2;  // the second product: both or neither
+  int len_out;
+  float* d_out;
+  int flags;
+  // set by name by the entries that have them
+  const float* d_in2 = nullptr;  // second table, indexed by column ids >= n_first (row id - n_first): gaib_spmm_gemm_2t / _part_bf16
+  int64_t n_first = 0, ld = 0;   // ld: a bf16 table's rows are this many elements apart (0: len_in)
+  bool bf16 = false;             // d_in (and d_in2) hold bf16 bits
+  const void* d_zs = nullptr;  // the zero-suppressed image of d_in (gaib_pack_zs, or gaib_pack_zs_wide at 256 columns)
+};
+
+// the routes (the table stands at gemm_route): nothing to do | one fused launch | the neighbour product fused, then the accumulating
+// product | one fused launch per 128-column K-slab | aggregate, then multiply | GAIB_ERR_UNSUPPORTED with its message
+enum GemmRouteKind { ROUTE_NONE, ROUTE_FUSED, ROUTE_FUSED_THEN_GEMM, ROUTE_KSLABS, ROUTE_UNFUSED, ROUTE_REFUSED };
+struct GemmRoute {
+  GemmRouteKind kind;
+  FuseForm form;  // of the fused launch (ROUTE_KSLABS: of the first slab's)
+};
+
+// the weight kinds the fused kernels take
+static bool fuse_kind_ok(int k) { return k == GAIB_W_GCN || k == GAIB_W_MEAN || k == GAIB_W_MEAN_T || k == GAIB_W_EDGE; }
+
+// short rows (fewer than 12 edges per row on average: halo-column halves, citation graphs) take the edge-stream form
+// (scripts/ab_flat.py: -34 % at 3 edges per row, -20 % at 5, even at 12, +2 % at 30); option spmm_flat forces or forbids it
+static bool edge_stream_rule(const gaib_ctx* ctx, const gaib_graph* g) {
+  return ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv);
+}
+
+// The shape-only part of "can the product ride on the aggregation in one launch": the strip height of that launch, 0 where there
+// is none.  The weight matrices [len_out x (len_in+4)] and 16 row strips must fit the CU's 160 KB of LDS; 65..128 columns need
+// 8-byte lanes.  (What the row classes of a partition must agree on: they share one output matrix, so either every class runs
+// the fused kernel or none does -- host/aggregators.cpp asks gaib_spmm_gemm_fusable first.)
+static int fuse_shape_strip(const gaib_ctx* ctx, int weight_kind, int len_in, int len_out, bool dual) {
+  if (!ctx->spmm_fuse || len_in < 1 || len_in > 128 || len_out < 1) return 0;
+  if ((len_in > 64 && len_in % 2 != 0) || !fuse_kind_ok(weight_kind)) return 0;
+  return fuse_strip_rows(len_in <= 64 ? 64 : 128, len_out, dual);
 }
 
 extern "C" int gaib_spmm_gemm_fusable(gaib_ctx* ctx, int weight_kind, int len_in, int len_out, int dual) {
-  return ctx && fuse_shape_ok(ctx, weight_kind, len_in, len_out, dual != 0) ? 1 : 0;
+  return ctx && fuse_shape_strip(ctx, weight_kind, len_in, len_out, dual != 0) != 0 ? 1 : 0;
 }
 
-// bf16: d_in (and d_in2) hold bf16 bits (gaib_spmm_gemm_bf16: whole graphs, checked by the caller; gaib_spmm_gemm_part_bf16: row
-// classes of a partition too).  Every test below is made on what the
-// fp32 call would see for the same table widened -- the widened table sits at "twice the address" (a bf16 table aligned to 8 B
-// stands for an fp32 one aligned to 16), sizes and the chunk rule count fp32 bytes -- so both take the same route, and each route
-// runs with the bf16 gather: no fp32 copy of the table anywhere.
-// d_zs: the zero-suppressed image of d_in (gaib_pack_zs, or gaib_pack_zs_wide at 256 columns; gaib_spmm_gemm_zs).  Only the
-// one-launch fused route over a whole graph (128 columns) and the K-slab route (256 columns: one slab image per launch) have
-// such a gather (buffer addressing, row forms): every other route is GAIB_ERR_UNSUPPORTED, decided on the dense sizes before
-// anything is launched.
-static int spmm_gemm_impl(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
-                          const float* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
-                          const float* d_W2, int len_out, float* d_out, int flags, const float* d_in2 = nullptr,
-                          int64_t n_first = 0, bool bf16 = false, const void* d_zs = nullptr, bool zs_query = false,
-                          int64_t ld_bf16 = 0) {
+// option spmm_tile_xcd -> FuseForm::tile_xcd (0 = global counter, else log2(chunk length in tiles) + 1).
+// -1 (default): by the graph's numbering -- XCD-affine chunks of 1024 tiles when at least a quarter of the edges stay
+// within 32 768 ids of their row, else the global counter (scripts/ab_tile_xcd.py, products size, D = 128: a numbering with
+// planted locality 5.94 -> 5.01 ms at 512-1024 tiles per chunk, a random one 7.60 -> 7.80 ms with ANY chunk length: hence the
+// rule instead of one setting).  1 = the round-2 form (16-tile chunks); n = chunk length, rounded down to 2^k.
+static int tile_xcd_arg(gaib_ctx* ctx, gaib_graph* g) {
+  int v = ctx->spmm_tile_xcd;
+  if (v < 0) {
+    if (gaib_graph_ensure_locality(ctx, g) != GAIB_OK) return 0;
+    v = g->near_frac >= 0.25f ? 1024 : 0;
+  }
+  if (v <= 0) return 0;
+  if (v == 1) v = 16;
+  int sh = 0;
+  while ((2 << sh) <= v) ++sh;
+  return sh + 1;
+}
+
+// Option spmm_hot_cold for a launch whose form has the hot/cold gather (fuse_form: 8-B lanes, row form, 8-row strip, one product,
+// global tile counter, buffer addressing, whole graph, fp32 or zero-suppressed table): the graph's flagged column ids when the option
+// resolves to on for this table, else NULL (the launch then reads the plain ids, default policy).
+//   1  on wherever the form runs on a square graph without column normalisers (a column's degree is its row's)
+//  -1  auto: GAIB_HOT_COLD_AUTO (common.h: what the measurement decided), a DENSE table (the packed gather measured slower
+//      with the option at every hot-set size), larger than twice the 256 MiB Infinity Cache -- a table that fits is resident
+//      whatever the policy -- and a numbering that is not local (near_frac < 0.25)
+//   0  off
+// The flags are per-graph preprocessing, built next to the heavy-row list on the first call outside a capture; inside a
+// capture nothing is built: without current flags the call runs with the default policy.
+static const uint32_t* hot_cold_cols(gaib_ctx* ctx, gaib_graph* g, int64_t table_bytes, bool packed) {
+  if (ctx->spmm_hot_cold == 0 || ctx->spmm_gather_mode == 3) return nullptr;  // (gather mode 3 sizes the one flagged array for the L2)
+  if (g->row_map || g->nc != g->nv || g->col_vdata || g->ne == 0) return nullptr;
+  if (ctx->spmm_hot_cold < 0) {
+    if (!GAIB_HOT_COLD_AUTO || packed || table_bytes <= ((int64_t)512 << 20)) return nullptr;
+    if (g->near_frac < 0.f && (ctx->capturing || gaib_graph_ensure_locality(ctx, g) != GAIB_OK)) return nullptr;
+    if (g->near_frac >= 0.25f) return nullptr;
+  }
+  const int64_t want = gaib_hot_rows_wanted(ctx, g);
+  if (!ctx->capturing && gaib_graph_ensure_hot_flags(ctx, g, want) != GAIB_OK) return nullptr;
+  return (g->colidx_flagged && g->hot_rows == want) ? g->colidx_flagged : nullptr;
+}
+
+// The form of the fused launch of a call: `dual` products on the `strip`-row strip (see the table at gemm_route).  Measures the
+// numbering's locality where spmm_tile_xcd is on auto (once per graph, not inside a capture); builds nothing else.
+static FuseForm fuse_form(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, bool part, bool dual, int strip, bool kslabs) {
+  FuseForm fm;
+  fm.vec = c.len_in <= 64 ? 1 : 2;
+  fm.strip = strip;
+  fm.dual = dual;
+  fm.yacc = false;
+  // the table(s) as the gather addresses them -- a bf16 table counts its own bytes here, the one place its real size decides
+  const int64_t ld = gather_ld(ctx, g, c.len_in, part, c.bf16, c.ld);
+  fm.buf = ctx->spmm_addr_mode != 2 && buf_bytes(c.d_in2 ? c.n_first : g->nc, ld, c.bf16) != 0 &&
+           (!c.d_in2 || buf_bytes(g->nc - c.n_first, ld, c.bf16) != 0);
+  fm.short_rows = edge_stream_rule(ctx, g);
+  fm.flat = fm.short_rows && !dual && strip == 8;
+  fm.ring = fm.flat && ctx->spmm_flat_ring != 0;
+  const int tile_xcd = tile_xcd_arg(ctx, g);  // (asked whatever the table kind: the locality is measured on a graph's first fused call)
+  fm.tile_xcd = part || c.bf16 ? 0 : tile_xcd;
+  // (hot_cold: the launch has the form; run_fused asks hot_cold_cols whether the option is on and the flags exist)
+  fm.hot_cold = !kslabs && !part && !c.bf16 && fm.vec == 2 && fm.buf && !dual && strip == 8 && !fm.flat && fm.tile_xcd == 0;
+  return fm;
+}
+
+// The route of a call and the form of its fused launch.  Launches no aggregation and reads nothing through the table, image or
+// matrix pointers (gaib_spmm_gemm_zs_route returns what it says, BEFORE the caller packs); the per-graph preprocessing it may run
+// is the heavy-row list (the chunk rule reads it) and the locality of the numbering, neither inside a capture.
+//
+//   call and shape (fp32 view of the table), first match                                                  route
+//   nv == 0 or len_out == 0                                                                               NONE
+//   whole graph, spmm_chunked 1 or chunk rule; len_in % 4 == 0, in / agg 16-B aligned                     UNFUSED (ordered chunks)
+//   spmm_fuse 0, a weight kind the fused kernels lack, ne == 0 on a whole graph                           UNFUSED
+//   len_in <= 64, or <= 128 even with in / agg 8-B aligned; W (and W2, len_out <= 128) fit 160 KB of LDS   FUSED: 4-B / 8-B lanes; 8-row strip where it
+//                                                                                                           fits next to W, else 2; two products: 2
+//   the same, whole graph, two products of which W alone fits (100 -> 256)                                FUSED_THEN_GEMM: the one-product form
+//   129 <= len_in <= 256 even, 8-B aligned, whole graph, ne > 0, a 128-column slab of W fits              KSLABS: per slab the one-product form, later
+//                                                                                                           slabs y += ; a second product follows
+//   everything else (odd above 64, > 256, unaligned)                                                      UNFUSED
+//   ... and where a row class of a partition would go UNFUSED: REFUSED (the classes' rows share one output)
+// "fp32 view": a bf16 table stands for its widened fp32 table -- at twice the address, the chunk rule counting fp32 bytes -- so
+// both take the same route, and each route runs the bf16 gather.  The form next to the route (fuse_form):
+//   edge stream  short rows (edge_stream_rule) on the one-product 8-row strip, never on a later K-slab; a ring with spmm_flat_ring
+//   addressing   buffer descriptors while every table is below 4 GB and spmm_addr_mode != 2, else 64-bit
+//   tile supply  spmm_tile_xcd (XCD-affine chunks; auto: a numbering with locality); global counter on classes and bf16 tables
+//   hot/cold     spmm_hot_cold (hot_cold_cols) on 8-B lanes, 8-row strip, one product, row form, buffer addressing, global
+//                counter, an fp32 or zero-suppressed table of a whole graph
+// A zero-suppressed image (d_zs) has a packed gather only on FUSED at 128 columns (two products, or the 8-row strip) and on KSLABS
+// at 256 columns, with buffer addressing, no edge stream on short rows, the global tile counter: any other form is REFUSED.
+static int gemm_route(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, GemmRoute* r) {
+  *r = GemmRoute{};
+  r->kind = ROUTE_NONE;
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm: NULL ctx/graph");
-  GAIB_CHECK(len_in >= 0 && len_out >= 0, "gaib_spmm_gemm: negative length");
-  GAIB_CHECK(ctx->device == g->device, "gaib_spmm_gemm: graph lives on device %d, ctx on %d", g->device,
-             ctx->device);
-  GAIB_CHECK((flags & ~(GAIB_RELU | GAIB_AGG_SCRATCH | GAIB_ACCUMULATE | GAIB_OVERLAPS_TRANSFER)) == 0,
-             "gaib_spmm_gemm: unsupported flags %d", flags);
-  GAIB_CHECK((d_rows2 == nullptr) == (d_W2 == nullptr), "gaib_spmm_gemm2: rows2 and W2 go together");
-  if (g->nv == 0 || len_out == 0) return GAIB_OK;
-  GAIB_CHECK(d_in && d_agg && d_W && d_out, "gaib_spmm_gemm: NULL pointer");
-  GAIB_CHECK(d_in != d_agg && d_agg != d_out && d_in != d_out && d_rows2 != d_out && d_rows2 != d_agg,
+  GAIB_CHECK(c.len_in >= 0 && c.len_out >= 0, "gaib_spmm_gemm: negative length");
+  GAIB_CHECK(ctx->device == g->device, "gaib_spmm_gemm: graph lives on device %d, ctx on %d", g->device, ctx->device);
+  GAIB_CHECK((c.flags & ~(GAIB_RELU | GAIB_AGG_SCRATCH | GAIB_ACCUMULATE | GAIB_OVERLAPS_TRANSFER)) == 0,
+             "gaib_spmm_gemm: unsupported flags %d", c.flags);
+  GAIB_CHECK((c.d_rows2 == nullptr) == (c.d_W2 == nullptr), "gaib_spmm_gemm2: rows2 and W2 go together");
+  if (g->nv == 0 || c.len_out == 0) return GAIB_OK;
+  GAIB_CHECK(c.d_in && c.d_agg && c.d_W && c.d_out, "gaib_spmm_gemm: NULL pointer");
+  GAIB_CHECK(c.d_in != c.d_agg && c.d_agg != c.d_out && c.d_in != c.d_out && c.d_rows2 != c.d_out && c.d_rows2 != c.d_agg,
              "gaib_spmm_gemm: buffers must not alias");
-  const bool dual = d_rows2 != nullptr;
-  const bool part = g->row_map != nullptr || d_in2 != nullptr;
-  const uintptr_t al = (bf16 ? ((uintptr_t)d_in | (uintptr_t)d_in2) << 1 : ((uintptr_t)d_in | (uintptr_t)d_in2)) | (uintptr_t)d_agg;
-  // the weight matrices [len_out x (len_in+4)] and 16 row strips must fit the CU's 160 KB of LDS;
-  // 65..128 columns need 8-byte lanes
-  const int kpad = len_in <= 64 ? 64 : 128;
-  const bool lanes_ok = len_in <= 64 ? true : (len_in % 2 == 0 && (al & 7) == 0);
+  const int len_in = c.len_in, len_out = c.len_out;
+  const bool dual = c.d_rows2 != nullptr;
+  const bool part = g->row_map != nullptr || c.d_in2 != nullptr;  // a row class of a partition
+  const uintptr_t tables = (uintptr_t)c.d_in | (uintptr_t)c.d_in2;
+  const uintptr_t al = (c.bf16 ? tables << 1 : tables) | (uintptr_t)c.d_agg;  // the fp32 view's alignment
   // dense graphs over a cache-sized table aggregate faster by ordered chunks (spmm_chunk_kernel) than row by row
   // inside the fused kernel: two kernels there
   const bool dense = !part && ctx->spmm_chunked != 0 && len_in % 4 == 0 && (al & 15) == 0 &&
                      (ctx->spmm_chunked == 1 || chunk_rule(ctx, g, len_in));
   // (a row class may be without edges -- isolated interior vertices -- and still owes its rows of y)
-  const bool shape_ok = ctx->spmm_fuse != 0 && !dense && len_in >= 1 && len_in <= 128 && lanes_ok && (g->ne > 0 || part) &&
-                        g->nv >= 1 &&
-                        (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN ||
-                         weight_kind == GAIB_W_MEAN_T || weight_kind == GAIB_W_EDGE);
-  // (the K-slab route of 129..256 columns, described where it runs below)
-  const bool kslab = !part && ctx->spmm_fuse != 0 && !dense && len_in > 128 && len_in <= 256 && len_in % 2 == 0 && (al & 7) == 0 &&
-                     len_out >= 1 && fuse_strip_rows(128, len_out, false) != 0 && g->ne > 0 &&
-                     (weight_kind == GAIB_W_GCN || weight_kind == GAIB_W_MEAN || weight_kind == GAIB_W_MEAN_T ||
-                      weight_kind == GAIB_W_EDGE);
-  if (d_zs) {
-    const int strip = shape_ok ? fuse_strip_rows(kpad, len_out, dual) : 0;
-    const int64_t dense_bytes = g->nc * (int64_t)len_in * 4;
-    // 128 columns: the one-launch fused route.  256 columns (a wide image, gaib_pack_zs_wide): the K-slab route, whose two launches
-    // are one-product launches whatever `dual` says (the self term follows as a dense product).  129 .. 255: a second slab narrower
-    // than 128 columns has no packed form.
+  const bool rows_ok = !dense && (len_in <= 64 || (al & 7) == 0) && (g->ne > 0 || part);
+  const int one = rows_ok ? fuse_shape_strip(ctx, c.weight_kind, len_in, len_out, dual) : 0;
+  const int one1 = rows_ok && dual && !part ? fuse_shape_strip(ctx, c.weight_kind, len_in, len_out, false) : 0;
+  const int slab = !part && ctx->spmm_fuse != 0 && !dense && len_in > 128 && len_in <= 256 && len_in % 2 == 0 && (al & 7) == 0 &&
+                           len_out >= 1 && g->ne > 0 && fuse_kind_ok(c.weight_kind)
+                       ? fuse_strip_rows(128, len_out, false)
+                       : 0;
+  if (one == 0 && one1 != 0) r->kind = ROUTE_FUSED_THEN_GEMM, r->form = fuse_form(ctx, g, c, part, false, one1, false);
+  else if (slab != 0) r->kind = ROUTE_KSLABS, r->form = fuse_form(ctx, g, c, part, false, slab, true);
+  else if (one != 0) r->kind = ROUTE_FUSED, r->form = fuse_form(ctx, g, c, part, dual, one, false);
+  else r->kind = ROUTE_UNFUSED;
+  const FuseForm& fm = r->form;
+  if (c.d_zs) {
+    // 256 columns (a wide image): the K-slab route's launches are one-product launches whatever `dual` says.  129 .. 255: a second
+    // slab narrower than 128 columns has no packed form.  Nor have the 2-row strip with one product, the edge stream the dense call
+    // takes on short rows (20-34 % faster than the row form at 3-5 edges per row), the XCD-affine supply, 64-bit addressing.
     const bool wide = len_in == 256;
-    bool ok = (wide ? kslab : (!part && len_in == 128 && strip == (dual ? 2 : 8))) && dense_bytes < ((int64_t)1 << 32) &&
-              ctx->spmm_addr_mode != 2 && ((uintptr_t)d_zs & 127) == 0;
-    // the variants the dense call would pick for this graph and have no packed form (launch_fused's own predicates): the edge
-    // stream on short rows (20-34 % faster than the row form at 3-5 edges per row), the XCD-affine tile supply on a numbering
-    // with locality.  The caller gathers dense there.
-    if (ok && (wide || !dual) && (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * g->nv))) ok = false;
-    if (ok && tile_xcd_arg(ctx, g) != 0) ok = false;
-    if (!ok) {
+    const bool packed = (wide ? r->kind == ROUTE_KSLABS : (r->kind == ROUTE_FUSED && !part && len_in == 128 && (fm.dual || fm.strip == 8))) &&
+                        fm.buf && !(fm.short_rows && (wide || !fm.dual)) && fm.tile_xcd == 0 && ((uintptr_t)c.d_zs & 127) == 0;
+    if (!packed) {
+      r->kind = ROUTE_REFUSED;
       gaib_set_error("gaib_spmm_gemm_zs: no zero-suppressed gather for this call (whole graph, 128 columns on the one-launch fused route "
                      "or 256 columns -- a wide image -- on the K-slab route, in the row form -- 8-row strip, two products or a K-slab, "
                      "no edge stream, global tile counter --, table below 4 GB, buffer addressing, image on a 128-B boundary)");
       return GAIB_ERR_UNSUPPORTED;
     }
-    if (zs_query) return GAIB_OK;
   }
-  // two products whose matrices do not fit LDS together (SAGE's 100 -> 256 input layer): the neighbour product still
-  // rides on the aggregation, the self term follows as an accumulating GEMM that also applies the activation
-  // (whole graphs only: a row class of a partition -- row map, second feature table -- cannot take this route, the
-  // accumulating GEMM below runs over rows [0, nv) of rows2 / out; it gets GAIB_ERR_UNSUPPORTED further down)
-  if (!part && shape_ok && dual && fuse_strip_rows(kpad, len_out, true) == 0 && fuse_strip_rows(kpad, len_out, false) != 0) {
-    GAIB_TRY(spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out,
-                            flags & ~GAIB_RELU, nullptr, 0, bf16, nullptr, false, ld_bf16));
-    return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2,
-                         GAIB_ACCUMULATE | ((flags & GAIB_RELU) ? GAIB_RELU : 0), d_out);
+  if (part && r->kind == ROUTE_UNFUSED) {
+    // the classes of a partition write disjoint rows of ONE output: the caller (host/aggregators.cpp) asks gaib_spmm_gemm_fusable
+    // first and runs aggregation + one dense product over all rows where the answer is no.  (Nor can a class take the route of two
+    // products that do not fit together: the accumulating product runs over rows [0, nv) of rows2 / out.)
+    r->kind = ROUTE_REFUSED;
+    gaib_set_error("gaib_spmm_gemm: a row class of a partition needs a fusable shape (len_in %d, len_out %d%s): aggregate "
+                   "with gaib_spmm_ex / gaib_spmm_2t and multiply all rows at once", len_in, len_out, dual ? ", two products" : "");
+    return GAIB_ERR_UNSUPPORTED;
   }
-  const bool fusable = shape_ok && fuse_strip_rows(kpad, len_out, dual) != 0;
-  if (part) {
-    // the classes of a partition write disjoint rows of ONE output: the caller (host/aggregators.cpp) asks
-    // gaib_spmm_gemm_fusable first and runs aggregation + one dense product over all rows where the answer is no
-    if (!fusable) {
-      gaib_set_error("gaib_spmm_gemm: a row class of a partition needs a fusable shape (len_in %d, len_out %d%s): aggregate "
-                     "with gaib_spmm_ex / gaib_spmm_2t and multiply all rows at once", len_in, len_out, dual ? ", two products" : "");
-      return GAIB_ERR_UNSUPPORTED;
-    }
-  }
-  // 129..256 columns (the hidden width 256 of scripts/run-sage-products.sh): op(W) does not fit LDS next to the strips,
-  // so the aggregation runs as two 128-column K-slabs through the same kernel, each with its [len_out x 128] slab of
-  // op(W) in LDS: slab 0 writes y = agg[:, :128] . op(W)[:128, :], slab 1 adds agg[:, 128:] . op(W)[128:, :] (and applies
-  // the activation).  The gathered bytes are the same as one 1-KB row gather per edge; colidx / weights are streamed
-  // twice and y is read-modify-written once -- against a separate pass over agg and a 2 x 2.45 M x 256 x 256 GEMM.
-  // A second product (SAGE's self term) follows as an accumulating GEMM.
-  if (kslab) {
-    SpmmArgs a0;
-    int wmode = 0;
-    GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a0, &wmode, nullptr, 0, bf16, ld_bf16));
-    a0.col_flagged = nullptr;  // (the K-slab forms have no hot/cold gather)
-    const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;
-    const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * len_in + 255) & ~(size_t)255;
-    GAIB_TRY(gaib_ws_reserve(ctx, wt_bytes + hv_bytes + 256));
-    float* wt = (float*)ctx->ws;
-    float* hv = (float*)((char*)ctx->ws + wt_bytes);
-    int* counter = (int*)((char*)hv + hv_bytes);
-    const float* wk = d_W;  // [len_out][len_in], k-contiguous
-    if (!transW) {
-      const int n = len_in * len_out;
-      transpose_small_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(len_in, len_out, d_W, wt);
-      GAIB_LAUNCH_CHECK();
-      wk = wt;
-    }
-    for (int k0 = 0; k0 < len_in; k0 += 128) {
-      SpmmArgs a = a0;
-      // (bf16: the slab offset and in_bytes count bf16 elements; the offset is one of columns, whatever the row stride)
-      a.in = bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0) : a0.in + k0;
-      a.ncols = len_in - k0 < 128 ? len_in - k0 : 128;
-      a.accumulate = 0;
-      a.out = (flags & GAIB_AGG_SCRATCH) ? nullptr : d_agg + k0;
-      if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * (bf16 ? 2 : 4));
-      FuseArgs f;
-      f.wt = wk + k0;
-      f.wt2 = nullptr;
-      f.rows2 = nullptr;
-      f.ldw = len_in;
-      f.y = d_out;
-      f.ldy = len_out;
-      f.n_out = len_out;
-      f.tile_counter = counter;
-      f.agg_in = (flags & GAIB_ACCUMULATE) ? d_agg + k0 : nullptr;
-      f.y_accum = k0 > 0;
-      f.overlaps_transfer = (flags & GAIB_OVERLAPS_TRANSFER) ? 1 : 0;
-      f.tile_xcd = tile_xcd_arg(ctx, g);
-      f.relu = ((flags & GAIB_RELU) && !dual && k0 + 128 >= len_in) ? 1 : 0;
-      f.heavy_agg = hv + k0;
-      f.heavy_rows = g->heavy_rows;
-      f.n_heavy = (int)g->n_heavy;
-      if (d_zs) {  // the slab's image in front, the dense table at the slab's first column behind it for over-capacity half rows
-        a.in2 = a.in;
-        a.in2_bytes = a.in_bytes;
-        a.in = reinterpret_cast<const float*>(static_cast<const char*>(d_zs) + (int64_t)(k0 / 128) * g->nc * GAIB_ZS_ROW_BYTES);
-        a.ld = GAIB_ZS_ROW_BYTES / 4;
-        a.in_bytes = (uint32_t)(g->nc * (int64_t)GAIB_ZS_ROW_BYTES);
-        GAIB_TRY(gaib_spmm_kslab_zs(ctx, g, &a, &f, hv + k0, wmode));
-      } else if (bf16) GAIB_TRY(gaib_spmm_fused_bf16(ctx, g, &a, &f, hv + k0, 2, wmode));
-      else GAIB_TRY(wmode == 0 ? (launch_fused<2, 0>(ctx, g, a, f, hv + k0)) : (launch_fused<2, 1>(ctx, g, a, f, hv + k0)));
-    }
-    if (dual)
-      return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2,
-                           GAIB_ACCUMULATE | ((flags & GAIB_RELU) ? GAIB_RELU : 0), d_out);
-    return GAIB_OK;
-  }
-  if (!fusable) {
-    const int act = (flags & GAIB_RELU) ? GAIB_RELU : 0;
-    if (bf16) GAIB_TRY(gaib_spmm_bf16_ld(ctx, g, weight_kind, d_edge_w, len_in, ld_bf16 > 0 ? ld_bf16 : len_in,
-                                         reinterpret_cast<const uint16_t*>(d_in), d_agg, flags & GAIB_ACCUMULATE));
-    else GAIB_TRY(spmm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, flags & GAIB_ACCUMULATE));
-    GAIB_TRY(gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_agg, d_W, dual ? 0 : act, d_out));
-    if (dual) return gaib_sgemm_ex(ctx, 0, transW, g->nv, len_out, len_in, d_rows2, d_W2, GAIB_ACCUMULATE | act, d_out);
-    return GAIB_OK;
-  }
-  SpmmArgs a;
-  int wmode = 0;
-  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, 0, 1, &a, &wmode, d_in2, n_first, bf16, ld_bf16));
-  a.accumulate = 0;  // (the fused kernel takes the partial sums through f.agg_in)
-  a.col_flagged = nullptr;  // (spmm_gather_mode 3 belongs to the row kernels of gaib_spmm)
-  if (!part && !bf16 && !dual)  // (two products: no hot/cold form, nothing to build)
-    a.col_flagged = hot_cold_cols(ctx, g, len_in, len_out, d_zs ? g->nc * (int64_t)GAIB_ZS_ROW_BYTES : g->nc * (int64_t)a.ld * 4, d_zs != nullptr);
-  if (flags & GAIB_AGG_SCRATCH) a.out = nullptr;  // the caller does not read agg: skip its store
-  // scratch: op(W) (and op(W2)) k-contiguous + the heavy rows' aggregates + the tile counter
-  const size_t wt_bytes = (sizeof(float) * (size_t)len_out * len_in + 255) & ~(size_t)255;
-  const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * len_in + 255) & ~(size_t)255;
-  GAIB_TRY(gaib_ws_reserve(ctx, 2 * wt_bytes + hv_bytes + 256));
-  float* wt = (float*)ctx->ws;
-  float* wt2 = (float*)((char*)ctx->ws + wt_bytes);
-  float* hv = (float*)((char*)ctx->ws + 2 * wt_bytes);
-  int* counter = (int*)((char*)hv + hv_bytes);
-  FuseArgs f;
-  f.wt = d_W;  // with transW, W is [len_out x len_in]: already k-contiguous
-  f.wt2 = d_W2;
-  if (!transW) {
-    const int n = len_in * len_out;
-    transpose_small_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(len_in, len_out, d_W, wt);
+  return GAIB_OK;
+}
+
+// the executors' workspace -- op(W) (and op(W2)) k-contiguous, the heavy rows' aggregates, the tile counters -- and the FuseArgs of a launch
+static int fuse_args(gaib_ctx* ctx, const gaib_graph* g, const GemmCall& c, bool dual, FuseArgs* pf) {
+  const size_t wt_bytes = (sizeof(float) * (size_t)c.len_out * c.len_in + 255) & ~(size_t)255;
+  const size_t hv_bytes = (sizeof(float) * (size_t)g->n_heavy * c.len_in + 255) & ~(size_t)255;
+  const int nw = dual ? 2 : 1;
+  GAIB_TRY(gaib_ws_reserve(ctx, nw * wt_bytes + hv_bytes + 256));
+  float* hv = (float*)((char*)ctx->ws + nw * wt_bytes);
+  const float* w[2] = {c.d_W, dual ? c.d_W2 : nullptr};  // with transW, [len_out x len_in]: already k-contiguous
+  for (int i = 0; i < nw && !c.transW; ++i) {
+    float* wt = (float*)((char*)ctx->ws + i * wt_bytes);
+    transpose_small_kernel<<<(c.len_in * c.len_out + 255) / 256, 256, 0, ctx->stream>>>(c.len_in, c.len_out, w[i], wt);
     GAIB_LAUNCH_CHECK();
-    f.wt = wt;
-    if (dual) {
-      transpose_small_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(len_in, len_out, d_W2, wt2);
-      GAIB_LAUNCH_CHECK();
-      f.wt2 = wt2;
-    }
+    w[i] = wt;
   }
-  f.rows2 = d_rows2;
-  f.ldw = len_in;
-  f.y_accum = 0;
-  f.overlaps_transfer = (flags & GAIB_OVERLAPS_TRANSFER) ? 1 : 0;
-  f.tile_xcd = tile_xcd_arg(ctx, g);
-  f.y = d_out;
-  f.ldy = len_out;
-  f.n_out = len_out;
-  f.tile_counter = counter;
-  f.agg_in = (flags & GAIB_ACCUMULATE) ? d_agg : nullptr;
-  f.relu = (flags & GAIB_RELU) ? 1 : 0;
+  FuseArgs& f = *pf;
+  f.wt = w[0];
+  f.wt2 = w[1];
+  f.rows2 = dual ? c.d_rows2 : nullptr;
+  f.ldw = c.len_in;
+  f.y = c.d_out;
+  f.ldy = c.len_out;
+  f.n_out = c.len_out;
+  f.relu = (c.flags & GAIB_RELU) ? 1 : 0;
   f.heavy_agg = hv;
   f.heavy_rows = g->heavy_rows;
   f.n_heavy = (int)g->n_heavy;
-  if (part && bf16) return gaib_spmm_part_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
-  if (part) return gaib_spmm_part_fused(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
-  if (bf16) return gaib_spmm_fused_bf16(ctx, g, &a, &f, hv, len_in <= 64 ? 1 : 2, wmode);
-  if (d_zs) {  // gather from the packed rows; the dense table stays behind them for over-capacity rows
+  f.tile_counter = (int*)((char*)hv + hv_bytes);
+  f.agg_in = (c.flags & GAIB_ACCUMULATE) ? c.d_agg : nullptr;
+  f.overlaps_transfer = (c.flags & GAIB_OVERLAPS_TRANSFER) ? 1 : 0;
+  f.y_accum = f.tile_xcd = 0;  // (the form's: set where the launch happens)
+  return GAIB_OK;
+}
+
+// the aggregation arguments of a fused call: no agg store where the caller does not read it, partial sums through FuseArgs::agg_in
+static int fuse_spmm_args(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, SpmmArgs* a, int* wmode) {
+  GAIB_TRY(spmm_setup(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.d_in, c.d_agg, 0, 1, a, wmode, c.d_in2, c.n_first, c.bf16, c.ld));
+  a->accumulate = 0;
+  a->col_flagged = nullptr;
+  if (c.flags & GAIB_AGG_SCRATCH) a->out = nullptr;
+  return GAIB_OK;
+}
+
+// one fused launch in the form fm with the kernels of the call's table kind; k0: the first column of a K-slab (else 0)
+static int launch_form(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, const FuseForm& fm, SpmmArgs a, const FuseArgs& f, int wmode, int k0) {
+  float* hv = const_cast<float*>(f.heavy_agg);
+  if (c.d_zs) {  // gather from the packed rows of the slab's image; the dense table stays behind them for over-capacity (half) rows
     a.in2 = a.in;
     a.in2_bytes = a.in_bytes;
-    a.in = static_cast<const float*>(d_zs);
+    a.in = reinterpret_cast<const float*>(static_cast<const char*>(c.d_zs) + (int64_t)(k0 / 128) * g->nc * GAIB_ZS_ROW_BYTES);
     a.ld = GAIB_ZS_ROW_BYTES / 4;
     a.in_bytes = (uint32_t)(g->nc * (int64_t)GAIB_ZS_ROW_BYTES);
-    return gaib_spmm_fused_zs(ctx, g, &a, &f, hv, wmode);
+    return c.len_in > 128 ? gaib_spmm_kslab_zs(ctx, g, fm, a, f, hv, wmode) : gaib_spmm_fused_zs(ctx, g, fm, a, f, hv, wmode);
   }
-  if (len_in <= 64) {
-    return wmode == 0 ? launch_fused<1, 0>(ctx, g, a, f, hv) : launch_fused<1, 1>(ctx, g, a, f, hv);
+  if (g->row_map || c.d_in2)
+    return c.bf16 ? gaib_spmm_part_fused_bf16(ctx, g, fm, a, f, hv, wmode) : gaib_spmm_part_fused(ctx, g, fm, a, f, hv, wmode);
+  if (c.bf16) return gaib_spmm_fused_bf16(ctx, g, fm, a, f, hv, wmode);
+  if (fm.vec == 1) return wmode == 0 ? launch_fused<1, 0>(ctx, g, fm, a, f, hv) : launch_fused<1, 1>(ctx, g, fm, a, f, hv);
+  return wmode == 0 ? launch_fused<2, 0>(ctx, g, fm, a, f, hv) : launch_fused<2, 1>(ctx, g, fm, a, f, hv);
+}
+
+static int run_fused(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, FuseForm fm) {
+  SpmmArgs a;
+  int wmode = 0;
+  GAIB_TRY(fuse_spmm_args(ctx, g, c, &a, &wmode));
+  if (fm.hot_cold) {
+    a.col_flagged = hot_cold_cols(ctx, g, c.d_zs ? g->nc * (int64_t)GAIB_ZS_ROW_BYTES : g->nc * a.ld * 4, c.d_zs != nullptr);
+    fm.hot_cold = a.col_flagged != nullptr;
   }
-  return wmode == 0 ? launch_fused<2, 0>(ctx, g, a, f, hv) : launch_fused<2, 1>(ctx, g, a, f, hv);
+  FuseArgs f;
+  GAIB_TRY(fuse_args(ctx, g, c, fm.dual, &f));
+  return launch_form(ctx, g, c, fm, a, f, wmode, 0);
+}
+
+// a product that no launch carries: out (+)= rows . op(W), with the activation
+static int trailing_gemm(gaib_ctx* ctx, const gaib_graph* g, const GemmCall& c, const float* rows, const float* W, int flags) {
+  return gaib_sgemm_ex(ctx, 0, c.transW, g->nv, c.len_out, c.len_in, rows, W, flags | ((c.flags & GAIB_RELU) ? GAIB_RELU : 0), c.d_out);
+}
+
+// 129..256 columns (the hidden width 256 of scripts/run-sage-products.sh): op(W) does not fit LDS next to the strips, so the
+// aggregation runs as two 128-column K-slabs through the same kernel, each with its [len_out x 128] slab of op(W) in LDS.  The
+// gathered bytes are those of one 1-KB row gather per edge; colidx / weights are streamed twice and y is read-modify-written once
+// -- against a separate pass over agg and a 2 x 2.45 M x 256 x 256 GEMM.  What a slab overrides: its column offsets, y += and the
+// row form behind slab 0, the activation on the last slab only.
+static int run_kslabs(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, const FuseForm& fm) {
+  const bool dual = c.d_rows2 != nullptr;
+  SpmmArgs a0;
+  int wmode = 0;
+  GAIB_TRY(fuse_spmm_args(ctx, g, c, &a0, &wmode));
+  FuseArgs f0;
+  GAIB_TRY(fuse_args(ctx, g, c, false, &f0));
+  for (int k0 = 0; k0 < c.len_in; k0 += 128) {
+    SpmmArgs a = a0;
+    // (bf16: the slab offset and in_bytes count bf16 elements; the offset is one of columns, whatever the row stride)
+    a.in = c.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0) : a0.in + k0;
+    a.ncols = c.len_in - k0 < 128 ? c.len_in - k0 : 128;
+    if (a.out) a.out += k0;
+    if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * (c.bf16 ? 2 : 4));
+    FuseArgs f = f0;
+    f.wt += k0;
+    if (f.agg_in) f.agg_in += k0;
+    f.heavy_agg += k0;
+    f.relu = f0.relu && !dual && k0 + 128 >= c.len_in;
+    FuseForm s = fm;
+    s.yacc = k0 > 0;
+    if (s.yacc) s.flat = s.ring = false;
+    GAIB_TRY(launch_form(ctx, g, c, s, a, f, wmode, k0));
+  }
+  return dual ? trailing_gemm(ctx, g, c, c.d_rows2, c.d_W2, GAIB_ACCUMULATE) : GAIB_OK;
+}
+
+static int run_unfused(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c) {
+  const bool dual = c.d_rows2 != nullptr;
+  if (c.bf16) GAIB_TRY(gaib_spmm_bf16_ld(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.ld > 0 ? c.ld : c.len_in,
+                                         reinterpret_cast<const uint16_t*>(c.d_in), c.d_agg, c.flags & GAIB_ACCUMULATE));
+  else GAIB_TRY(spmm_impl(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.d_in, c.d_agg, c.flags & GAIB_ACCUMULATE));
+  if (!dual) return trailing_gemm(ctx, g, c, c.d_agg, c.d_W, 0);
+  GAIB_TRY(gaib_sgemm_ex(ctx, 0, c.transW, g->nv, c.len_out, c.len_in, c.d_agg, c.d_W, 0, c.d_out));
+  return trailing_gemm(ctx, g, c, c.d_rows2, c.d_W2, GAIB_ACCUMULATE);
+}
+
+static int spmm_gemm_run(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c) {
+  GemmRoute r;
+  GAIB_TRY(gemm_route(ctx, g, c, &r));
+  switch (r.kind) {
+    case ROUTE_FUSED: return run_fused(ctx, g, c, r.form);
+    case ROUTE_FUSED_THEN_GEMM: {  // the neighbour product rides on the aggregation, the self term follows and applies the activation
+      GemmCall n = c;
+      n.d_rows2 = n.d_W2 = nullptr;
+      n.flags &= ~GAIB_RELU;
+      GAIB_TRY(run_fused(ctx, g, n, r.form));
+      return trailing_gemm(ctx, g, c, c.d_rows2, c.d_W2, GAIB_ACCUMULATE);
+    }
+    case ROUTE_KSLABS: return run_kslabs(ctx, g, c, r.form);
+    case ROUTE_UNFUSED: return run_unfused(ctx, g, c);
+    default: return GAIB_OK;  // ROUTE_NONE (a refusal has returned its code above)
+  }
 }
 
 extern "C" int gaib_spmm_gemm(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w,
                               int len_in, const float* d_in, float* d_agg, const float* d_W, int transW,
                               int len_out, float* d_out, int flags) {
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out,
-                        d_out, flags);
+  return spmm_gemm_run(ctx, g, GemmCall{weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out, flags});
 }
 
 extern "C" int gaib_spmm_gemm2(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w,
                                int len_in, const float* d_in, float* d_agg, const float* d_W, int transW,
                                const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags) {
   GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2: NULL second operand");
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out,
-                        d_out, flags);
+  return spmm_gemm_run(ctx, g, GemmCall{weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags});
 }
 
 // Would gaib_spmm_gemm_zs / gaib_spmm_gemm2_zs (d_rows2 != NULL) take this call?  GAIB_OK or GAIB_ERR_UNSUPPORTED from the route
-// information alone: nothing is launched, nothing is read through the pointers -- a caller asks BEFORE it packs.
+// function alone: nothing is launched, nothing is read through the pointers -- a caller asks BEFORE it packs.
 extern "C" int gaib_spmm_gemm_zs_route(gaib_ctx* ctx, gaib_graph* g, int weight_kind, int len_in, const float* d_in, const void* d_zs,
                                        float* d_agg, const float* d_rows2, int len_out, float* d_out) {
   GAIB_CHECK(d_zs, "gaib_spmm_gemm_zs_route: NULL packed table");
-  return spmm_gemm_impl(ctx, g, weight_kind, nullptr, len_in, d_in, d_agg, d_in, 1, d_rows2, d_rows2 ? d_in : nullptr, len_out, d_out,
-                        0, nullptr, 0, false, d_zs, true);
+  GemmCall c{weight_kind, nullptr, len_in, d_in, d_agg, d_in, 1, d_rows2, d_rows2 ? d_in : nullptr, len_out, d_out, 0};
+  c.d_zs = d_zs;
+  GemmRoute r;
+  return gemm_route(ctx, g, c, &r);
 }
 
 // agg = A.in ; out = act(agg . op(W) [+ rows2 . op(W2)]) gathering from the zero-suppressed image d_zs of d_in (gaib_pack_zs at 128
@@ -738,8 +808,9 @@ extern "C" int gaib_spmm_gemm_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, 
                                  float* d_out, int flags) {
   GAIB_CHECK(d_zs, "gaib_spmm_gemm_zs: NULL packed table");
   GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm_zs: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which gather dense tables");
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out, flags,
-                        nullptr, 0, false, d_zs);
+  GemmCall c{weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, nullptr, nullptr, len_out, d_out, flags};
+  c.d_zs = d_zs;
+  return spmm_gemm_run(ctx, g, c);
 }
 
 extern "C" int gaib_spmm_gemm2_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
@@ -748,8 +819,9 @@ extern "C" int gaib_spmm_gemm2_zs(gaib_ctx* ctx, gaib_graph* g, int weight_kind,
   GAIB_CHECK(d_zs, "gaib_spmm_gemm2_zs: NULL packed table");
   GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_zs: NULL second operand");
   GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm2_zs: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which gather dense tables");
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags,
-                        nullptr, 0, false, d_zs);
+  GemmCall c{weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags};
+  c.d_zs = d_zs;
+  return spmm_gemm_run(ctx, g, c);
 }
 
 extern "C" int gaib_spmm_gemm_2t(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
@@ -758,8 +830,10 @@ extern "C" int gaib_spmm_gemm_2t(gaib_ctx* ctx, gaib_graph* g, int weight_kind, 
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm_2t: NULL ctx/graph");
   GAIB_CHECK(d_in2 || n_first >= g->nc || g->nv == 0 || g->ne == 0, "gaib_spmm_gemm_2t: NULL second table with columns beyond n_first");
   GAIB_CHECK(!d_in2 || (d_in2 != d_agg && d_in2 != d_out), "gaib_spmm_gemm_2t: buffers must not alias");
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags,
-                        d_in2, n_first);
+  GemmCall c{weight_kind, d_edge_w, len_in, d_in, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags};
+  c.d_in2 = d_in2;
+  c.n_first = n_first;
+  return spmm_gemm_run(ctx, g, c);
 }
 
 extern "C" int gaib_spmm_mh(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w,
@@ -902,8 +976,10 @@ static int spmm_gemm_bf16_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, c
     gaib_set_error("gaib_spmm_gemm_bf16: a row class of a partition (graph with a row map) is not supported: fp32 tables only");
     return GAIB_ERR_UNSUPPORTED;
   }
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2,
-                        d_W2, len_out, d_out, flags, nullptr, 0, true, nullptr, false, ld);
+  GemmCall c{weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags};
+  c.bf16 = true;
+  c.ld = ld;
+  return spmm_gemm_run(ctx, g, c);
 }
 
 extern "C" int gaib_spmm_gemm_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in,
@@ -961,7 +1037,7 @@ extern "C" int gaib_spmm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight_kind
                       reinterpret_cast<const float*>(d_in2), n_first, true));
   GAIB_CHECK(wmode <= 1, "gaib_spmm_part_bf16: a row class of a partition aggregates with GAIB_W_GCN / _MEAN / _MEAN_T / single-head "
                          "_EDGE weights (got kind %d)", weight_kind);
-  return gaib_spmm_part_plain_bf16(ctx, g, &a, wmode, len);
+  return gaib_spmm_part_plain_bf16(ctx, g, a, wmode, len);
 }
 
 // gaib_spmm_gemm_2t with the table(s) in bf16 (d_rows2 / d_W2: both or NULL; d_in2 may be NULL): the route of the fp32 call on the
@@ -973,6 +1049,9 @@ extern "C" int gaib_spmm_gemm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight
   GAIB_CHECK(ctx && g, "gaib_spmm_gemm_part_bf16: NULL ctx/graph");
   GAIB_CHECK(!d_in2 || ((const void*)d_in2 != (const void*)d_agg && (const void*)d_in2 != (const void*)d_out),
              "gaib_spmm_gemm_part_bf16: buffers must not alias");
-  return spmm_gemm_impl(ctx, g, weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2,
-                        d_W2, len_out, d_out, flags, reinterpret_cast<const float*>(d_in2), n_first, true);
+  GemmCall c{weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_in), d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags};
+  c.d_in2 = reinterpret_cast<const float*>(d_in2);
+  c.n_first = n_first;
+  c.bf16 = true;
+  return spmm_gemm_run(ctx, g, c);
 }

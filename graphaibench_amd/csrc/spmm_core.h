@@ -4,8 +4,7 @@
 #include <type_traits>
 #include "common.h"
 
-namespace {
-
+// (outside the unnamed namespace: the launchers declared in spmm_kernels.h pass it by reference between translation units)
 struct SpmmArgs {
   const int64_t* rowptr;
   const uint32_t* col;
@@ -40,6 +39,8 @@ struct SpmmArgs {
   uint32_t n_first;          //   rank's own rows.  in2 == NULL: one table, n_first = 0xffffffff
   uint32_t in2_bytes;        // BUF kernels: size of the second table (< 4 GB; of its bf16 bits when the tables are bf16)
 };
+
+namespace {
 
 // the row of the caller's matrices that row r of the graph stands for
 template <bool PART>

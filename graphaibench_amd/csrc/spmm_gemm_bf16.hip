@@ -5,19 +5,16 @@
 // flight and widened exactly (bits << 16) where consumed.  Weights, the CSR order of a row's additions with separate multiply
 // and add, the heavy threshold and its 16-wave LDS combine, partial sums, op(W) in LDS, the MFMA loop and every store are the
 // fp32 kernels' own, so agg and y are bit-identical to gaib_spmm_gemm on the widened table.  The route (fused, two K-slabs,
-// fused + accumulating GEMM, two kernels) is chosen by spmm_gemm_impl (spmm.hip) on what the fp32 call would see.
+// fused + accumulating GEMM, two kernels) is chosen by the route function of spmm.hip (gemm_route) on what the fp32 call would see.
 // No reference counterpart (the reference aggregates and multiplies fp32 tables in separate passes:
 // src/gnn/gconv/gcn_aggregator.cpp:48-77, include/gnn/graph_operations.h:8-178).
 // A translation unit of its own so that this set of instantiations compiles next to spmm.hip's.
 #include "spmm_kernels.h"
 
-int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                         int vec, int wmode) {
-  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
-  const FuseArgs& f = *static_cast<const FuseArgs*>(fuse_args);
-  if (vec == 1)
-    return wmode == 0 ? launch_fused<1, 0, false, uint16_t>(ctx, g, a, f, heavy_scratch)
-                      : launch_fused<1, 1, false, uint16_t>(ctx, g, a, f, heavy_scratch);
-  return wmode == 0 ? launch_fused<2, 0, false, uint16_t>(ctx, g, a, f, heavy_scratch)
-                    : launch_fused<2, 1, false, uint16_t>(ctx, g, a, f, heavy_scratch);
+int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode) {
+  if (fm.vec == 1)
+    return wmode == 0 ? launch_fused<1, 0, false, uint16_t>(ctx, g, fm, a, f, heavy_scratch)
+                      : launch_fused<1, 1, false, uint16_t>(ctx, g, fm, a, f, heavy_scratch);
+  return wmode == 0 ? launch_fused<2, 0, false, uint16_t>(ctx, g, fm, a, f, heavy_scratch)
+                    : launch_fused<2, 1, false, uint16_t>(ctx, g, fm, a, f, heavy_scratch);
 }

@@ -331,6 +331,8 @@ int dispatch_vec(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a0, int len
 // issued between gathers waits ~5 us behind them (measured: +1.5 ms per pass at products scale);
 // from LDS the dense product costs only the y store.
 // Heavy rows are aggregated first by spmm_heavy_kernel into a compact scratch and picked up here.
+}  // namespace
+
 struct FuseArgs {
   const float* wt;            // [n_out][K]
   float* y;                   // [n_rows][ldy]
@@ -350,25 +352,32 @@ struct FuseArgs {
   int tile_xcd;               // 0: one global counter; n > 0: tiles off eight per-XCD counters over interleaved chunks of 2^(n-1) tiles
 };
 
-// option spmm_tile_xcd -> FuseArgs::tile_xcd (0 = global counter, else log2(chunk length in tiles) + 1).
-// -1 (default): by the graph's numbering -- XCD-affine chunks of 1024 tiles when at least a quarter of the edges stay
-// within 32 768 ids of their row, else the global counter.  Measured (scripts/ab_tile_xcd.py, products size, D = 128): a
-// numbering with planted locality 5.94 -> 5.01 ms at 512-1024 tiles per chunk (6.2 ms at 16-128: an XCD's 512 waves in
-// flight then span 65 536 rows); a random numbering 7.60 -> 7.80 ms with ANY chunk length, and 8.1 ms with eight counters
-// WITHOUT the XCD affinity -- i.e. on a random order the one shared in-order window over the streamed arrays is worth 3 %,
-// hence the rule instead of one setting.  1 = the round-2 form (16-tile chunks); n = chunk length, rounded down to 2^k.
-static int tile_xcd_arg(gaib_ctx* ctx, gaib_graph* g) {
-  int v = ctx->spmm_tile_xcd;
-  if (v < 0) {
-    if (gaib_graph_ensure_locality(ctx, g) != GAIB_OK) return 0;
-    v = g->near_frac >= 0.25f ? 1024 : 0;
-  }
-  if (v <= 0) return 0;
-  if (v == 1) v = 16;
-  int sh = 0;
-  while ((2 << sh) <= v) ++sh;
-  return sh + 1;
-}
+// The form of one fused launch.  The route function of spmm.hip decides it once (gemm_route / fuse_form: the table of routes and
+// forms stands there); launch_fused and the packed launchers of spmm_gemm_zs.hip dispatch on it and derive none of it again.
+struct FuseForm {
+  int vec;          // lane width in floats: 1 (up to 64 columns) or 2 (65 .. 128, and every K-slab)
+  int strip;        // rows a wave parks in LDS at a time: 8 or 2 (fuse_strip_rows)
+  bool dual;        // two products in this launch
+  bool short_rows;  // the edge-stream rule holds on this graph (edge_stream_rule: option spmm_flat, edges per row) ...
+  bool flat;        // ... and this launch takes the edge stream: one product, 8-row strip, not a later K-slab
+  bool ring;        // the edge stream as a software pipeline (option spmm_flat_ring)
+  bool buf;         // buffer addressing: every table below 4 GB and option spmm_addr_mode != 2; else 64-bit addresses
+  bool yacc;        // y += : a later K-slab (FuseArgs::y_accum)
+  bool hot_cold;    // hot/cold gathers through the graph's flagged column ids (SpmmArgs::col_flagged)
+  int tile_xcd;     // tile supply (FuseArgs::tile_xcd): 0 on row classes and bf16 tables
+};
+
+// the launchers in translation units of their own: row classes (spmm_part.hip, spmm_part_bf16.hip), the fused kernels over a bf16
+// table (spmm_gemm_bf16.hip) and over a zero-suppressed one (spmm_gemm_zs.hip: one launch, or one K-slab of a 256-column aggregation)
+int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a, int wmode, int len);
+int gaib_spmm_part_plain_bf16(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a, int wmode, int len);
+int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+int gaib_spmm_kslab_zs(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+
+namespace {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int FUSE_ROWS = 16;
@@ -888,34 +897,21 @@ inline int fuse_strip_rows(int kpad, int n_out, bool dual) {
   return fuse_lds_bytes(kpad, n_out, dual, 2) <= 160 * 1024 ? 2 : 0;
 }
 
-// E = uint16_t: a.in (and a.in2) point at bf16 bits, a.ld counts elements, a.in_bytes / a.in2_bytes are the bf16 sizes.  Gathers in flight
-// per wave: a bf16 gather is held packed (half the registers of an fp32 one), so the row forms keep GAIB_BF16_FUSE_U of them where
-// fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  The XCD-affine tile supply is not compiled in for bf16 (it would
-// triple this set of instantiations for the planted-locality case alone; the supply changes no row's sum): global counter.
-template <int VEC, int WMODE, bool PART = false, typename E = float>
-int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
-  constexpr bool BF = sizeof(E) == 2;
-  constexpr int U = 16;                               // the heavy kernel's, and the fp32 row forms'
-  constexpr int UROW = BF ? GAIB_BF16_FUSE_U : U;     // row forms
-  constexpr int UFLAT = BF ? 16 : 8;                  // edge-stream forms
+// What every fused launcher starts with (launch_fused below, the packed launchers of spmm_gemm_zs.hip): the form's fields the
+// kernel reads set, the heavy rows aggregated into the scratch by spmm_heavy_kernel, the grid with its CU reserve, the tile
+// counters zeroed, and the profile row of the launch that follows (a zero-suppressed table is priced on the dense formula under
+// the dense keys: a work rate in dense bytes).
+struct FusedLaunch { unsigned grid; size_t lds; const char* key; double bytes, flops; };
+template <int VEC, int WMODE, bool PART, typename E>
+int fused_prologue(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArgs& a, FuseArgs& f, float* heavy_scratch, FusedLaunch* fl) {
+  constexpr bool BF = sizeof(E) == 2, ZS = ZsTraits<E>::zs;
+  // the hot/cold forms are compiled for 8-B lanes over an fp32 or zero-suppressed table of a whole graph
+  constexpr bool HC = !PART && VEC == 2 && (std::is_same<E, float>::value || std::is_same<E, zs_t>::value);
+  constexpr int U = 16;
   constexpr double EB = sizeof(E);
-  constexpr int K = 64 * VEC;
-  // buffer loads need every table below 4 GB
-  const bool buf = a.in_bytes != 0 && ctx->spmm_addr_mode != 2 && (!PART || !a.in2 || a.in2_bytes != 0);
-  if constexpr (PART || BF) f.tile_xcd = 0;
-  const bool dual = f.wt2 != nullptr;
-  const int strip = fuse_strip_rows(K, f.n_out, dual);  // 8, 2 or 0 (does not fit: the caller checked)
-  // short rows (fewer than 12 edges per row on average: halo-column halves, citation graphs): the edge-stream form
-  // (scripts/ab_flat.py: -34 % at 3 edges per row, -20 % at 5, even at 12, +2 % at 30)
-  const bool flat = !dual && strip == 8 && !f.y_accum &&
-                    (ctx->spmm_flat >= 1 || (ctx->spmm_flat < 0 && g->ne < 12 * (int64_t)a.n_rows));
-  // hot/cold gathers (option spmm_hot_cold; a.col_flagged is set by the caller when the option resolves to on and the graph's
-  // flagged column ids exist): compiled for ONE form only -- 8-B lanes, row form, 8-row strip, one product, global tile counter,
-  // buffer addressing -- and for the heavy kernel next to it.  Every other form reads the plain ids with the default policy.
-  bool hot_cold = false;
-  if constexpr (!PART && !BF && VEC == 2)
-    hot_cold = a.col_flagged && buf && !dual && strip == 8 && !flat && !f.y_accum && f.tile_xcd == 0;
-  if (hot_cold) a.col = a.col_flagged;
+  f.y_accum = fm.yacc;
+  f.tile_xcd = fm.tile_xcd;
+  if (fm.hot_cold) a.col = a.col_flagged;
   if (g->n_heavy > 0) {
     SpmmArgs h = a;
     h.row_list = g->heavy_rows;
@@ -924,39 +920,59 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
     h.compact = 1;  // (row k of the scratch has the stride of the output rows, h.ldo)
     h.relu = 0;
     h.accumulate = 0;
-    size_t lds = sizeof(float) * HEAVY_WAVES * 64 * VEC;
+    const size_t lds = sizeof(float) * HEAVY_WAVES * 64 * VEC;
+    const dim3 hgrid((unsigned)g->n_heavy);
     ProfScope ps(ctx, BF ? "spmm_bf16_heavy" : "spmm_heavy",
                  gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1, EB),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
-    bool launched_h = false;
-    if constexpr (!PART && !BF && VEC == 2) {
-      if (hot_cold) {
-        spmm_heavy_kernel<VEC, 1, WMODE, U, 3, false, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
-        launched_h = true;
+    bool launched = false;
+    if constexpr (HC) {
+      if (fm.hot_cold) {
+        spmm_heavy_kernel<VEC, 1, WMODE, U, 3, false, E><<<hgrid, HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+        launched = true;
       }
     }
-    if (launched_h) {
-    } else if (buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
-    else spmm_heavy_kernel<VEC, 1, WMODE, U, 0, PART, E><<<dim3((unsigned)g->n_heavy), HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    if constexpr (ZS) {  // (the packed gather has buffer addressing only)
+      if (!launched) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<hgrid, HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    } else if (launched) {
+    } else if (fm.buf) spmm_heavy_kernel<VEC, 1, WMODE, U, 1, PART, E><<<hgrid, HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
+    else spmm_heavy_kernel<VEC, 1, WMODE, U, 0, PART, E><<<hgrid, HEAVY_WAVES * 64, lds, ctx->stream>>>(h);
     GAIB_LAUNCH_CHECK();
   }
-  const size_t lds = fuse_lds_bytes(K, f.n_out, dual, strip);
+  fl->lds = fuse_lds_bytes(64 * VEC, f.n_out, fm.dual, fm.strip);
   const int64_t ntiles = cdiv64(a.n_rows, FUSE_ROWS);
   int cus = ctx->spmm_fuse_cus > 0 ? ctx->spmm_fuse_cus : ctx->num_cus;
   // a halo exchange is in flight on the communication stream (the caller said so): its kernels need CUs to land on, and a
   // persistent workgroup of this kernel owns its CU's registers until the last tile (measured: 224 of 256 CUs cost 1.5 %)
   if (f.overlaps_transfer && gaib_comm_reserve(ctx) > 0) cus = std::max(cus - gaib_comm_reserve(ctx), std::min(cus, 64));
-  const unsigned grid = (unsigned)std::min<int64_t>(cus, cdiv64(ntiles, FUSE_WAVES));
+  fl->grid = (unsigned)std::min<int64_t>(cus, cdiv64(ntiles, FUSE_WAVES));
   GAIB_HIP(hipMemsetAsync(f.tile_counter, 0, 8 * sizeof(int), ctx->stream));  // one counter per XCD
   // SURVEY 8(d) for the aggregation part (the heavy rows' edges are the heavy kernel's) + what the riding product moves: the
   // aggregate rows stored (unless scratch) or continued (agg_in), y written (read too on a later K-slab), the second row operand
   const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_all = (double)a.n_rows;
-  const double fused_bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (dual ? 1 : 0), EB) +
-                             r_all * 4.0 * f.n_out * (f.y_accum ? 2 : 1);
-  const double fused_flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (dual ? 2 : 1);
-  ProfScope ps(ctx, BF ? (!PART ? "spmm_gemm_bf16_fused" : (a.in2 ? "part_bf16_fused_2t" : (f.agg_in ? "part_bf16_fused_acc" : "part_bf16_fused")))
-                       : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused")), fused_bytes,
-               fused_flops, a.ncols);
+  fl->bytes = gaib_alg_spmm_bytes(e_l, r_all, a.ncols, WMODE == 0 ? 0 : 4, (a.out ? 1 : 0) + (f.agg_in ? 1 : 0) + (fm.dual ? 1 : 0), EB) +
+              r_all * 4.0 * f.n_out * (fm.yacc ? 2 : 1);
+  fl->flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (fm.dual ? 2 : 1);
+  fl->key = BF ? (!PART ? "spmm_gemm_bf16_fused" : (a.in2 ? "part_bf16_fused_2t" : (f.agg_in ? "part_bf16_fused_acc" : "part_bf16_fused")))
+               : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused"));
+  return GAIB_OK;
+}
+
+// One fused launch in the form fm (decided by spmm.hip's route function).  E = uint16_t: a.in (and a.in2) point at bf16 bits, a.ld counts elements, a.in_bytes / a.in2_bytes are the bf16 sizes.  Gathers in flight
+// per wave: a bf16 gather is held packed (half the registers of an fp32 one), so the row forms keep GAIB_BF16_FUSE_U of them where
+// fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  The XCD-affine tile supply is not compiled in for bf16 (it would
+// triple this set of instantiations for the planted-locality case alone; the supply changes no row's sum) nor for row classes
+// (rectangular graphs: their numbering is never measured as local): the form says global counter there.
+// Hot/cold gathers are compiled for ONE form only -- 8-B lanes, row form, 8-row strip, one product, global tile counter, buffer
+// addressing -- and for the heavy kernel next to it (fused_prologue).
+template <int VEC, int WMODE, bool PART = false, typename E = float>
+int launch_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
+  constexpr bool BF = sizeof(E) == 2;
+  constexpr int UROW = BF ? GAIB_BF16_FUSE_U : 16;  // row forms
+  constexpr int UFLAT = BF ? 16 : 8;                 // edge-stream forms
+  FusedLaunch fl;
+  GAIB_TRY((fused_prologue<VEC, WMODE, PART, E>(ctx, g, fm, a, f, heavy_scratch, &fl)));
+  ProfScope ps(ctx, fl.key, fl.bytes, fl.flops, a.ncols);
   // more than 64 KB of dynamic LDS has to be asked for
   // (the edge-stream form keeps 8 gathers in flight, not 16: with 16 the operand fragments of the dense product
   // spill and are reloaded inside the MFMA loop)
@@ -968,79 +984,60 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a, FuseArgs f, flo
         (const void*)spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE, E>,          \
         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                     \
     spmm_gemm_kernel<VEC, WMODE, UU, GM, STRIP, DUAL, FLAT, YACC, PART, RING, AFF, PRE, E>                            \
-        <<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);                                                    \
+        <<<dim3(fl.grid), FUSE_WAVES * 64, fl.lds, ctx->stream>>>(a, f);                                              \
   } while (0)
-#define GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, AFF)                                                   \
-  do {                                                                                                                \
-    if constexpr (AFF && !FLAT) {                                                                                     \
-      if (ctx->spmm_prefetch_ids) GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, AFF, true);                  \
-      else GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, AFF, false);                                        \
-    } else {                                                                                                          \
-      GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, AFF, false);                                             \
-    }                                                                                                                 \
-  } while (0)
-  // (row classes of a partition are rectangular graphs: their numbering is never measured as local, no affine variants)
+  // (the affine variants exist for fp32 tables of whole graphs, with the next row's ids prefetched in the row forms)
 #define GAIB_FUSED_LAUNCH_R(GM, STRIP, DUAL, FLAT, YACC, RING)                                                        \
   do {                                                                                                                \
+    bool affine = false;                                                                                              \
     if constexpr (!PART && !BF) {                                                                                     \
-      if (f.tile_xcd) GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, true);                                   \
-      else GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, false);                                             \
-    } else {                                                                                                          \
-      GAIB_FUSED_LAUNCH_A(GM, STRIP, DUAL, FLAT, YACC, RING, false);                                                  \
+      if (fm.tile_xcd) {                                                                                              \
+        affine = true;                                                                                                \
+        if (!FLAT && ctx->spmm_prefetch_ids) GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, true, !FLAT);     \
+        else GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, true, false);                                     \
+      }                                                                                                               \
     }                                                                                                                 \
+    if (!affine) GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, false, false);                                \
   } while (0)
-#define GAIB_FUSED_LAUNCH_Y(GM, STRIP, DUAL, FLAT, YACC) GAIB_FUSED_LAUNCH_R(GM, STRIP, DUAL, FLAT, YACC, false)
-#define GAIB_FUSED_LAUNCH(GM, STRIP, DUAL, FLAT) GAIB_FUSED_LAUNCH_Y(GM, STRIP, DUAL, FLAT, false)
-  const bool ring = flat && ctx->spmm_flat_ring != 0;  // the edge stream as a software pipeline (see RING)
+#define GAIB_FUSED_LAUNCH(STRIP, DUAL, FLAT, YACC, RING)                                                              \
+  do {                                                                                                                \
+    if (fm.buf) GAIB_FUSED_LAUNCH_R(1, STRIP, DUAL, FLAT, YACC, RING);                                                \
+    else GAIB_FUSED_LAUNCH_R(0, STRIP, DUAL, FLAT, YACC, RING);                                                       \
+  } while (0)
+  bool launched = false;
   // option spmm_bf16_fuse_u (benchmark only): the other depth of the A/B, on the headline variant alone -- bf16 row form,
   // 8-row strip, buffer addressing, 8-B lanes (whole graphs)
-  bool launched = false;
   if constexpr (BF && VEC == 2 && !PART) {
     constexpr int UALT = UROW == 32 ? 16 : 32;
-    if (ctx->spmm_bf16_fuse_u == UALT && buf && !dual && strip == 8 && !flat && !f.y_accum) {
+    if (ctx->spmm_bf16_fuse_u == UALT && fm.buf && !fm.dual && fm.strip == 8 && !fm.flat && !fm.yacc) {
       GAIB_HIP(hipFuncSetAttribute((const void*)spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       spmm_gemm_kernel<2, WMODE, UALT, 1, 8, false, false, false, false, false, false, false, E>
-          <<<dim3(grid), FUSE_WAVES * 64, lds, ctx->stream>>>(a, f);
+          <<<dim3(fl.grid), FUSE_WAVES * 64, fl.lds, ctx->stream>>>(a, f);
       launched = true;
     }
   }
   if constexpr (!PART && !BF && VEC == 2) {
-    if (hot_cold) {
+    if (fm.hot_cold) {
       GAIB_FUSED_LAUNCH_P(3, 8, false, false, false, false, false, false);
       ctx->spmm_hot_cold_launches++;
       launched = true;
     }
   }
   if (launched) {
-  } else if (f.y_accum) {  // the second K-slab of a 129..256-column aggregation (VEC == 2 only; never dual or flat; not on row classes)
+  } else if (fm.yacc) {  // a later K-slab of a 129..256-column aggregation (8-B lanes, whole graphs; never two products or the edge stream)
     if constexpr (VEC == 2 && !PART) {
-      if (buf) {
-        if (strip == 2) GAIB_FUSED_LAUNCH_Y(1, 2, false, false, true);
-        else GAIB_FUSED_LAUNCH_Y(1, 8, false, false, true);
-      } else {
-        if (strip == 2) GAIB_FUSED_LAUNCH_Y(0, 2, false, false, true);
-        else GAIB_FUSED_LAUNCH_Y(0, 8, false, false, true);
-      }
+      if (fm.strip == 2) GAIB_FUSED_LAUNCH(2, false, false, true, false);
+      else GAIB_FUSED_LAUNCH(8, false, false, true, false);
     }
-  } else if (buf) {
-    if (dual) GAIB_FUSED_LAUNCH(1, 2, true, false);
-    else if (strip == 2) GAIB_FUSED_LAUNCH(1, 2, false, false);
-    else if (flat && ring) GAIB_FUSED_LAUNCH_R(1, 8, false, true, false, true);
-    else if (flat) GAIB_FUSED_LAUNCH(1, 8, false, true);
-    else GAIB_FUSED_LAUNCH(1, 8, false, false);
-  } else {
-    if (dual) GAIB_FUSED_LAUNCH(0, 2, true, false);
-    else if (strip == 2) GAIB_FUSED_LAUNCH(0, 2, false, false);
-    else if (flat && ring) GAIB_FUSED_LAUNCH_R(0, 8, false, true, false, true);
-    else if (flat) GAIB_FUSED_LAUNCH(0, 8, false, true);
-    else GAIB_FUSED_LAUNCH(0, 8, false, false);
-  }
-#undef GAIB_FUSED_LAUNCH_A
+  } else if (fm.dual) GAIB_FUSED_LAUNCH(2, true, false, false, false);
+  else if (fm.strip == 2) GAIB_FUSED_LAUNCH(2, false, false, false, false);
+  else if (fm.ring) GAIB_FUSED_LAUNCH(8, false, true, false, true);
+  else if (fm.flat) GAIB_FUSED_LAUNCH(8, false, true, false, false);
+  else GAIB_FUSED_LAUNCH(8, false, false, false, false);
 #undef GAIB_FUSED_LAUNCH_P
 #undef GAIB_FUSED_LAUNCH_R
 #undef GAIB_FUSED_LAUNCH
-#undef GAIB_FUSED_LAUNCH_Y
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

@@ -59,15 +59,11 @@ int part_vec(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a0, int len) {
 
 }  // namespace
 
-int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len) {
-  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
+int gaib_spmm_part_plain(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a, int wmode, int len) {
   return wmode == 0 ? part_vec<0>(ctx, g, a, len) : part_vec<1>(ctx, g, a, len);
 }
 
-int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                         int vec, int wmode) {
-  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
-  const FuseArgs& f = *static_cast<const FuseArgs*>(fuse_args);
-  if (vec == 1) return wmode == 0 ? launch_fused<1, 0, true>(ctx, g, a, f, heavy_scratch) : launch_fused<1, 1, true>(ctx, g, a, f, heavy_scratch);
-  return wmode == 0 ? launch_fused<2, 0, true>(ctx, g, a, f, heavy_scratch) : launch_fused<2, 1, true>(ctx, g, a, f, heavy_scratch);
+int gaib_spmm_part_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode) {
+  if (fm.vec == 1) return wmode == 0 ? launch_fused<1, 0, true>(ctx, g, fm, a, f, heavy_scratch) : launch_fused<1, 1, true>(ctx, g, fm, a, f, heavy_scratch);
+  return wmode == 0 ? launch_fused<2, 0, true>(ctx, g, fm, a, f, heavy_scratch) : launch_fused<2, 1, true>(ctx, g, fm, a, f, heavy_scratch);
 }

@@ -5,7 +5,7 @@
 // descriptors the (wave-uniform) column id selects -- or the 64-bit path --, held as the packed words it arrived in and widened
 // exactly (bits << 16) where it is consumed.  Weights, the CSR order of a row's additions with separate multiply and add, the heavy
 // threshold and its 16-wave LDS combine, the GAIB_ACCUMULATE continuation, op(W) in LDS, the MFMA loop and every store are the
-// fp32 kernels' own, and the route is chosen on the fp32 sizes (spmm_gemm_impl, spmm.hip): results are bit-identical to
+// fp32 kernels' own, and the route is chosen on the fp32 sizes (gemm_route, spmm.hip): results are bit-identical to
 // gaib_spmm_ex / gaib_spmm_2t / gaib_spmm_gemm_2t on the tables widened to fp32.
 // No reference counterpart (the reference has no multi-GPU GNN and aggregates fp32 tables:
 // src/gnn/gconv/gcn_aggregator.cpp:48-77; the partition structure is src/partitioner/graph_partition.cc:70-80,128-178).
@@ -66,20 +66,16 @@ int part_vec_bf16(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a0, int le
 
 }  // namespace
 
-int gaib_spmm_part_plain_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, int wmode, int len) {
-  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
+int gaib_spmm_part_plain_bf16(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a, int wmode, int len) {
   return wmode == 0 ? part_vec_bf16<0>(ctx, g, a, len) : part_vec_bf16<1>(ctx, g, a, len);
 }
 
 // row forms with 8- and 2-row strips, two products, the edge stream in batches and as a software pipeline; gathers in flight as
 // in the whole-graph bf16 kernels (launch_fused).  No XCD-affine variants, as for every PART instantiation.
-int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const void* spmm_args, const void* fuse_args, float* heavy_scratch,
-                              int vec, int wmode) {
-  const SpmmArgs& a = *static_cast<const SpmmArgs*>(spmm_args);
-  const FuseArgs& f = *static_cast<const FuseArgs*>(fuse_args);
-  if (vec == 1)
-    return wmode == 0 ? launch_fused<1, 0, true, bf16_t>(ctx, g, a, f, heavy_scratch)
-                      : launch_fused<1, 1, true, bf16_t>(ctx, g, a, f, heavy_scratch);
-  return wmode == 0 ? launch_fused<2, 0, true, bf16_t>(ctx, g, a, f, heavy_scratch)
-                    : launch_fused<2, 1, true, bf16_t>(ctx, g, a, f, heavy_scratch);
+int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode) {
+  if (fm.vec == 1)
+    return wmode == 0 ? launch_fused<1, 0, true, bf16_t>(ctx, g, fm, a, f, heavy_scratch)
+                      : launch_fused<1, 1, true, bf16_t>(ctx, g, fm, a, f, heavy_scratch);
+  return wmode == 0 ? launch_fused<2, 0, true, bf16_t>(ctx, g, fm, a, f, heavy_scratch)
+                    : launch_fused<2, 1, true, bf16_t>(ctx, g, fm, a, f, heavy_scratch);
 }
