@@ -22,6 +22,7 @@ static float* common_ptr(L* l, int which) {
     case GAIBL_W_NEIGH_GRAD: return l->weight_neigh_grad_ptr();
     case GAIBL_W_SELF: return l->weight_self_ptr();
     case GAIBL_W_SELF_GRAD: return l->weight_self_grad_ptr();
+    case GAIBL_FEAT_MASK: return reinterpret_cast<float*>(l->feat_mask_ptr());
     default: return nullptr;
   }
 }
@@ -129,7 +130,7 @@ void gaibl_layer_set_phase(void* layer, int phase) {
 
 float* gaibl_layer_ptr(void* layer, int which) {
   LayerBox* b = static_cast<LayerBox*>(layer);
-  if (which <= GAIBL_W_SELF_GRAD) {
+  if (which <= GAIBL_W_SELF_GRAD || which == GAIBL_FEAT_MASK) {
     if (b->kind == GAIBL_GCN) return common_ptr(b->gcn, which);
     if (b->kind == GAIBL_SAGE) return common_ptr(b->sage, which);
     return common_ptr(b->gat, which);

@@ -23,7 +23,9 @@ enum {
   GAIBL_ALPHA_RGRAD = 9, GAIBL_NORM_SCORES = 10, GAIBL_TEMP_SCORES = 11, GAIBL_SCORES = 12,
   GAIBL_NORM_SCORES_GRAD = 13,
   GAIBL_NORM_SCORES_DROPPED = 14, /* GAT, score_drop > 0: attention . mask . scale of the last training forward */
-  GAIBL_ATTN_MASKS = 15           /* ... and its masks (uint8 [ne][heads], returned through the float* type) */
+  GAIBL_ATTN_MASKS = 15,          /* ... and its masks (uint8 [ne][heads], returned through the float* type) */
+  GAIBL_FEAT_MASK = 16            /* every kind, feat_drop > 0: the feature-dropout mask of the last training forward (uint8
+                                     [num_samples][dim_in], through the float* type); NULL when feat_drop == 0 */
 };
 
 void gaibl_init(int device, void* hip_stream); /* gpu_context::set */

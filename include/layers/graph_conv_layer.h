@@ -33,6 +33,7 @@ class gconv_state {
   float* weight_neigh_grad_ptr() { return d_W_neigh_grad; }
   float* weight_self_ptr() { return d_W_self; }
   float* weight_self_grad_ptr() { return d_W_self_grad; }
+  mask_t* feat_mask_ptr() { return dropout_mask; }  // [num_samples x dim_in], NULL when feat_drop == 0
   int get_dim_in() const { return dim_in; }
   int get_dim_out() const { return dim_out; }
   // ---- extension: a constant input -----------------------------------------------------------------------------
