@@ -21,7 +21,7 @@ INCLUDE = ROOT / "include"
 ORACLE = ROOT / "oracle"
 REFERENCE = Path("/root/reference")
 
-HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "elementwise.hip", "probe.hip", "comm.hip"]
+HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_fp8.hip", "spmm_gemm_fp8.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "elementwise.hip", "probe.hip", "comm.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

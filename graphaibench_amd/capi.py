@@ -90,6 +90,12 @@ SIGNATURES = {
     "gaib_spmm_gemm2_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_spmm_gemm_bf16_ld": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "gaib_spmm_gemm2_bf16_ld": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    "gaib_fp8_row_stride": (_i, [_i, C.POINTER(_i64)]),
+    "gaib_cast_f32_fp8_rows": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "gaib_cast_fp8_f32_rows": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp]),
+    "gaib_spmm_fp8": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _i]),
+    "gaib_spmm_gemm_fp8": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "gaib_spmm_gemm2_fp8": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gaib_graph_split_classes": (_i, [_vp, _vp, _vp, _pp, _pp, _pp, _pp, C.POINTER(_i64), C.POINTER(_i64), _i]),
     "gaib_graph_split_pieces": (_i, [_vp, _vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _pp]),
     "gaib_graph_set_row_map": (_i, [_vp, _vp, _vp, _i64]),
@@ -640,6 +646,91 @@ class Context:
             return out
         _check(self.lib.gaib_spmm_gemm_bf16(self.h, g.h, kind, _ptr(edge_w), len_in, _ptr(x), _ptr(agg), _ptr(W),
                                             1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm_bf16")
+        return out
+
+    # ---- fp8 feature tables with per-row scales (torch.uint8 tensors hold the e4m3 bytes) --------
+    def fp8_row_stride(self, length: int) -> int:
+        """gaib_fp8_row_stride: the row stride (bytes) of an fp8 table of `length` columns"""
+        v = _i64()
+        _check(self.lib.gaib_fp8_row_stride(length, C.byref(v)), "gaib_fp8_row_stride")
+        return v.value
+
+    def cast_f32_fp8_rows(self, x, ld: int | None = None, q=None, scale=None):
+        """gaib_cast_f32_fp8_rows: x fp32 [rows x len] -> (q torch.uint8 [rows x ld], scale fp32 [rows]); ld defaults to
+        fp8_row_stride(len); the bytes behind len are 0"""
+        import torch
+
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+        rows, length = x.shape
+        if ld is None:
+            ld = self.fp8_row_stride(length)
+        if q is None:
+            q = torch.empty((rows, ld), dtype=torch.uint8, device=x.device)
+        if scale is None:
+            scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        assert q.is_contiguous() and q.dtype == torch.uint8 and q.numel() == rows * ld
+        assert scale.is_contiguous() and scale.dtype == torch.float32 and scale.numel() == rows
+        _check(self.lib.gaib_cast_f32_fp8_rows(self.h, rows, length, _ptr(x), ld, _ptr(q), _ptr(scale)), "gaib_cast_f32_fp8_rows")
+        return q, scale
+
+    def cast_fp8_f32_rows(self, q, scale, length: int, out=None):
+        """gaib_cast_fp8_f32_rows: the exact widening of q [rows x ld] (torch.uint8) with its row scales into fp32 [rows x length]"""
+        import torch
+
+        assert q.is_contiguous() and q.dtype == torch.uint8 and q.dim() == 2
+        assert scale.is_contiguous() and scale.dtype == torch.float32 and scale.numel() == q.shape[0]
+        rows, ld = q.shape
+        if out is None:
+            out = torch.empty((rows, length), dtype=torch.float32, device=q.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == rows * length
+        _check(self.lib.gaib_cast_fp8_f32_rows(self.h, rows, length, ld, _ptr(q), _ptr(scale), _ptr(out)), "gaib_cast_fp8_f32_rows")
+        return out
+
+    def spmm_fp8(self, g: "Graph", kind: int, q, scale, out, edge_w=None, accumulate: bool = False, relu: bool = False):
+        """gaib_spmm_fp8: q a [nc x ld] torch.uint8 table whose first out.shape[1] columns are the e4m3 elements, scale its fp32
+        row scales, out fp32 [nv x len].  The bits of spmm on the widened table."""
+        import torch
+
+        assert q.is_contiguous() and out.is_contiguous() and q.dim() == 2 and q.dtype == torch.uint8
+        assert scale.is_contiguous() and scale.dtype == torch.float32 and out.dtype == torch.float32
+        flags = (1 if accumulate else 0) | (2 if relu else 0)
+        _check(self.lib.gaib_spmm_fp8(self.h, g.h, kind, _ptr(edge_w), out.shape[1], q.shape[1], _ptr(q), _ptr(scale), _ptr(out),
+                                      flags), "gaib_spmm_fp8")
+        return out
+
+    def spmm_gemm_fp8(self, g: "Graph", kind: int, q, scale, agg, W, out, transW: bool = False, relu: bool = False,
+                      agg_scratch: bool = False, edge_w=None, accumulate: bool = False, rows2=None, W2=None):
+        """gaib_spmm_gemm_fp8: spmm_gemm with the table as q [nc x ld] torch.uint8 + fp32 row scales; agg, W and out fp32.  The
+        bits of spmm_gemm on the widened table."""
+        import torch
+
+        assert q.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
+        assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.is_contiguous()
+        assert agg.dtype == torch.float32 and out.dtype == torch.float32
+        len_in, len_out = agg.shape[1], out.shape[1]
+        assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))
+        flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0)
+        if rows2 is not None:
+            return self.spmm_gemm2_fp8(g, kind, q, scale, agg, W, rows2, W2, out, transW=transW, relu=relu, agg_scratch=agg_scratch,
+                                       edge_w=edge_w, accumulate=accumulate)
+        _check(self.lib.gaib_spmm_gemm_fp8(self.h, g.h, kind, _ptr(edge_w), len_in, q.shape[1], _ptr(q), _ptr(scale), _ptr(agg), _ptr(W),
+                                           1 if transW else 0, len_out, _ptr(out), flags), "gaib_spmm_gemm_fp8")
+        return out
+
+    def spmm_gemm2_fp8(self, g: "Graph", kind: int, q, scale, agg, W, rows2, W2, out, transW: bool = False, relu: bool = False,
+                       agg_scratch: bool = False, edge_w=None, accumulate: bool = False):
+        """gaib_spmm_gemm2_fp8: + rows2 . op(W2) in the same store"""
+        import torch
+
+        assert q.is_contiguous() and agg.is_contiguous() and W.is_contiguous() and out.is_contiguous()
+        assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.is_contiguous()
+        len_in, len_out = agg.shape[1], out.shape[1]
+        assert tuple(W.shape) == ((len_out, len_in) if transW else (len_in, len_out))
+        assert rows2.is_contiguous() and W2.is_contiguous() and W2.shape == W.shape and rows2.shape[1] == len_in
+        flags = (2 if relu else 0) | (4 if agg_scratch else 0) | (1 if accumulate else 0)
+        _check(self.lib.gaib_spmm_gemm2_fp8(self.h, g.h, kind, _ptr(edge_w), len_in, q.shape[1], _ptr(q), _ptr(scale), _ptr(agg),
+                                            _ptr(W), 1 if transW else 0, _ptr(rows2), _ptr(W2), len_out, _ptr(out), flags),
+               "gaib_spmm_gemm2_fp8")
         return out
 
     # ---- zero-suppressed tables (int32 tensors of [rows x 96] hold the packed rows) -----------

@@ -103,6 +103,7 @@ struct gaib_ctx {
   int agg_zs_wide;           // 1 (with agg_zs): ... and a gradient of 256 columns from its wide image (gaib_pack_zs_wide, the K-slab route)
   int agg_zs_paused;         // written by the layer library's guard: 1 while it gathers dense because too many rows are over capacity
   int agg_bf16;              // 1: the layer library's GCN / SAGE aggregations gather from a bf16 copy of the table (gaib_spmm_bf16, gaib_spmm_gemm_bf16)
+  int agg_fp8;               // 1: ... from an fp8 copy with per-row scales (gaib_cast_f32_fp8_rows, gaib_spmm_fp8, gaib_spmm_gemm_fp8); never together with agg_bf16
   int gemm_bf16;             // 1: the layer library's SAGE self products multiply the bf16 table the aggregation has just cast (gaib_gemm_bf16) where it covers the shape
   int gemm_bf16_kernel;      // 1 (default): gaib_gemm_bf16 runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_gemm_bf16_cover says 0
   int sgemm_variant;         // 0 = auto

@@ -790,6 +790,110 @@ __global__ __launch_bounds__(256) void unpack_zs_wide_kernel(int64_t rows, const
   }
 }
 
+// ---- fp8 tables with per-row scales (include/gaib.h) ----------------------------------------------------------
+// Row r becomes ld bytes of OCP e4m3 "fn" and scale[r] = 2^k: k the smallest integer with amax * 2^-k <= 448 (amax over the
+// row's finite elements), clamped to [-126, 120], 0 for a row without a non-zero finite element.  On the bits of amax = 1.m x
+// 2^(e - 127): 448 = 1.75 x 2^8, so k = e - 127 - 8, one more where 1.m > 1.75; a subnormal amax is far below the lower clamp.
+__device__ __forceinline__ int fp8_row_exponent(unsigned amax_bits) {
+  if (amax_bits == 0u) return 0;
+  const int e = (int)(amax_bits >> 23);
+  if (e == 0) return -126;
+  const int k = e - 135 + ((amax_bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return k < -126 ? -126 : (k > 120 ? 120 : k);
+}
+// four elements times 2^-k (exact) as four e4m3 bytes, round to nearest even (v_cvt_pk_fp8_f32); magnitudes above 448 saturate,
+// a NaN or an infinity becomes the NaN of its sign (0x7f / 0xff: the format has no infinity); columns >= nvalid are pad: byte 0
+__device__ __forceinline__ unsigned fp8_quant4(const float (&v)[4], float inv, int nvalid) {
+  float s[4];
+  unsigned fix_mask = 0u, fix_val = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    s[k] = v[k] * inv;
+    const unsigned b = __float_as_uint(s[k]);
+    if ((b & 0x7fffffffu) >= 0x7f800000u) {
+      fix_mask |= 0xffu << (8 * k);
+      fix_val |= (0x7fu | ((b >> 24) & 0x80u)) << (8 * k);
+      s[k] = 0.f;
+    } else {
+      s[k] = fminf(fmaxf(s[k], -448.f), 448.f);
+    }
+    if (k >= nvalid) {
+      fix_mask |= 0xffu << (8 * k);
+      fix_val &= ~(0xffu << (8 * k));
+      s[k] = 0.f;
+    }
+  }
+  int p = 0;
+  p = __builtin_amdgcn_cvt_pk_fp8_f32(s[0], s[1], p, false);
+  p = __builtin_amdgcn_cvt_pk_fp8_f32(s[2], s[3], p, true);
+  return ((unsigned)p & ~fix_mask) | fix_val;
+}
+// One wave per row, a lane per 4 consecutive columns (one 4-B store; ld % 4 == 0): the row's amax by a wave reduction, then the
+// conversion.  The lane's first four values stay in registers between the two passes (rows up to 256 columns are read once);
+// wider rows read the rest again, from the cache.  VIN: 16-B loads (in 16-B aligned, len % 4 == 0).
+template <bool VIN>
+__global__ __launch_bounds__(256) void cast_f32_fp8_rows_kernel(int64_t rows, int len, int64_t ld, const float* __restrict__ in,
+                                                                uint8_t* __restrict__ q, float* __restrict__ scale) {
+  const int lane = threadIdx.x & 63;
+  const int ngroups = (int)(ld / 4);
+  auto load4 = [&](const float* src, int c, float (&v)[4]) {
+    if (VIN && c + 4 <= len) {
+      const f4 a = *reinterpret_cast<const f4*>(src + c);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = a[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = c + k < len ? src[c + k] : 0.f;
+    }
+  };
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+    const float* src = in + r * len;
+    float v0[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned amax = 0u;
+    for (int gq = lane; gq < ngroups; gq += 64) {
+      float v[4];
+      load4(src, 4 * gq, v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (gq == lane) v0[k] = v[k];
+        const unsigned b = __float_as_uint(v[k]) & 0x7fffffffu;
+        if (b < 0x7f800000u) amax = b > amax ? b : amax;  // (the bit patterns of non-negative floats order as the values do)
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const unsigned t = (unsigned)__shfl_xor((int)amax, o, 64);
+      amax = t > amax ? t : amax;
+    }
+    const int k2 = fp8_row_exponent(amax);
+    const float inv = __uint_as_float((unsigned)(127 - k2) << 23);
+    if (lane == 0) scale[r] = __uint_as_float((unsigned)(127 + k2) << 23);
+    unsigned* dst = reinterpret_cast<unsigned*>(q + r * ld);
+    for (int gq = lane; gq < ngroups; gq += 64) {
+      float v[4];
+      if (gq == lane) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = v0[k];
+      } else {
+        load4(src, 4 * gq, v);
+      }
+      dst[gq] = fp8_quant4(v, inv, len - 4 * gq);
+    }
+  }
+}
+// the exact widening into dense rows: out[r][c] = f32(q[r][c]) * scale[r]
+__global__ __launch_bounds__(256) void cast_fp8_f32_rows_kernel(int64_t n, int len, int64_t ld, const uint8_t* __restrict__ q,
+                                                                const float* __restrict__ scale, float* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t r = i / len;
+    const int64_t c = i - r * len;
+    const unsigned b = q[r * ld + c];
+    // (a NaN byte becomes the quiet NaN of ITS sign: the conversion instruction and the product both hand back one default NaN)
+    out[i] = (b & 0x7fu) == 0x7fu ? __uint_as_float(0x7fc00000u | ((b << 24) & 0x80000000u)) : __builtin_amdgcn_cvt_f32_fp8((int)b, 0) * scale[r];
+  }
+}
+
 }  // namespace
 
 extern "C" int gaib_fill_f32(gaib_ctx* ctx, int64_t n, float value, float* d_x) {
@@ -852,6 +956,38 @@ extern "C" int gaib_cast_bf16_f32(gaib_ctx* ctx, int64_t n, const uint16_t* d_in
   ProfScope ps(ctx, "cast_bf16_f32", 6.0 * (double)n);
   if (vec) cast_bf16_f32_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, ctx->stream>>>(n, d_in, d_out, 1);
   else cast_bf16_f32_scalar_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, d_in, d_out);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+// No host wait and no allocation in either fp8 cast: both are legal inside a stream capture.
+extern "C" int gaib_cast_f32_fp8_rows(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, int64_t ld, uint8_t* d_q, float* d_scale) {
+  GAIB_CHECK(ctx, "gaib_cast_f32_fp8_rows: NULL ctx");
+  GAIB_CHECK(rows >= 0 && len >= 0, "gaib_cast_f32_fp8_rows: rows or len < 0");
+  GAIB_CHECK(ld >= len && ld % 4 == 0, "gaib_cast_f32_fp8_rows: row stride ld (%lld bytes) must be a multiple of 4 not below len (%d)",
+             (long long)ld, len);
+  if (rows == 0) return GAIB_OK;
+  GAIB_CHECK(d_scale && (d_q || ld == 0) && (d_in || len == 0), "gaib_cast_f32_fp8_rows: NULL argument");
+  GAIB_CHECK(((uintptr_t)d_q & 3) == 0, "gaib_cast_f32_fp8_rows: the fp8 table must be 4-byte aligned (16 for the aggregation calls)");
+  GAIB_CHECK((const void*)d_in != (const void*)d_q && (const void*)d_in != (const void*)d_scale, "gaib_cast_f32_fp8_rows: in and out must not alias");
+  ProfScope ps(ctx, "cast_f32_fp8", (double)rows * (4.0 * len + (double)ld + 4.0));
+  const unsigned grid = (unsigned)std::min<int64_t>((rows + 3) / 4, (int64_t)ctx->num_cus * 64);
+  if (len % 4 == 0 && ((uintptr_t)d_in & 15) == 0) cast_f32_fp8_rows_kernel<true><<<grid, 256, 0, ctx->stream>>>(rows, len, ld, d_in, d_q, d_scale);
+  else cast_f32_fp8_rows_kernel<false><<<grid, 256, 0, ctx->stream>>>(rows, len, ld, d_in, d_q, d_scale);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+extern "C" int gaib_cast_fp8_f32_rows(gaib_ctx* ctx, int64_t rows, int len, int64_t ld, const uint8_t* d_q, const float* d_scale,
+                                      float* d_out) {
+  GAIB_CHECK(ctx, "gaib_cast_fp8_f32_rows: NULL ctx");
+  GAIB_CHECK(rows >= 0 && len >= 0 && ld >= len, "gaib_cast_fp8_f32_rows: rows or len < 0, or ld below len");
+  if (rows == 0 || len == 0) return GAIB_OK;
+  GAIB_CHECK(d_q && d_scale && d_out, "gaib_cast_fp8_f32_rows: NULL argument");
+  GAIB_CHECK((const void*)d_q != (const void*)d_out && (const void*)d_scale != (const void*)d_out, "gaib_cast_fp8_f32_rows: in and out must not alias");
+  const int64_t n = rows * len;
+  ProfScope ps(ctx, "cast_fp8_f32", 5.0 * (double)n + 4.0 * (double)rows);
+  cast_fp8_f32_rows_kernel<<<stream_grid(n, 256), 256, 0, ctx->stream>>>(n, len, ld, d_q, d_scale, d_out);
   GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }

@@ -75,6 +75,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->spmm_bf16_pad = 1;
   c->agg_bf16_ld_last = 0;
   c->agg_bf16 = 0;
+  c->agg_fp8 = 0;
   c->gemm_bf16 = 0;
   c->gemm_bf16_kernel = 1;
   c->agg_zs = 1;
@@ -542,6 +543,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "spmm_flat_ring")) *h_value = ctx->spmm_flat_ring;
   else if (!strcmp(key, "num_cus")) *h_value = ctx->num_cus;
   else if (!strcmp(key, "agg_bf16")) *h_value = ctx->agg_bf16;
+  else if (!strcmp(key, "agg_fp8")) *h_value = ctx->agg_fp8;
   else if (!strcmp(key, "gat_bf16")) *h_value = ctx->gat_bf16;
   else if (!strcmp(key, "gat_fused_drop")) *h_value = ctx->gat_fused_drop;
   else if (!strcmp(key, "gat_fused_wide")) *h_value = ctx->gat_fused_wide;
@@ -619,7 +621,12 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
     ctx->agg_bf16_ld_last = (int)value;
   } else if (!strcmp(key, "agg_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
+    GAIB_CHECK(value == 0 || !ctx->agg_fp8, "agg_bf16 = 1 while agg_fp8 is 1: one table format at a time");
     ctx->agg_bf16 = (int)value;
+  } else if (!strcmp(key, "agg_fp8")) {
+    GAIB_CHECK(value == 0 || value == 1, "agg_fp8 must be 0 (fp32 tables) or 1 (fp8 tables with row scales)");
+    GAIB_CHECK(value == 0 || !ctx->agg_bf16, "agg_fp8 = 1 while agg_bf16 is 1: one table format at a time");
+    ctx->agg_fp8 = (int)value;
   } else if (!strcmp(key, "gat_bf16")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_bf16 must be 0 (fp32 tables) or 1 (bf16 tables)");
     ctx->gat_bf16 = (int)value;

@@ -39,6 +39,7 @@ namespace {
 // (HT/4 16-byte loads), parked in the wave's LDS slice with a row stride of HT + 1 floats and picked up per (edge, head)
 // from there: 2 + 2 wave instructions per chunk instead of one 4-byte global load per lane and edge.
 // E = uint16_t: the table holds bf16 bits (a lane's 4 elements are one 8-B load, widened exactly); sums as for fp32.
+// E = fp8_t: e4m3 bytes with row scales (one 4-B load, widened exactly; the scale of an edge's column rides in its weight).
 template <int G, int WMODE, int HT = 0, typename E = float>
 __global__ __launch_bounds__(256) void spmm_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row,
                                                          const uint32_t* chunk_ebase, const uint32_t* chunk_start,
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(256) void spmm_chunk_kernel(int64_t n_chunks, const
   if (lane < n) {
     if constexpr (WMODE == 0) wl = a.rw[row];
     else if constexpr (WMODE == 1 || WMODE == 2) wl = load_edge_w<WMODE>(a, eb + lane);
+    if constexpr (sizeof(E) == 1) wl = fp8_fold_scale<0>(a, cl, wl);
   }
   const bool colok = sl * 4 < a.ncols;
   const int coff = colok ? sl * 4 : 0;
@@ -86,7 +88,9 @@ __global__ __launch_bounds__(256) void spmm_chunk_kernel(int64_t n_chunks, const
     for (int u = 0; u < U; ++u) {
       const int ei = gbase + j + u;  // edge of the chunk this group handles now
       const uint32_t cj = (uint32_t)__shfl((int)cl, ei, 64);
-      if constexpr (sizeof(E) == 2)
+      if constexpr (sizeof(E) == 1)
+        x[u] = load_elems<4, E>(reinterpret_cast<const char*>(a.in) + ((int64_t)cj * a.ld + coff));
+      else if constexpr (sizeof(E) == 2)
         x[u] = load_elems<4, E>(reinterpret_cast<const char*>(a.in) + ((int64_t)cj * a.ld + coff) * 2);
       else
         x[u] = *reinterpret_cast<const f32x4_t*>(a.in + (int64_t)cj * a.ld + coff);
@@ -159,7 +163,7 @@ int launch_chunked(gaib_ctx* ctx, gaib_graph* g, const SpmmArgs& a) {
   {
     // col + gathered row + the edge's weights; a partial row per chunk written (and read again by the reduction)
     const double wb = WMODE == 0 ? 0.0 : (WMODE >= 3 ? 4.0 * a.heads : 4.0);
-    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_chunk" : "spmm_chunk",
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_chunk" : (sizeof(E) == 1 ? "spmm_fp8_chunk" : "spmm_chunk"),
                  (double)g->ne * ((double)sizeof(E) * a.ncols + 4.0 + wb) + (double)g->n_chunks * 4.0 * a.ncols,
                  2.0 * (double)g->ne * a.ncols);
 #define GAIB_CHUNK(GG) \
@@ -247,15 +251,15 @@ extern "C" int gaib_bf16_row_stride(gaib_ctx* ctx, gaib_graph* g, int len, int64
 }
 
 // size of a table of `rows` rows of `ld` elements as the buffer-descriptor path sees it: 0 where it reaches 4 GB (64-bit addresses then)
-static uint32_t buf_bytes(int64_t rows, int64_t ld, bool bf16) {
-  const int64_t b = rows * ld * (bf16 ? 2 : 4);
+static uint32_t buf_bytes(int64_t rows, int64_t ld, bool bf16, bool fp8 = false) {
+  const int64_t b = rows * ld * (fp8 ? 1 : (bf16 ? 2 : 4));
   return b < ((int64_t)1 << 32) ? (uint32_t)b : 0u;
 }
 
 // row stride (elements) the gather reads the table at: a bf16 table's own (ld_bf16 > 0: the caller cast it that way), an fp32
 // table's re-strided copy where pad_stride_floats makes one
 static int64_t gather_ld(const gaib_ctx* ctx, const gaib_graph* g, int len, bool part, bool bf16, int64_t ld_bf16) {
-  if (bf16) return ld_bf16 > 0 ? ld_bf16 : len;
+  if (bf16) return ld_bf16 > 0 ? ld_bf16 : len;  // (and an fp8 table's: callers pass bf16 || fp8)
   const int64_t lp = pad_stride_floats(ctx, g, len, part);
   return lp > 0 ? lp : len;
 }
@@ -266,9 +270,11 @@ static int64_t gather_ld(const gaib_ctx* ctx, const gaib_graph* g, int len, bool
 // cold-column flags), and the buffer-descriptor path is chosen by the tables' bf16 byte sizes
 // ld_bf16 > 0: the row stride of a bf16 table in elements (gaib_spmm_bf16_ld; the caller cast it that way: gaib_cast_f32_bf16_rows)
 // -- it enters the gather addresses, the descriptor size and the 4 GB test, nothing else
+// fp8: d_in holds e4m3 bytes at the row stride ld_bf16 (bytes; gaib_spmm_fp8): gathered as they are like a bf16 table, but WITH the
+// cold-column flags of gather mode 3 (the row kernels' scale fetch masks them); the caller points a.in2 at the row scales
 static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len,
                       const float* d_in, float* d_out, int flags, int heads, SpmmArgs* pa, int* wmode,
-                      const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false, int64_t ld_bf16 = 0) {
+                      const float* d_in2 = nullptr, int64_t n_first = 0, bool bf16 = false, int64_t ld_bf16 = 0, bool fp8 = false) {
   SpmmArgs& a = *pa;
   const bool part = g->row_map != nullptr || d_in2 != nullptr;  // a row class of a partition (spmm_part.hip)
   GAIB_CHECK(!d_in2 || (n_first >= 0 && n_first <= g->nc), "gaib_spmm: n_first (%lld) outside the %lld columns",
@@ -312,7 +318,7 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
   a.ldo = len;
   // odd-width tables: gathered from a copy re-strided to whole 64-B pieces where that saves lines (pad_stride_floats)
   {
-    const int64_t lp_pad = bf16 ? 0 : pad_stride_floats(ctx, g, len, part);
+    const int64_t lp_pad = bf16 || fp8 ? 0 : pad_stride_floats(ctx, g, len, part);
     if (lp_pad > 0) {
       const int lp = (int)lp_pad;
       GAIB_TRY(gaib_pad_reserve(ctx, (size_t)g->nc * (size_t)lp * 4));
@@ -324,9 +330,9 @@ static int spmm_setup(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float
       a.ld = lp;
     }
   }
-  if (bf16 && ld_bf16 > 0) a.ld = ld_bf16;
-  // feature table = nc rows of a.ld elements (4 B, or 2 B in bf16); the 32-bit buffer path needs it below 4 GB
-  a.in_bytes = buf_bytes(d_in2 ? n_first : g->nc, a.ld, bf16);
+  if ((bf16 || fp8) && ld_bf16 > 0) a.ld = ld_bf16;
+  // feature table = nc rows of a.ld elements (4 B, 2 B in bf16, 1 B in fp8); the 32-bit buffer path needs it below 4 GB
+  a.in_bytes = buf_bytes(d_in2 ? n_first : g->nc, a.ld, bf16, fp8);
   if (d_in2) a.in2_bytes = buf_bytes(g->nc - n_first, a.ld, bf16);
   switch (weight_kind) {
     case GAIB_W_GCN:
@@ -456,6 +462,8 @@ struct GemmCall {
   int64_t n_first = 0, ld = 0;   // ld: a bf16 table's rows are this many elements apart (0: len_in)
   bool bf16 = false;             // d_in (and d_in2) hold bf16 bits
   const void* d_zs = nullptr;  // the zero-suppressed image of d_in (gaib_pack_zs, or gaib_pack_zs_wide at 256 columns)
+  bool fp8 = false;                // d_in holds e4m3 bytes at the row stride ld (bytes), d_scale the row scales (gaib_spmm_gemm_fp8)
+  const float* d_scale = nullptr;
 };
 
 // the routes (the table stands at gemm_route): nothing to do | one fused launch | the neighbour product fused, then the accumulating
@@ -539,16 +547,16 @@ static FuseForm fuse_form(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, bool 
   fm.dual = dual;
   fm.yacc = false;
   // the table(s) as the gather addresses them -- a bf16 table counts its own bytes here, the one place its real size decides
-  const int64_t ld = gather_ld(ctx, g, c.len_in, part, c.bf16, c.ld);
-  fm.buf = ctx->spmm_addr_mode != 2 && buf_bytes(c.d_in2 ? c.n_first : g->nc, ld, c.bf16) != 0 &&
+  const int64_t ld = gather_ld(ctx, g, c.len_in, part, c.bf16 || c.fp8, c.ld);
+  fm.buf = ctx->spmm_addr_mode != 2 && buf_bytes(c.d_in2 ? c.n_first : g->nc, ld, c.bf16, c.fp8) != 0 &&
            (!c.d_in2 || buf_bytes(g->nc - c.n_first, ld, c.bf16) != 0);
   fm.short_rows = edge_stream_rule(ctx, g);
   fm.flat = fm.short_rows && !dual && strip == 8;
   fm.ring = fm.flat && ctx->spmm_flat_ring != 0;
   const int tile_xcd = tile_xcd_arg(ctx, g);  // (asked whatever the table kind: the locality is measured on a graph's first fused call)
-  fm.tile_xcd = part || c.bf16 ? 0 : tile_xcd;
+  fm.tile_xcd = part || c.bf16 || c.fp8 ? 0 : tile_xcd;
   // (hot_cold: the launch has the form; run_fused asks hot_cold_cols whether the option is on and the flags exist)
-  fm.hot_cold = !kslabs && !part && !c.bf16 && fm.vec == 2 && fm.buf && !dual && strip == 8 && !fm.flat && fm.tile_xcd == 0;
+  fm.hot_cold = !kslabs && !part && !c.bf16 && !c.fp8 && fm.vec == 2 && fm.buf && !dual && strip == 8 && !fm.flat && fm.tile_xcd == 0;
   return fm;
 }
 
@@ -568,10 +576,11 @@ static FuseForm fuse_form(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, bool 
 //   everything else (odd above 64, > 256, unaligned)                                                      UNFUSED
 //   ... and where a row class of a partition would go UNFUSED: REFUSED (the classes' rows share one output)
 // "fp32 view": a bf16 table stands for its widened fp32 table -- at twice the address, the chunk rule counting fp32 bytes -- so
-// both take the same route, and each route runs the bf16 gather.  The form next to the route (fuse_form):
+// both take the same route, and each route runs the bf16 gather; an fp8 table (c.fp8) likewise, at four times the address.  The
+// form next to the route (fuse_form):
 //   edge stream  short rows (edge_stream_rule) on the one-product 8-row strip, never on a later K-slab; a ring with spmm_flat_ring
 //   addressing   buffer descriptors while every table is below 4 GB and spmm_addr_mode != 2, else 64-bit
-//   tile supply  spmm_tile_xcd (XCD-affine chunks; auto: a numbering with locality); global counter on classes and bf16 tables
+//   tile supply  spmm_tile_xcd (XCD-affine chunks; auto: a numbering with locality); global counter on classes, bf16 and fp8 tables
 //   hot/cold     spmm_hot_cold (hot_cold_cols) on 8-B lanes, 8-row strip, one product, row form, buffer addressing, global
 //                counter, an fp32 or zero-suppressed table of a whole graph
 // A zero-suppressed image (d_zs) has a packed gather only on FUSED at 128 columns (two products, or the 8-row strip) and on KSLABS
@@ -593,7 +602,7 @@ static int gemm_route(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, GemmRoute
   const bool dual = c.d_rows2 != nullptr;
   const bool part = g->row_map != nullptr || c.d_in2 != nullptr;  // a row class of a partition
   const uintptr_t tables = (uintptr_t)c.d_in | (uintptr_t)c.d_in2;
-  const uintptr_t al = (c.bf16 ? tables << 1 : tables) | (uintptr_t)c.d_agg;  // the fp32 view's alignment
+  const uintptr_t al = (c.fp8 ? tables << 2 : (c.bf16 ? tables << 1 : tables)) | (uintptr_t)c.d_agg;  // the fp32 view's alignment
   // dense graphs over a cache-sized table aggregate faster by ordered chunks (spmm_chunk_kernel) than row by row
   // inside the fused kernel: two kernels there
   const bool dense = !part && ctx->spmm_chunked != 0 && len_in % 4 == 0 && (al & 15) == 0 &&
@@ -673,7 +682,8 @@ static int fuse_args(gaib_ctx* ctx, const gaib_graph* g, const GemmCall& c, bool
 
 // the aggregation arguments of a fused call: no agg store where the caller does not read it, partial sums through FuseArgs::agg_in
 static int fuse_spmm_args(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, SpmmArgs* a, int* wmode) {
-  GAIB_TRY(spmm_setup(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.d_in, c.d_agg, 0, 1, a, wmode, c.d_in2, c.n_first, c.bf16, c.ld));
+  GAIB_TRY(spmm_setup(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.d_in, c.d_agg, 0, 1, a, wmode, c.d_in2, c.n_first, c.bf16, c.ld, c.fp8));
+  if (c.fp8) a->in2 = c.d_scale;
   a->accumulate = 0;
   a->col_flagged = nullptr;
   if (c.flags & GAIB_AGG_SCRATCH) a->out = nullptr;
@@ -694,6 +704,7 @@ static int launch_form(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, const Fu
   if (g->row_map || c.d_in2)
     return c.bf16 ? gaib_spmm_part_fused_bf16(ctx, g, fm, a, f, hv, wmode) : gaib_spmm_part_fused(ctx, g, fm, a, f, hv, wmode);
   if (c.bf16) return gaib_spmm_fused_bf16(ctx, g, fm, a, f, hv, wmode);
+  if (c.fp8) return gaib_spmm_fused_fp8(ctx, g, fm, a, f, hv, wmode);
   if (fm.vec == 1) return wmode == 0 ? launch_fused<1, 0>(ctx, g, fm, a, f, hv) : launch_fused<1, 1>(ctx, g, fm, a, f, hv);
   return wmode == 0 ? launch_fused<2, 0>(ctx, g, fm, a, f, hv) : launch_fused<2, 1>(ctx, g, fm, a, f, hv);
 }
@@ -731,10 +742,12 @@ static int run_kslabs(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, const Fus
   for (int k0 = 0; k0 < c.len_in; k0 += 128) {
     SpmmArgs a = a0;
     // (bf16: the slab offset and in_bytes count bf16 elements; the offset is one of columns, whatever the row stride)
-    a.in = c.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0) : a0.in + k0;
+    a.in = c.fp8    ? reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(a0.in) + k0)
+           : c.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a0.in) + k0)
+                    : a0.in + k0;
     a.ncols = c.len_in - k0 < 128 ? c.len_in - k0 : 128;
     if (a.out) a.out += k0;
-    if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * (c.bf16 ? 2 : 4));
+    if (a.in_bytes) a.in_bytes -= (uint32_t)(k0 * (c.fp8 ? 1 : (c.bf16 ? 2 : 4)));
     FuseArgs f = f0;
     f.wt += k0;
     if (f.agg_in) f.agg_in += k0;
@@ -750,7 +763,9 @@ static int run_kslabs(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c, const Fus
 
 static int run_unfused(gaib_ctx* ctx, gaib_graph* g, const GemmCall& c) {
   const bool dual = c.d_rows2 != nullptr;
-  if (c.bf16) GAIB_TRY(gaib_spmm_bf16_ld(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.ld > 0 ? c.ld : c.len_in,
+  if (c.fp8) GAIB_TRY(gaib_spmm_fp8(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.ld, reinterpret_cast<const uint8_t*>(c.d_in),
+                                    c.d_scale, c.d_agg, c.flags & GAIB_ACCUMULATE));
+  else if (c.bf16) GAIB_TRY(gaib_spmm_bf16_ld(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.ld > 0 ? c.ld : c.len_in,
                                          reinterpret_cast<const uint16_t*>(c.d_in), c.d_agg, c.flags & GAIB_ACCUMULATE));
   else GAIB_TRY(spmm_impl(ctx, g, c.weight_kind, c.d_edge_w, c.len_in, c.d_in, c.d_agg, c.flags & GAIB_ACCUMULATE));
   if (!dual) return trailing_gemm(ctx, g, c, c.d_agg, c.d_W, 0);
@@ -1054,4 +1069,105 @@ extern "C" int gaib_spmm_gemm_part_bf16(gaib_ctx* ctx, gaib_graph* g, int weight
   c.n_first = n_first;
   c.bf16 = true;
   return spmm_gemm_run(ctx, g, c);
+}
+
+// ---- fp8 feature tables with per-row scales (the kernels: spmm_fp8.hip, spmm_gemm_fp8.hip) ------------------------
+// The table is e4m3 "fn" bytes [nc x ld] (ld = the row stride in bytes) with a power-of-two scale per row; row r stands for
+// f32(q[r][:]) * scale[r], both steps exact.  The kernels are the fp32 ones with an fp8 gather (RowGather<.., E = fp8_t>) and the
+// scale of an edge's column folded into its weight (spmm_core.h): the same CSR order with separate multiply and add, the same
+// heavy threshold and 16-wave LDS combine, the same choice of the ordered-chunk form -- made on what the fp32 call would see --,
+// so the result is bit-identical to gaib_spmm_ex / gaib_spmm_gemm(2) on the widened table while w_e * scale and the products
+// stay normal numbers.
+extern "C" int gaib_fp8_row_stride(int len, int64_t* ld) {
+  GAIB_CHECK(ld, "gaib_fp8_row_stride: NULL argument");
+  GAIB_CHECK(len >= 0, "gaib_fp8_row_stride: len < 0");
+  if (len % 128 == 0) *ld = len;
+  else if (len <= 128) {
+    int64_t p = 4;
+    while (p < len) p <<= 1;
+    *ld = p;
+  } else *ld = ((int64_t)len + 127) / 128 * 128;
+  return GAIB_OK;
+}
+
+// what every fp8 aggregation call checks before it touches anything; GAIB_ERR_UNSUPPORTED for what the fp8 gather does not have
+static int fp8_table_check(const char* who, const gaib_graph* g, int len, int64_t ld, const uint8_t* d_q) {
+  GAIB_CHECK(len >= 0, "%s: len < 0", who);
+  GAIB_CHECK(ld >= len && ld % 4 == 0, "%s: row stride ld (%lld bytes) must be a multiple of 4 not below len (%d): gaib_fp8_row_stride",
+             who, (long long)ld, len);
+  if (g->row_map) {
+    gaib_set_error("%s: a row class of a partition (graph with a row map) is not supported: fp32 or bf16 tables only", who);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (g->nc * ld >= ((int64_t)1 << 32)) {
+    gaib_set_error("%s: an fp8 table of 4 GB or more (%lld rows of %lld bytes) is not supported: buffer addressing only", who,
+                   (long long)g->nc, (long long)ld);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  if (((uintptr_t)d_q & 15) != 0) {
+    gaib_set_error("%s: the fp8 table must start on a 16-byte boundary", who);
+    return GAIB_ERR_UNSUPPORTED;
+  }
+  return GAIB_OK;
+}
+
+extern "C" int gaib_spmm_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, int64_t ld,
+                             const uint8_t* d_q, const float* d_scale, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_fp8: NULL ctx/graph");
+  GAIB_CHECK((flags & ~(GAIB_ACCUMULATE | GAIB_RELU)) == 0, "gaib_spmm_fp8: unsupported flags %d", flags);
+  GAIB_CHECK(ctx->device == g->device, "gaib_spmm_fp8: graph lives on device %d, ctx on %d", g->device, ctx->device);
+  GAIB_TRY(fp8_table_check("gaib_spmm_fp8", g, len, ld, d_q));
+  if (len == 0 || g->nv == 0) return GAIB_OK;
+  GAIB_CHECK(d_q && d_scale && d_out, "gaib_spmm_fp8: NULL table, scale or output pointer");
+  GAIB_CHECK((const void*)d_q != (const void*)d_out && (const void*)d_scale != (const void*)d_out, "gaib_spmm_fp8: in and out must not alias");
+  SpmmArgs a;
+  int wmode = 0;
+  GAIB_TRY(spmm_setup(ctx, g, weight_kind, d_edge_w, len, reinterpret_cast<const float*>(d_q), d_out, flags, 1, &a, &wmode, nullptr, 0,
+                      false, ld, true));
+  a.in2 = d_scale;
+  // the fp32 path's choice of the ordered-chunk form, made on what IT would see (as gaib_spmm_bf16_ld): the widened table is
+  // 16-B aligned wherever this one is 4-B aligned
+  const int64_t ld32 = pad_stride_floats(ctx, g, len, false) > 0 ? pad_stride_floats(ctx, g, len, false) : len;
+  const bool chunk_shape = len % 4 == 0 && len <= 256 && g->ne > 0 && (((uintptr_t)d_out & 15) == 0);
+  if (chunk_shape && (ctx->spmm_chunked == 1 || (ctx->spmm_chunked < 0 && chunk_rule(ctx, g, ld32)))) {
+    switch (wmode) {
+      case 0: return launch_chunked<0, fp8_t>(ctx, g, a);
+      case 1: return launch_chunked<1, fp8_t>(ctx, g, a);
+      default: return launch_chunked<2, fp8_t>(ctx, g, a);
+    }
+  }
+  return gaib_spmm_plain_fp8(ctx, g, a, wmode, len);
+}
+
+// agg = A.widen(q, scale) ; out = act(agg . op(W) [+ rows2 . op(W2)]): the route gaib_spmm_gemm(2) takes on the widened table
+// (gemm_route: every test on the fp32 sizes), run with the fp8 gather.
+static int spmm_gemm_fp8_entry(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                               const uint8_t* d_q, const float* d_scale, float* d_agg, const float* d_W, int transW,
+                               const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(ctx && g, "gaib_spmm_gemm_fp8: NULL ctx/graph");
+  GAIB_CHECK(!(flags & GAIB_OVERLAPS_TRANSFER), "gaib_spmm_gemm_fp8: GAIB_OVERLAPS_TRANSFER belongs to partitioned runs, which "
+                                                "aggregate fp32 or bf16 tables");
+  GAIB_TRY(fp8_table_check("gaib_spmm_gemm_fp8", g, len_in, ld, d_q));
+  GAIB_CHECK(g->nv == 0 || len_out == 0 || d_scale, "gaib_spmm_gemm_fp8: NULL scale pointer");
+  GAIB_CHECK((const void*)d_scale != (const void*)d_agg && (const void*)d_scale != (const void*)d_out, "gaib_spmm_gemm_fp8: buffers must not alias");
+  GemmCall c{weight_kind, d_edge_w, len_in, reinterpret_cast<const float*>(d_q), d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out, flags};
+  c.fp8 = true;
+  c.ld = ld;
+  c.d_scale = d_scale;
+  return spmm_gemm_run(ctx, g, c);
+}
+
+extern "C" int gaib_spmm_gemm_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                                  const uint8_t* d_q, const float* d_scale, float* d_agg, const float* d_W, int transW, int len_out,
+                                  float* d_out, int flags) {
+  return spmm_gemm_fp8_entry(ctx, g, weight_kind, d_edge_w, len_in, ld, d_q, d_scale, d_agg, d_W, transW, nullptr, nullptr, len_out,
+                             d_out, flags);
+}
+
+extern "C" int gaib_spmm_gemm2_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                                   const uint8_t* d_q, const float* d_scale, float* d_agg, const float* d_W, int transW,
+                                   const float* d_rows2, const float* d_W2, int len_out, float* d_out, int flags) {
+  GAIB_CHECK(d_rows2 && d_W2, "gaib_spmm_gemm2_fp8: NULL second operand");
+  return spmm_gemm_fp8_entry(ctx, g, weight_kind, d_edge_w, len_in, ld, d_q, d_scale, d_agg, d_W, transW, d_rows2, d_W2, len_out, d_out,
+                             flags);
 }

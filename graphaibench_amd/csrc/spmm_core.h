@@ -1,4 +1,5 @@
-// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_part.hip, spmm_part_bf16.hip, spmm_gemm_bf16.hip):
+// spmm_core.h -- device code shared by the aggregation kernels (spmm.hip, spmm_part.hip, spmm_part_bf16.hip, spmm_gemm_bf16.hip, spmm_fp8.hip,
+// spmm_gemm_fp8.hip):
 // launch arguments, the feature-row gather and the per-wave edge loop.
 #pragma once
 #include <type_traits>
@@ -38,6 +39,7 @@ struct SpmmArgs {
   const float* in2;          // column ids >= n_first index this second table (row id - n_first): the halo table behind the
   uint32_t n_first;          //   rank's own rows.  in2 == NULL: one table, n_first = 0xffffffff
   uint32_t in2_bytes;        // BUF kernels: size of the second table (< 4 GB; of its bf16 bits when the tables are bf16)
+  // fp8 tables (E = fp8_t; never PART): in2 points at the table's row scales, float[nc] (see fp8_scales)
 };
 
 namespace {
@@ -144,10 +146,59 @@ __device__ __forceinline__ typename VecT<VEC>::type widen_bf16(typename Bf16Raw<
   }
   return v;
 }
+// fp8 tables (E = fp8_t: OCP e4m3 "fn" bytes): VEC elements arrive in VEC bytes and are widened exactly by
+// v_cvt_pk_f32_fp8 / v_cvt_f32_fp8.  A row r of the table stands for f32(q[r][:]) * scale[r] with scale[r] a power of two: the
+// scale never touches the VEC x CT gathered elements -- it is folded into the edge's weight, w_e * scale[col_e] (an exact
+// product while it stays a normal number, and one that commutes with the rounding of w * x), fetched per lane next to the
+// column id and weight of a 64-edge chunk and consumed through the same readlane.  Everything after the gather is the fp32
+// kernels' own, as for bf16.
+struct fp8_t { uint8_t bits; };
+template <int VEC> struct Fp8Raw;  // the packed bytes of VEC fp8 elements
+template <> struct Fp8Raw<1> { typedef unsigned char type; };
+template <> struct Fp8Raw<2> { typedef unsigned short type; };
+template <> struct Fp8Raw<4> { typedef unsigned type; };
+template <> struct Fp8Raw<8> { typedef u2_t type; };
+template <int VEC>
+__device__ __forceinline__ typename VecT<VEC>::type widen_fp8(typename Fp8Raw<VEC>::type r) {
+  typename VecT<VEC>::type v;
+  if constexpr (VEC == 1) v = __builtin_amdgcn_cvt_f32_fp8((int)(unsigned)r, 0);
+  else if constexpr (VEC == 2) v = __builtin_amdgcn_cvt_pk_f32_fp8((int)(unsigned)r, false);
+  else {
+#pragma unroll
+    for (int i = 0; i < VEC / 4; ++i) {
+      unsigned w;
+      if constexpr (VEC == 4) w = r;
+      else w = r[i];
+      const typename VecT<2>::type lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+      v[4 * i] = lo[0];
+      v[4 * i + 1] = lo[1];
+      v[4 * i + 2] = hi[0];
+      v[4 * i + 3] = hi[1];
+    }
+  }
+  return v;
+}
+// the row scales of an fp8 table (SpmmArgs::in2) and the weight lane l of a 64-edge chunk holds for its edge: w_e * scale[col_e]
+// (WMODE 0 at a fixed row: roww * scale[col_e]).  c is the lane's column id as loaded -- under gather mode 3 its top bit is the
+// hot/cold flag and is masked before it indexes the scales.
+__device__ __forceinline__ const float* fp8_scales(const SpmmArgs& a) { return a.in2; }
+template <int GM>
+__device__ __forceinline__ float fp8_fold_scale(const SpmmArgs& a, uint32_t c, float w) {
+  return w * fp8_scales(a)[GM == 3 ? (c & 0x7fffffffu) : c];
+}
+// the weight of edge idx of a 64-edge chunk in the edge-stream forms, where the row (and its weight roww) changes along the
+// stream: an fp8 table's lanes hold w_e * scale[col_e], under WMODE 0 the scale alone -- roww * scale[col_e], one exact product
+// per edge, never one per gathered element
+template <int WMODE, bool F8>
+__device__ __forceinline__ float stream_w(float roww, float w, int idx) {
+  if constexpr (F8 && WMODE == 0) return roww * readlane_f(w, idx);
+  else return (WMODE == 0) ? roww : readlane_f(w, idx);
+}
 // VEC elements of type E at p (global address) as VEC floats
 template <int VEC, typename E>
 __device__ __forceinline__ typename VecT<VEC>::type load_elems(const char* p) {
   if constexpr (sizeof(E) == 4) return *reinterpret_cast<const typename VecT<VEC>::type*>(p);
+  else if constexpr (sizeof(E) == 1) return widen_fp8<VEC>(*reinterpret_cast<const typename Fp8Raw<VEC>::type*>(p));
   else return widen_bf16<VEC>(*reinterpret_cast<const typename Bf16Raw<VEC>::type*>(p));
 }
 
@@ -211,11 +262,16 @@ struct RowGather {
   // (half the registers).  load_raw() requests, widen() -- exact, bits << 16 -- belongs at the point of use: widened at the load,
   // the shifts sit between the loads of a batch and every gather in flight holds fp32-sized registers.
   // A zero-suppressed gather is held as the two dwords the lane asked for (lanes 0 .. 47 cover the 384-B row).
+  // An fp8 gather is held as the VEC bytes it arrived in (a quarter of the registers) and widened by v_cvt_pk_f32_fp8 at the same point.
+  static constexpr bool F8 = sizeof(E) == 1;
+  static_assert(!PART || !F8, "two-table gathers: fp32 or bf16 tables");
+  typedef typename std::conditional<F8, typename Fp8Raw<VEC>::type, typename VecT<VEC>::type>::type wide_raw_t;
   typedef typename std::conditional<ZS, u2_t, typename std::conditional<sizeof(E) == 2, typename Bf16Raw<VEC>::type,
-                                                                           typename VecT<VEC>::type>::type>::type raw_t;
+                                                                           wide_raw_t>::type>::type raw_t;
   static __device__ __forceinline__ typename VecT<VEC>::type widen(const raw_t& r) {
     static_assert(!ZS, "zero-suppressed tables are expanded by zs_issue / zs_select");
     if constexpr (sizeof(E) == 2) return widen_bf16<VEC>(r);
+    else if constexpr (F8) return widen_fp8<VEC>(r);
     else return r;
   }
   // Expansion of a zero-suppressed row where it is consumed.  Control flow is wave-uniform here and every lane is live: the masks
@@ -306,7 +362,7 @@ struct RowGather {
       return load_buf<0>(cj, voff);
     } else {
       const char* rowp = inb + (int64_t)cj * ldb;  // scalar base
-      if constexpr (sizeof(E) == 2) return *reinterpret_cast<const raw_t*>(rowp + voff);
+      if constexpr (sizeof(E) == 2 || F8) return *reinterpret_cast<const raw_t*>(rowp + voff);
       else return *reinterpret_cast<const vec_t*>(rowp + voff);
     }
   }
@@ -322,6 +378,11 @@ struct RowGather {
       else if constexpr (VEC == 2) return __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX);
       else if constexpr (VEC == 4) return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX);
       else return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, soff, AUX);
+    } else if constexpr (F8) {  // fp8: a quarter of the bytes (b8 / b16 / b32 / b64 for 1 / 2 / 4 / 8 elements)
+      if constexpr (VEC == 1) return __builtin_amdgcn_raw_buffer_load_b8(rsrc, (int)voff, soff, AUX);
+      else if constexpr (VEC == 2) return __builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)voff, soff, AUX);
+      else if constexpr (VEC == 4) return __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX);
+      else return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, soff, AUX);
     } else if constexpr (VEC == 1) {
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, soff, AUX));
     } else if constexpr (VEC == 2) {
@@ -402,6 +463,11 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
   const gather_t gather(a);
   typename gather_t::raw_t x[U][CT];  // gather destinations (bf16: packed words, widened where consumed); the tail's piece p lives in x[p .. 2p-1]
   constexpr bool MH = WMODE >= 3;  // multi-head: every lane fetches the weight of ITS head itself
+  // fp8 tables: lane l's weight is w_e * scale[col_e] in every single-head mode (WMODE 0: roww * scale[col_e], so that mode
+  // reads its weight through the readlane too)
+  constexpr bool F8 = gather_t::F8;
+  static_assert(!F8 || !PRE, "fp8 tables: the caller's prefetched weights do not carry the scales");
+  constexpr bool LANE_W = WMODE != 0 || F8;  // the edge's weight comes from lane j of w (else: roww)
   int hd[CT];
   float wv[MH ? U : 1][CT];
 #pragma unroll
@@ -422,6 +488,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
     } else if (lane < n) {
       c = a.col[base + lane];
       if constexpr (WMODE == 1 || WMODE == 2) w = load_edge_w<WMODE>(a, base + lane);
+      if constexpr (F8) w = fp8_fold_scale<BUF>(a, c, WMODE == 0 ? roww : w);
     }
     int j = 0;
     // full batches: U independent row gathers in flight, straight-line code
@@ -445,7 +512,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
       } else {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, j + u));
+          const float wj = !LANE_W ? roww : (MH ? 0.f : readlane_f(w, j + u));
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
             float wsel = wj;
@@ -489,7 +556,7 @@ __device__ __forceinline__ void wave_accumulate(const SpmmArgs& a, int lane, int
           } else {
 #pragma unroll
             for (int u = 0; u < p; ++u) {
-              const float wj = (WMODE == 0) ? roww : (MH ? 0.f : readlane_f(w, jj + u));
+              const float wj = !LANE_W ? roww : (MH ? 0.f : readlane_f(w, jj + u));
 #pragma unroll
               for (int ct = 0; ct < CT; ++ct) {
                 // (the tail is short: its per-head weights are fetched at the point of use)

@@ -1,5 +1,7 @@
 // spmm_kernels.h -- the aggregation kernels and their launchers, shared by spmm.hip (whole graphs), spmm_part.hip (the
-// row classes of a vertex-range partition) and spmm_part_bf16.hip (the same over bf16 tables).  Every kernel takes a compile-time PART flag:
+// row classes of a vertex-range partition), spmm_part_bf16.hip (the same over bf16 tables), spmm_gemm_bf16.hip / spmm_gemm_zs.hip
+// (the fused kernels over bf16 / zero-suppressed tables) and spmm_fp8.hip / spmm_gemm_fp8.hip (the row and the fused kernels over
+// fp8 tables with row scales, whole graphs only).  Every kernel takes a compile-time PART flag:
 //   PART = false  the graph's row r is row r of the caller's matrices, one feature table (spmm.hip)
 //   PART = true   the graph is a COMPACT subset of a rank's rows (gaib_graph_split_classes): row r stands for row
 //                 row_map[r] of out / agg / rows2 / y, and column ids >= n_first index a second table (the halo table
@@ -11,7 +13,7 @@
 namespace {
 
 // ---- light rows, one wave per row ------------------------------------------------------
-// E: element type of the gathered table (float, or uint16_t = bf16 bits; see RowGather)
+// E: element type of the gathered table (float, uint16_t = bf16 bits, or fp8_t = e4m3 bytes with row scales; see RowGather)
 template <int VEC, int CT, int WMODE, int U, int BUF, bool PART = false, typename E = float>
 __global__ __launch_bounds__(256) void spmm_w64_kernel(SpmmArgs a) {
   typedef typename VecT<VEC>::type vec_t;
@@ -142,7 +144,7 @@ int launch_w64_u(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
     h.row_list = g->heavy_rows;
     h.row_order = g->heavy_rows + g->n_heavy;
     size_t lds = sizeof(float) * HEAVY_WAVES * CT * 64 * VEC;
-    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_heavy" : "spmm_heavy",
+    ProfScope ps(ctx, sizeof(E) == 2 ? "spmm_bf16_heavy" : (sizeof(E) == 1 ? "spmm_fp8_heavy" : "spmm_heavy"),
                  gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, EB),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
     // (a 1024-thread workgroup leaves a wave 128 VGPRs: the multi-head edge-weight modes -- a weight per head and edge next to
@@ -166,6 +168,7 @@ int launch_w64_u(gaib_ctx* ctx, const gaib_graph* g, SpmmArgs a) {
     // (row classes of a partition are timed under keys of their own: interior / owned-column pass, halo-column pass, one pass)
     const double e_l = (double)g->ne - (g->n_heavy > 0 ? (double)g->heavy_edges : 0.0), r_l = (double)a.n_rows - (double)g->n_heavy;
     ProfScope ps(ctx, sizeof(E) == 2 ? (!PART ? "spmm_bf16_light" : (a.in2 ? "part_bf16_light_2t" : (a.accumulate ? "part_bf16_light_acc" : "part_bf16_light")))
+                      : sizeof(E) == 1 ? "spmm_fp8_light"
                                      : (!PART ? "spmm_light" : (a.in2 ? "part_light_2t" : (a.accumulate ? "part_light_acc" : "part_light"))),
                  gaib_alg_spmm_bytes(e_l, r_l, a.ncols, WMODE == 0 ? 0 : 4, a.accumulate ? 2 : 1, EB), 2.0 * e_l * a.ncols, a.ncols);
     spmm_w64_kernel<VEC, CT, WMODE, U, BUF, PART, E><<<dim3(grid), 256, 0, ctx->stream>>>(a);
@@ -376,6 +379,9 @@ int gaib_spmm_part_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm
 int gaib_spmm_fused_bf16(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
 int gaib_spmm_fused_zs(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
 int gaib_spmm_kslab_zs(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
+// ... and the row kernels and the fused kernels over an fp8 table with row scales (spmm_fp8.hip, spmm_gemm_fp8.hip; a.in2 = the scales)
+int gaib_spmm_plain_fp8(gaib_ctx* ctx, const gaib_graph* g, const SpmmArgs& a, int wmode, int len);
+int gaib_spmm_fused_fp8(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, const SpmmArgs& a, const FuseArgs& f, float* heavy_scratch, int wmode);
 
 namespace {
 
@@ -565,6 +571,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
             if (e < e_hi) {
               c = a.col[e];
               if constexpr (WMODE == 1 || WMODE == 2) w = load_edge_w<WMODE>(a, e);
+              if constexpr (gather_t::F8) w = fp8_fold_scale<GM>(a, c, WMODE == 0 ? 1.f : w);  // (the row weight changes along the stream: stream_w)
             }
           };
           if constexpr (RING) {
@@ -621,7 +628,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                   while (e_lo + k + u == row_end) flush();
-                  vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), gather_t::widen(x[u]));
+                  vacc<VEC>(acc, stream_w<WMODE, gather_t::F8>(roww, w_cur, kc + u), gather_t::widen(x[u]));
                   x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
                 }
               } else {
@@ -629,7 +636,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
                 for (int u = 0; u < U; ++u) {
                   if (k + u < total) {
                     while (e_lo + k + u == row_end) flush();
-                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w_cur, kc + u), gather_t::widen(x[u]));
+                    vacc<VEC>(acc, stream_w<WMODE, gather_t::F8>(roww, w_cur, kc + u), gather_t::widen(x[u]));
                   }
                   if (k + u + U < total)
                     x[u] = gather.load_raw((uint32_t)__builtin_amdgcn_readlane((int)c_src, (kc + u + U) & 63), voff[0]);
@@ -645,6 +652,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
             if (lane < n) {
               c = a.col[base + lane];
               if constexpr (WMODE == 1 || WMODE == 2) w = load_edge_w<WMODE>(a, base + lane);
+              if constexpr (gather_t::F8) w = fp8_fold_scale<GM>(a, c, WMODE == 0 ? 1.f : w);
             }
             typename gather_t::raw_t x[U];
             int j = 0;
@@ -656,7 +664,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
 #pragma unroll
               for (int u = 0; u < U; ++u) {
                 while (base + j + u == row_end) flush();
-                vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, j + u), gather_t::widen(x[u]));
+                vacc<VEC>(acc, stream_w<WMODE, gather_t::F8>(roww, w, j + u), gather_t::widen(x[u]));
               }
             }
             const int rest = n - j;
@@ -679,7 +687,7 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void spmm_gemm_kernel(SpmmArgs a, 
 #pragma unroll
                   for (int u = 0; u < p; ++u) {
                     while (base + jj + u == row_end) flush();
-                    vacc<VEC>(acc, (WMODE == 0) ? roww : readlane_f(w, jj + u), gather_t::widen(x[p + u]));
+                    vacc<VEC>(acc, stream_w<WMODE, gather_t::F8>(roww, w, jj + u), gather_t::widen(x[p + u]));
                   }
                   jj += p;
                 }
@@ -904,7 +912,7 @@ inline int fuse_strip_rows(int kpad, int n_out, bool dual) {
 struct FusedLaunch { unsigned grid; size_t lds; const char* key; double bytes, flops; };
 template <int VEC, int WMODE, bool PART, typename E>
 int fused_prologue(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArgs& a, FuseArgs& f, float* heavy_scratch, FusedLaunch* fl) {
-  constexpr bool BF = sizeof(E) == 2, ZS = ZsTraits<E>::zs;
+  constexpr bool BF = sizeof(E) == 2, F8 = sizeof(E) == 1, ZS = ZsTraits<E>::zs;
   // the hot/cold forms are compiled for 8-B lanes over an fp32 or zero-suppressed table of a whole graph
   constexpr bool HC = !PART && VEC == 2 && (std::is_same<E, float>::value || std::is_same<E, zs_t>::value);
   constexpr int U = 16;
@@ -922,7 +930,7 @@ int fused_prologue(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmA
     h.accumulate = 0;
     const size_t lds = sizeof(float) * HEAVY_WAVES * 64 * VEC;
     const dim3 hgrid((unsigned)g->n_heavy);
-    ProfScope ps(ctx, BF ? "spmm_bf16_heavy" : "spmm_heavy",
+    ProfScope ps(ctx, BF ? "spmm_bf16_heavy" : (F8 ? "spmm_fp8_heavy" : "spmm_heavy"),
                  gaib_alg_spmm_bytes((double)g->heavy_edges, (double)g->n_heavy, a.ncols, WMODE == 0 ? 0 : 4, 1, EB),
                  2.0 * g->heavy_edges * a.ncols, a.ncols);
     bool launched = false;
@@ -954,22 +962,25 @@ int fused_prologue(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmA
               r_all * 4.0 * f.n_out * (fm.yacc ? 2 : 1);
   fl->flops = 2.0 * e_l * a.ncols + 2.0 * r_all * a.ncols * f.n_out * (fm.dual ? 2 : 1);
   fl->key = BF ? (!PART ? "spmm_gemm_bf16_fused" : (a.in2 ? "part_bf16_fused_2t" : (f.agg_in ? "part_bf16_fused_acc" : "part_bf16_fused")))
+               : F8 ? "spmm_gemm_fp8_fused"
                : !PART ? "spmm_gemm_fused" : (a.in2 ? "part_fused_2t" : (f.agg_in ? "part_fused_acc" : "part_fused"));
   return GAIB_OK;
 }
 
 // One fused launch in the form fm (decided by spmm.hip's route function).  E = uint16_t: a.in (and a.in2) point at bf16 bits, a.ld counts elements, a.in_bytes / a.in2_bytes are the bf16 sizes.  Gathers in flight
 // per wave: a bf16 gather is held packed (half the registers of an fp32 one), so the row forms keep GAIB_BF16_FUSE_U of them where
-// fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  The XCD-affine tile supply is not compiled in for bf16 (it would
+// fp32 keeps 16, the edge-stream forms 16 where fp32 keeps 8.  E = fp8_t (whole graphs only): a.in points at e4m3 bytes, a.ld
+// counts bytes, a.in2 names the row scales; a gather is held in a quarter of the registers and takes bf16's depths; like bf16 it
+// has neither the affine supply nor the hot/cold form.  The XCD-affine tile supply is not compiled in for bf16 (it would
 // triple this set of instantiations for the planted-locality case alone; the supply changes no row's sum) nor for row classes
 // (rectangular graphs: their numbering is never measured as local): the form says global counter there.
 // Hot/cold gathers are compiled for ONE form only -- 8-B lanes, row form, 8-row strip, one product, global tile counter, buffer
 // addressing -- and for the heavy kernel next to it (fused_prologue).
 template <int VEC, int WMODE, bool PART = false, typename E = float>
 int launch_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArgs a, FuseArgs f, float* heavy_scratch) {
-  constexpr bool BF = sizeof(E) == 2;
-  constexpr int UROW = BF ? GAIB_BF16_FUSE_U : 16;  // row forms
-  constexpr int UFLAT = BF ? 16 : 8;                 // edge-stream forms
+  constexpr bool BF = sizeof(E) == 2, F8 = sizeof(E) == 1;  // (an fp8 gather in flight is held in a quarter of the registers: bf16's depths)
+  constexpr int UROW = BF || F8 ? GAIB_BF16_FUSE_U : 16;  // row forms
+  constexpr int UFLAT = BF || F8 ? 16 : 8;                 // edge-stream forms
   FusedLaunch fl;
   GAIB_TRY((fused_prologue<VEC, WMODE, PART, E>(ctx, g, fm, a, f, heavy_scratch, &fl)));
   ProfScope ps(ctx, fl.key, fl.bytes, fl.flops, a.ncols);
@@ -990,7 +1001,7 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArg
 #define GAIB_FUSED_LAUNCH_R(GM, STRIP, DUAL, FLAT, YACC, RING)                                                        \
   do {                                                                                                                \
     bool affine = false;                                                                                              \
-    if constexpr (!PART && !BF) {                                                                                     \
+    if constexpr (!PART && !BF && !F8) {                                                                              \
       if (fm.tile_xcd) {                                                                                              \
         affine = true;                                                                                                \
         if (!FLAT && ctx->spmm_prefetch_ids) GAIB_FUSED_LAUNCH_P(GM, STRIP, DUAL, FLAT, YACC, RING, true, !FLAT);     \
@@ -1017,7 +1028,7 @@ int launch_fused(gaib_ctx* ctx, const gaib_graph* g, const FuseForm& fm, SpmmArg
       launched = true;
     }
   }
-  if constexpr (!PART && !BF && VEC == 2) {
+  if constexpr (!PART && !BF && !F8 && VEC == 2) {
     if (fm.hot_cold) {
       GAIB_FUSED_LAUNCH_P(3, 8, false, false, false, false, false, false);
       ctx->spmm_hot_cold_launches++;

@@ -86,6 +86,61 @@ static bool bf16_for(Graph& g, int len) {
   return !g.has_halo() || len % 2 == 0;
 }
 
+// ---- fp8 feature tables with per-row scales (option agg_fp8) ---------------------------------------------------------------
+bool aggregator::fp8_tables() { return gaib_host::option("agg_fp8") != 0; }
+// One process-wide scratch holding the table ([rows x ld] bytes, rounded up to 256) and its row scales behind it.  Grown outside
+// captures only and retired, not freed, like g_bf16_tab: a recorded epoch may still name a buffer that had to grow.
+static uint8_t* g_fp8_tab = nullptr;
+static size_t g_fp8_cap = 0;
+static gaib_ctx* g_fp8_ctx = nullptr;
+static std::vector<uint8_t*> g_fp8_retired;
+static uint8_t* fp8_scratch(size_t bytes) {
+  if (g_fp8_ctx != C()) {  // a new process context (gpu_context::set): start a buffer on its device
+    if (g_fp8_tab) g_fp8_retired.push_back(g_fp8_tab);
+    g_fp8_tab = nullptr;
+    g_fp8_cap = 0;
+    g_fp8_ctx = C();
+  }
+  if (bytes > g_fp8_cap) {
+    if (g_fp8_tab) g_fp8_retired.push_back(g_fp8_tab);
+    g_fp8_tab = nullptr;
+    g_fp8_cap = 0;
+    // (inside a capture gaib_malloc refuses: the run has to reserve the scratch before it records)
+    GAIB_OR_DIE(gaib_malloc(C(), bytes, (void**)&g_fp8_tab));
+    g_fp8_cap = bytes;
+  }
+  return g_fp8_tab;
+}
+struct Fp8Table {
+  const uint8_t* q;
+  const float* scale;
+  int64_t ld;
+};
+// the table of a WHOLE graph `dg` (`len` floats per row at `in`) cast into the scratch at gaib_fp8_row_stride's stride
+static Fp8Table to_fp8(gaib_graph* dg, int len, const float* in) {
+  const size_t rows = (size_t)gaib_graph_nc(dg);
+  Fp8Table t;
+  GAIB_OR_DIE(gaib_fp8_row_stride(len, &t.ld));
+  const size_t tab_bytes = (rows * (size_t)t.ld + 255) & ~(size_t)255;
+  uint8_t* base = fp8_scratch(tab_bytes + rows * sizeof(float));
+  float* scale = reinterpret_cast<float*>(base + tab_bytes);
+  GAIB_OR_DIE(gaib_cast_f32_fp8_rows(C(), (int64_t)rows, len, in, t.ld, base, scale));
+  t.q = base;
+  t.scale = scale;
+  return t;
+}
+// does this aggregation run on an fp8 table?  Whole graphs: always under agg_fp8.  A graph with a halo (partitioned run) has no
+// exchange that carries fp8 rows with their scales and no row-class kernels: refused, never a silent fp32 path.
+static bool fp8_for(Graph& g) {
+  if (!aggregator::fp8_tables()) return false;
+  if (g.has_halo()) {
+    fprintf(stderr, "GPU error: agg_fp8 (GAIB_AGG_DTYPE=fp8) on a graph with a halo (partitioned run): fp8 feature tables are "
+            "gathered on whole graphs only\n");
+    exit(EXIT_FAILURE);
+  }
+  return true;
+}
+
 // ---- zero-suppressed gradient tables (option agg_zs) ---------------------------------------------------------------------
 // Where the packed launch set (pack + heavy + fused) stops beating the dense one: the share of rows over capacity from which
 // the layers gather dense.  An over-capacity row costs a dense 512-B gather that the wave waits for on top of its packed one.
@@ -293,6 +348,7 @@ static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* 
   if (count) count_edges(g);
   const int act = relu ? GAIB_RELU : 0;
   const bool bf16 = bf16_for(g, len);
+  const bool fp8 = fp8_for(g);
   if (g.has_halo()) {
     auto run = [&](auto tab) {
       partitioned(g, kind, len, tab, out, true, [&](gaib_graph* dg, decltype(tab) t, decltype(tab) t2, int64_t n_first, int extra) {
@@ -310,6 +366,12 @@ static void aggregate_rows(Graph& g, int kind, int len, const float* in, float* 
     GAIB_OR_DIE(gaib_spmm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, out, act));
     return;
   }
+  if (fp8) {
+    gaib_graph* dg = dev(g);
+    const Fp8Table t = to_fp8(dg, len, in);
+    GAIB_OR_DIE(gaib_spmm_fp8(C(), dg, kind, NULL, len, t.ld, t.q, t.scale, out, act));
+    return;
+  }
   GAIB_OR_DIE(gaib_spmm_ex(C(), dev(g), kind, NULL, len, in, out, act));
 }
 
@@ -319,6 +381,7 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
   OpTimer t(OP_SPARSEMM);
   count_edges(g);
   const bool bf16 = bf16_for(g, len);
+  const bool fp8 = fp8_for(g);
   const int act = relu ? GAIB_RELU : 0;
   const int flags = act | (keep_agg ? 0 : GAIB_AGG_SCRATCH);
   const Product prod{agg, W, transW ? 1 : 0, rows2, W2, len_out, out};
@@ -361,6 +424,17 @@ void aggregator::aggregate_then_matmul(int kind, int len, Graph& g, const float*
       GAIB_OR_DIE(gaib_spmm_gemm2_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, flags));
     else
       GAIB_OR_DIE(gaib_spmm_gemm_bf16_ld(C(), dg, kind, NULL, len, ld, tab, agg, W, transW ? 1 : 0, len_out, out, flags));
+    return;
+  }
+  if (fp8) {
+    // fp8 table with row scales: the route (and the bits) of the fp32 branch below on the rounded table; ahead of the
+    // zero-suppressed branch like bf16.  The self rows stay fp32 (option gemm_bf16 is inert without a bf16 table).
+    gaib_graph* dg = dev(g);
+    const Fp8Table t = to_fp8(dg, len, in);
+    if (rows2)
+      GAIB_OR_DIE(gaib_spmm_gemm2_fp8(C(), dg, kind, NULL, len, t.ld, t.q, t.scale, agg, W, transW ? 1 : 0, rows2, W2, len_out, out, flags));
+    else
+      GAIB_OR_DIE(gaib_spmm_gemm_fp8(C(), dg, kind, NULL, len, t.ld, t.q, t.scale, agg, W, transW ? 1 : 0, len_out, out, flags));
     return;
   }
   // (256 columns, option agg_zs_wide: the K-slab route, whose launches are one-product ones -- ZS_TWO_PRODUCTS concerns the

@@ -57,15 +57,16 @@ void gpu_context::set(int device, void* hip_stream) {
       pos = end + 1;
     }
   }
-  // the precision of the aggregations' feature tables (GCN / SAGE): fp32 (default) or bf16 -- a user-facing switch, so that
-  // a driver linked against the layer library gets bf16 tables without code changes
+  // the precision of the aggregations' feature tables (GCN / SAGE): fp32 (default), bf16, or fp8 with per-row scales -- a
+  // user-facing switch, so that a driver linked against the layer library gets narrow tables without code changes
   if (const char* d = getenv("GAIB_AGG_DTYPE")) {
     const std::string dt(d);
-    if (dt != "fp32" && dt != "bf16") {
-      fprintf(stderr, "GAIB_AGG_DTYPE=%s: expected fp32 or bf16\n", d);
+    if (dt != "fp32" && dt != "bf16" && dt != "fp8") {
+      fprintf(stderr, "GAIB_AGG_DTYPE=%s: expected fp32, bf16 or fp8\n", d);
       exit(EXIT_FAILURE);
     }
     check(gaib_set_option(g_ctx, "agg_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_AGG_DTYPE)");
+    check(gaib_set_option(g_ctx, "agg_fp8", dt == "fp8" ? 1 : 0), "gaib_set_option (GAIB_AGG_DTYPE)");
   }
   // the dense self products of the SAGE layers under bf16 tables: fp32 rows (default) or the bf16 table with exactly split
   // weights (option gemm_bf16; without GAIB_AGG_DTYPE=bf16 there is no table and nothing changes)

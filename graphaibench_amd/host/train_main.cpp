@@ -203,6 +203,13 @@ struct Trainer {
     // l2norm + dense head for sampling and GAT (net.cpp:69-71)
     if (subg_size > 0 || ARCH == gnn_arch::GAT) use_l2norm = use_dense = true;
     if (subg_size > 0) inductive = 1;  // net.cpp:160
+    // fp8 tables (GAIB_AGG_DTYPE=fp8, context option agg_fp8) take whole graphs: refused on more than one rank BEFORE the
+    // communicator is built -- every rank reads the same environment and leaves alike, none waits in a collective
+    const bool fp8 = aggregator::fp8_tables();
+    if (fp8 && env_int("GAIB_WORLD", "WORLD_SIZE", 1) > 1) {
+      std::cerr << "GAIB_AGG_DTYPE=fp8 (agg_fp8) runs on one GPU only: fp8 feature tables have no halo exchange and no row-class kernels\n";
+      exit(EXIT_FAILURE);
+    }
     init_comm();
     if (ARCH == gnn_arch::GAT) {
       // GAT's own tables: fp32, or bf16 with GAIB_GAT_DTYPE=bf16 (context option gat_bf16; whole graphs only)
@@ -225,16 +232,19 @@ struct Trainer {
         exit(EXIT_FAILURE);
       }
     }
-    if (root())
+    // (fp8 tables say so on a line of their own; GAT gathers fp32 whatever the option says)
+    if (fp8 && root())
+      std::cout << "[gaib] aggregation tables: " << (ARCH == gnn_arch::GAT ? "fp32 (fp8 asked; GAT gathers fp32)" : "fp8") << "\n";
+    else if (root())
       std::cout << "aggregation tables: "
                 << (bf16 ? (ARCH == gnn_arch::GAT ? "fp32 (bf16 asked; GAT gathers fp32)"
                                                   : (world > 1 ? "bf16 (odd widths on a partition: fp32)" : "bf16"))
                          : "fp32")
                 << "\n";
     if (aggregator::gemm_bf16_products() && root()) std::cout << "dense self products: bf16 tables\n";
-    if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root())
+    if (world == 1 && !bf16 && !fp8 && ARCH != gnn_arch::GAT && root())
       std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
-    if (world == 1 && !bf16 && ARCH != gnn_arch::GAT && root() && aggregator::zs_wide_tables())
+    if (world == 1 && !bf16 && !fp8 && ARCH != gnn_arch::GAT && root() && aggregator::zs_wide_tables())
       std::cout << "relu-masked gradients of 256 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs_wide = 1)" : "dense (agg_zs = 0 overrides agg_zs_wide = 1)") << "\n";
     if (bf16 && world > 1 && ARCH == gnn_arch::GAT) {
       std::cerr << "GAIB_AGG_DTYPE=bf16 with GAT runs on one GPU only (GAT gathers fp32 tables; GCN and SAGE take bf16 tables on a partition)\n";
@@ -1000,7 +1010,15 @@ int launch_ranks(int n, char** argv) {
 
 int main(int argc, char* argv[]) {
   if (const char* nr = getenv("GAIB_RANKS")) {
-    if (atoi(nr) > 1 && !getenv("RANK") && !getenv("GAIB_RANK")) return launch_ranks(atoi(nr), argv);
+    if (atoi(nr) > 1 && !getenv("RANK") && !getenv("GAIB_RANK")) {
+      // (what every rank would say in parse(), said once and before any rank is started)
+      if (const char* dt = getenv("GAIB_AGG_DTYPE"))
+        if (std::string(dt) == "fp8") {
+          std::cerr << "GAIB_AGG_DTYPE=fp8 (agg_fp8) runs on one GPU only: fp8 feature tables have no halo exchange and no row-class kernels\n";
+          return EXIT_FAILURE;
+        }
+      return launch_ranks(atoi(nr), argv);
+    }
   }
   if (argc <= 4 || (argc > 9 && argc != 13)) {
     std::cout << "Usage: ./train data num_epochs num_threads type_loss "

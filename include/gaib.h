@@ -638,6 +638,44 @@ int gaib_spmm_gemm_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const 
 int gaib_spmm_gemm2_bf16_ld(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
                             const uint16_t* d_in, float* d_agg, const float* d_W, int transW, const float* d_rows2,
                             const float* d_W2, int len_out, float* d_out, int flags);
+/* ---- fp8 feature tables with per-row scales (opt-in) ----
+ * Elements: OCP e4m3 "fn", the encoding of torch.float8_e4m3fn -- 1-4-3, bias 7, largest finite 448, no infinities, NaN = 0x7f /
+ * 0xff.  A table is raw uint8_t [rows x ld], ld the row stride in BYTES, with a float [rows] array of row scales next to it.
+ * gaib_fp8_row_stride (pure: no device, no graph): *ld = len where len % 128 == 0; else the next power of two >= max(len, 4) for
+ * len <= 128; else len rounded up to a multiple of 128.  With the table on a 128-byte boundary no row of <= 128 columns
+ * straddles a 128-byte line and wider rows start on one.
+ * gaib_cast_f32_fp8_rows: d_in dense fp32 [rows x len] -> d_q [rows x ld] (ld >= len, ld % 4 == 0, d_q 4-byte aligned) and
+ * d_scale [rows].  scale[r] is exactly 2^k, k the smallest integer with amax(r) * 2^-k <= 448, clamped to [-126, 120]; amax is
+ * taken over the row's finite elements; k = 0 for a row with no non-zero finite element.  The element stored is x * 2^-k (exact)
+ * rounded to nearest, ties to even; a magnitude still above 448 saturates to +-448; a NaN stays a NaN of its sign; +-inf
+ * becomes the NaN of its sign (the format has no infinity).  Pad bytes (columns len .. ld - 1) are written as 0.  One kernel,
+ * no host wait, no allocation: legal inside a stream capture.
+ * gaib_cast_fp8_f32_rows: the widening, dense [rows x len] output: out[r][c] = f32(q[r][c]) * scale[r]; both steps are exact.
+ * gaib_spmm_fp8: gaib_spmm_ex over such a table -- flags GAIB_ACCUMULATE | GAIB_RELU, the five single-head weight kinds, square
+ * and rectangular graphs, any len >= 1.  d_out is BIT-IDENTICAL to gaib_spmm_ex on the widened table (gaib_cast_fp8_f32_rows),
+ * for every row, while w_e * scale[col_e] and the products stay normal fp32 numbers: the scale of an edge's column is multiplied
+ * into the edge's weight -- an exact product that commutes with the rounding of w * x --, everything after the gather is the fp32
+ * kernels' own (edge order, separate multiply and add, heavy threshold, the 16-wave combine, the ordered-chunk rule decided on
+ * the fp32 sizes).  Where the product w_e * scale[col_e] or a term leaves the normal range (an under- or overflow the fp32 call on
+ * the widened table would meet at another point), the results may differ.  Profile keys spmm_fp8_light / _heavy / _chunk.
+ * gaib_spmm_gemm_fp8 / gaib_spmm_gemm2_fp8: gaib_spmm_gemm / gaib_spmm_gemm2 over such a table (the arguments of the bf16 _ld
+ * calls with d_q, d_scale in place of the bf16 table): the route is the fp32 call's on the widened table, every route test made
+ * on the fp32 sizes; d_agg (unless GAIB_AGG_SCRATCH) and d_out bit-identical to it under the same condition.  Profile key
+ * spmm_gemm_fp8_fused.
+ * Refused with GAIB_ERR_UNSUPPORTED, a message and nothing touched: a graph with a row map (a row class of a partition), a table
+ * of 4 GB or more (buffer addressing only), a table not on a 16-byte boundary.  The calls take no head count: multi-head weights
+ * have no fp8 form.  Two-table gathers and zero-suppressed tables have none either. */
+int gaib_fp8_row_stride(int len, int64_t* ld);
+int gaib_cast_f32_fp8_rows(gaib_ctx* ctx, int64_t rows, int len, const float* d_in, int64_t ld, uint8_t* d_q, float* d_scale);
+int gaib_cast_fp8_f32_rows(gaib_ctx* ctx, int64_t rows, int len, int64_t ld, const uint8_t* d_q, const float* d_scale, float* d_out);
+int gaib_spmm_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len, int64_t ld, const uint8_t* d_q,
+                  const float* d_scale, float* d_out, int flags);
+int gaib_spmm_gemm_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                       const uint8_t* d_q, const float* d_scale, float* d_agg, const float* d_W, int transW, int len_out,
+                       float* d_out, int flags);
+int gaib_spmm_gemm2_fp8(gaib_ctx* ctx, gaib_graph* g, int weight_kind, const float* d_edge_w, int len_in, int64_t ld,
+                        const uint8_t* d_q, const float* d_scale, float* d_agg, const float* d_W, int transW, const float* d_rows2,
+                        const float* d_W2, int len_out, float* d_out, int flags);
 /* bf16 tables on the row classes of a vertex-range partition (the functions above keep their refusals; the capability has
  * names of its own).  d_in / d_in2 hold bf16 bits, everything else is fp32.
  * gaib_spmm_part_bf16: with d_in2 == NULL gaib_spmm_ex on a bf16 table (n_first is ignored), with d_in2 != NULL gaib_spmm_2t on
@@ -970,11 +1008,15 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "spmm_bf16_fuse_u" (0; benchmark only, readable): gathers a wave keeps in flight in the headline variant of the bf16 fused
  * kernel (row form, 8-row strip, buffer addressing, 65..128 columns): 0 = what ships, 16 / 32 = that depth.  Same bits.
  * "sampler_device" (default 0; readable): read by the trainer, not by the library: 1 = every sampled epoch's subgraph, feature
- * rows and label rows are built on the device (gaib_graph_induce, gaib_gather_rows, gaib_gather_rows_u8), 0 = on the host. */
+ * rows and label rows are built on the device (gaib_graph_induce, gaib_gather_rows, gaib_gather_rows_u8), 0 = on the host.
+ * A third feature option: "agg_fp8" (default 0; readable): 1 = the layer library's GCN and SAGE aggregations of whole graphs gather
+ * from an fp8 copy of their table with per-row scales (gaib_cast_f32_fp8_rows at gaib_fp8_row_stride's stride + gaib_spmm_fp8 /
+ * gaib_spmm_gemm_fp8 / gaib_spmm_gemm2_fp8); setting it while "agg_bf16" is 1, or "agg_bf16" while it is 1, is GAIB_ERR_INVALID; a
+ * graph with a halo refuses it; GAT ignores it. */
 int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
 /* what a record wants to name: "comm_reserve_cus" (CUs the fused kernel leaves to the transport: the EFFECTIVE figure -- option,
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
- * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
+ * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
  * "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);

@@ -19,6 +19,12 @@ class aggregator {
   // one partition sequence of host/aggregators.cpp (partitioned<T>), which fp32 tables run through as well; odd
   // widths run in fp32 there; a halo with fp32 callbacks only refuses the option.
   static bool bf16_tables();
+  // extension: fp8 feature tables with per-row scales (context option "agg_fp8" = 1, or GAIB_AGG_DTYPE=fp8; never together
+  // with "agg_bf16"): on a whole graph the GCN / SAGE aggregations cast their table into a process-wide scratch -- e4m3 bytes
+  // at gaib_fp8_row_stride's stride, a power-of-two scale per row -- and gather from there (gaib_spmm_fp8, gaib_spmm_gemm_fp8 /
+  // gaib_spmm_gemm2_fp8 where the product rides along; fp32 sums and output): the fp32 layer on the rounded table.  The scratch
+  // grows on first use, outside a capture, like the bf16 one.  A graph with a halo refuses the option; GAT ignores it.
+  static bool fp8_tables();
   // extension: dense self products on that bf16 table (context option "gemm_bf16" = 1, or GAIB_GEMM_DTYPE=bf16; only under
   // bf16_tables()): where a SAGE layer on a whole graph runs its self term as a separate accumulating product and
   // gaib_gemm_bf16 covers the shape, the product multiplies the table the aggregation has just cast (weights split exactly
