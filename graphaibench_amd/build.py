@@ -21,7 +21,7 @@ INCLUDE = ROOT / "include"
 ORACLE = ROOT / "oracle"
 REFERENCE = Path("/root/reference")
 
-HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_fp8.hip", "spmm_gemm_fp8.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "elementwise.hip", "probe.hip", "comm.hip"]
+HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_fp8.hip", "spmm_gemm_fp8.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "sgemm_split.hip", "elementwise.hip", "probe.hip", "comm.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -35,6 +35,9 @@ HIPCC_FLAGS = [
     # a kernel that misses its own __launch_bounds__ occupancy target is an error, not a remark (round 6: 21 sgemm tilings did)
     "-Werror=pass-failed",
 ]
+# per translation unit, on top of HIPCC_FLAGS: sgemm_split.hip's register split is scalar fp32 arithmetic by design (one
+# subtraction per value and plane) -- the compiler forms no packed fp32 instructions there
+HIPCC_EXTRA = {"sgemm_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -67,7 +70,7 @@ def build_hip(force: bool = False) -> Path:
         s = CSRC / src
         o = LIB / (src + ".o")
         if force or _stale(o, [s, *headers]):
-            jobs.append([hipcc, *HIPCC_FLAGS, f"-I{INCLUDE}", f"-I{CSRC}", "-c", s, "-o", o])
+            jobs.append([hipcc, *HIPCC_FLAGS, *HIPCC_EXTRA.get(src, []), f"-I{INCLUDE}", f"-I{CSRC}", "-c", s, "-o", o])
         objs.append(o)
     if jobs:  # the translation units are independent: compile them side by side (a clean build drops from 4 to ~1.5 min)
         from concurrent.futures import ThreadPoolExecutor

@@ -135,6 +135,8 @@ SIGNATURES = {
     "gaib_sgemm_ex": (_i, [_vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _i, _vp]),
     "gaib_gemm_bf16": (_i, [_vp, _i, _i64, _i, _i, _i64, _vp, _vp, _i, _vp]),
     "gaib_gemm_bf16_cover": (_i, [_vp, _i, _i, _i, _i64]),
+    "gaib_sgemm_split": (_i, [_vp, _i, _i64, _i, _i, _i64, _vp, _vp, _i, _vp]),
+    "gaib_sgemm_split_cover": (_i, [_vp, _i, _i, _i, _i64]),
     "gaib_bias_add": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_colsum": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_rng_uniform": (_i, [_vp, _i64, _f, _f, _u64, _vp]),
@@ -1098,6 +1100,25 @@ class Context:
     def gemm_bf16_cover(self, N: int, K: int, lda: int, transB=False) -> bool:
         """gaib_gemm_bf16_cover: would gaib_gemm_bf16 run this shape and stride (option gemm_bf16_kernel included)?"""
         return bool(self.lib.gaib_gemm_bf16_cover(self.h, int(transB), N, K, lda))
+
+    def sgemm_split(self, A, B, Cm, K=None, transB=False, accum=False, relu=False):
+        """gaib_sgemm_split: Cm[M x N] (=|+=) A[:, :K] . op(B) for fp32 A [M x lda] (K defaults to lda) and fp32 B ([K x N], or
+        [N x K] with transB), both split exactly into bf16 planes on the device.  Raises GaibError (status -5) where
+        sgemm_split_cover says no."""
+        import torch
+
+        assert A.dtype == torch.float32 and A.dim() == 2 and A.is_contiguous() and Cm.is_contiguous() and B.is_contiguous()
+        M, N = Cm.shape
+        lda = A.shape[1]
+        K = lda if K is None else K
+        assert A.shape[0] == M and tuple(B.shape) == ((N, K) if transB else (K, N))
+        flags = (1 if accum else 0) | (2 if relu else 0)
+        _check(self.lib.gaib_sgemm_split(self.h, int(transB), M, N, K, lda, _ptr(A), _ptr(B), flags, _ptr(Cm)), "gaib_sgemm_split")
+        return Cm
+
+    def sgemm_split_cover(self, N: int, K: int, lda: int, transB=False) -> bool:
+        """gaib_sgemm_split_cover: would gaib_sgemm_split run this shape and stride (option sgemm_split_kernel included)?"""
+        return bool(self.lib.gaib_sgemm_split_cover(self.h, int(transB), N, K, lda))
 
     # ---- elementwise / loss / optimizer -----------------------------------------------------
     def bias_add(self, x, b):

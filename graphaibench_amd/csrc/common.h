@@ -106,6 +106,8 @@ struct gaib_ctx {
   int agg_fp8;               // 1: ... from an fp8 copy with per-row scales (gaib_cast_f32_fp8_rows, gaib_spmm_fp8, gaib_spmm_gemm_fp8); never together with agg_bf16
   int gemm_bf16;             // 1: the layer library's SAGE self products multiply the bf16 table the aggregation has just cast (gaib_gemm_bf16) where it covers the shape
   int gemm_bf16_kernel;      // 1 (default): gaib_gemm_bf16 runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_gemm_bf16_cover says 0
+  int sgemm_split;           // 1: gaib_sgemm_ex / gaib_sgemm hand a product with transA = 0 that gaib_sgemm_split covers to it before any other route
+  int sgemm_split_kernel;    // 1 (default): gaib_sgemm_split runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_sgemm_split_cover says 0
   int sgemm_variant;         // 0 = auto
   int gat_fast;              // reserved
   int gat_chunk_colsum;      // GAT backward column sums by ordered chunks: -1 = dense graphs, 0 never, 1 always

@@ -26,6 +26,9 @@ int gaib_sgemm_skinny_try(gaib_ctx* ctx, int transA, int transB, int64_t M, int6
                           const float* d_B, int flags, float* d_C, int* handled);
 int gaib_sgemm_wide_tn_try(gaib_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* d_A, float* d_G, const float* d_mask,
                            int flags, float* d_C, int* handled);
+// sgemm_split.hip: true when the option sgemm_split is on and gaib_sgemm_split covers the call (shape, pointers, no aliasing)
+bool gaib_sgemm_split_takes(gaib_ctx* ctx, int transA, int transB, int64_t N, int64_t K, const float* d_A, const float* d_B,
+                            const float* d_C);
 
 namespace {
 
@@ -1055,6 +1058,9 @@ extern "C" int gaib_sgemm_ex(gaib_ctx* ctx, int transA, int transB, int64_t M, i
     gaib_set_error("gaib_sgemm: transA && transB is not on the GNN path (unsupported)");
     return GAIB_ERR_UNSUPPORTED;
   }
+  // option sgemm_split (default 0): a covered product with transA = 0 runs on the bf16 matrix cores, both operands split exactly
+  if (gaib_sgemm_split_takes(ctx, transA, transB, N, K, d_A, d_B, d_C))
+    return gaib_sgemm_split(ctx, transB, M, (int)N, (int)K, K, d_A, d_B, flags, d_C);
   {  // round 6: the products whose output or inner width is the class / input feature count (sgemm_skinny.hip)
     int handled = 0;
     GAIB_TRY(gaib_sgemm_skinny_try(ctx, transA, transB, M, N, K, d_A, d_B, flags, d_C, &handled));

@@ -724,6 +724,26 @@ int gaib_gemm_bf16(gaib_ctx* ctx, int transB, int64_t M, int N, int K, int64_t l
 /* 1 when the call above would run (shape, stride and option "gemm_bf16_kernel" only; no pointer, no launch), else 0 */
 int gaib_gemm_bf16_cover(gaib_ctx* ctx, int transB, int N, int K, int64_t lda);
 
+/* ---- fp32 dense product on the bf16 matrix cores, both operands split exactly (sgemm_split.hip) ----
+ * C[M x N] (=|+=) A . op(B), A fp32 [M x K] at row stride lda (elements), B fp32 ([K x N], or [N x K] with transB), C fp32
+ * [M x N] dense; flags = GAIB_ACCUMULATE | GAIB_RELU as gaib_sgemm_ex.
+ * op(B) is split on the device into the three planes of gaib_gemm_bf16 (same rule, same bits).  Every finite A[i][k] with
+ * |a| >= 2^-100 is split in registers, by truncation, into three bf16 values whose sum is a exactly (truncation cannot overflow:
+ * FLT_MAX stays finite).  All nine plane products of every term are exact in fp32 and enter an fp32 accumulator of the bf16
+ * matrix cores: the result is a sum of 9 K exact terms (+ C when accumulating), the only rounding the accumulation's.  Every
+ * output element comes from one wave in one fixed instruction sequence: bit-identical from run to run and independent of how M
+ * is spread over waves; not bit-identical to any fp32 call.  A non-finite A[i][k] makes exactly the outputs of row i non-finite;
+ * an infinity surfaces as NaN (inf - inf in the split).  No host wait, no workspace: safe inside gaib_capture_begin/end.
+ * Cover: 4 <= K <= 256, K % 4 == 0; 4 <= N <= 256, N % 4 == 0; lda >= K, lda % 4 == 0 (and lda <= 2^22); d_A and d_C on 16-byte
+ * boundaries; any M >= 0 (M == 0: GAIB_OK, nothing launched); option "sgemm_split_kernel" = 1.  Anything else:
+ * GAIB_ERR_UNSUPPORTED with nothing written -- the caller falls back to gaib_sgemm_ex.  Columns K .. lda - 1 of a row and rows
+ * past M are never consumed.  A and C go through per-tile buffer descriptors: 4 GB and more need no other path.
+ * Profile: key "sgemm_split", tag MxNxK; bytes 4 M K + 4 M N (1 + accum) + 4 K N, flops 2 M N K (the useful ones, not x 9). */
+int gaib_sgemm_split(gaib_ctx* ctx, int transB, int64_t M, int N, int K, int64_t lda, const float* d_A, const float* d_B,
+                     int flags, float* d_C);
+/* 1 when the call above would run (shape, stride and option "sgemm_split_kernel" only; no pointer, no launch), else 0 */
+int gaib_sgemm_split_cover(gaib_ctx* ctx, int transB, int N, int K, int64_t lda);
+
 /* weight gradient with the layer's d_relu folded in (d_relu_gpu on grad_in followed by matmul(transA),
  * gcn_layer.cpp:33-52): d_G <- d_G where d_mask > 0 else 0 (IN PLACE, what d_relu_gpu leaves behind) and
  * C[M x N] (=|+=) A^T . G for A [K x M], G / mask [K x N].  One pass over G instead of two. */
@@ -988,6 +1008,11 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * gaib_gemm_bf16_cover says 1, that product is gaib_gemm_bf16 on the bf16 table the aggregation has just cast instead of
  * gaib_sgemm_ex on the fp32 rows; "gemm_bf16_kernel" (default 1): 0 = gaib_gemm_bf16 refuses every call (GAIB_ERR_UNSUPPORTED),
  * gaib_gemm_bf16_cover says 0;
+ * "sgemm_split" (default 0; readable): 1 = gaib_sgemm_ex and gaib_sgemm hand a call with transA = 0 that gaib_sgemm_split covers
+ * (gaib_sgemm_split_cover at lda = K, A and C on 16-byte boundaries, C no alias of an operand) to gaib_sgemm_split before any other
+ * route: the layer library's matmul, the dense routes of the fused aggregation, GAT's X . W, the class products of partitions;
+ * weight gradients (transA = 1) and uncovered shapes keep their routes; "sgemm_split_kernel" (default 1; readable): 0 =
+ * gaib_sgemm_split refuses every call (GAIB_ERR_UNSUPPORTED), gaib_sgemm_split_cover says 0, and "sgemm_split" = 1 changes nothing;
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
  * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs), and
  * gaib_gat_forward_fused_drop_bf16 / gaib_gat_backward_fused_drop_bf16 where attention dropout stays in the sweep ("gat_fused_drop"
@@ -1018,7 +1043,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
+ * "sgemm_split", "sgemm_split_kernel", "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus
