@@ -137,6 +137,9 @@ SIGNATURES = {
     "gaib_gemm_bf16_cover": (_i, [_vp, _i, _i, _i, _i64]),
     "gaib_sgemm_split": (_i, [_vp, _i, _i64, _i, _i, _i64, _vp, _vp, _i, _vp]),
     "gaib_sgemm_split_cover": (_i, [_vp, _i, _i, _i, _i64]),
+    "gaib_sgemm_split_tn": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
+    "gaib_sgemm_split_tn_cover": (_i, [_vp, _i64, _i64]),
+    "gaib_sgemm_split_tn_parts": (_i, [_vp, _i64, _i64, _i64]),
     "gaib_bias_add": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_colsum": (_i, [_vp, _i64, _i, _vp, _vp]),
     "gaib_rng_uniform": (_i, [_vp, _i64, _f, _f, _u64, _vp]),
@@ -1119,6 +1122,29 @@ class Context:
     def sgemm_split_cover(self, N: int, K: int, lda: int, transB=False) -> bool:
         """gaib_sgemm_split_cover: would gaib_sgemm_split run this shape and stride (option sgemm_split_kernel included)?"""
         return bool(self.lib.gaib_sgemm_split_cover(self.h, int(transB), N, K, lda))
+
+    def sgemm_split_tn(self, A, G, Cm, mask=None, accum=False):
+        """gaib_sgemm_split_tn: Cm[M x N] (=|+=) A^T . G for fp32 A [K x M] and G [K x N], both split exactly into bf16 planes on
+        the device; with mask [K x N], G <- where(mask > 0, G, +0.0) in place first.  Raises GaibError (status -5) where
+        sgemm_split_tn_cover says no."""
+        import torch
+
+        assert A.dtype == torch.float32 and G.dtype == torch.float32 and A.dim() == 2 and G.dim() == 2
+        assert A.is_contiguous() and G.is_contiguous() and Cm.is_contiguous() and (mask is None or mask.is_contiguous())
+        K, M = A.shape
+        N = G.shape[1]
+        assert G.shape[0] == K and tuple(Cm.shape) == (M, N) and (mask is None or mask.shape == G.shape)
+        _check(self.lib.gaib_sgemm_split_tn(self.h, M, N, K, _ptr(A), _ptr(G), _ptr(mask) if mask is not None else None,
+                                            1 if accum else 0, _ptr(Cm)), "gaib_sgemm_split_tn")
+        return Cm
+
+    def sgemm_split_tn_cover(self, M: int, N: int) -> bool:
+        """gaib_sgemm_split_tn_cover: would gaib_sgemm_split_tn run this output shape?"""
+        return bool(self.lib.gaib_sgemm_split_tn_cover(self.h, M, N))
+
+    def sgemm_split_tn_parts(self, M: int, N: int, K: int) -> int:
+        """gaib_sgemm_split_tn_parts: partial slabs summed into each output element (1: C is written directly)"""
+        return int(self.lib.gaib_sgemm_split_tn_parts(self.h, M, N, K))
 
     # ---- elementwise / loss / optimizer -----------------------------------------------------
     def bias_add(self, x, b):

@@ -108,6 +108,7 @@ struct gaib_ctx {
   int gemm_bf16_kernel;      // 1 (default): gaib_gemm_bf16 runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_gemm_bf16_cover says 0
   int sgemm_split;           // 1: gaib_sgemm_ex / gaib_sgemm hand a product with transA = 0 that gaib_sgemm_split covers to it before any other route
   int sgemm_split_kernel;    // 1 (default): gaib_sgemm_split runs; 0: it returns GAIB_ERR_UNSUPPORTED and gaib_sgemm_split_cover says 0
+  int sgemm_split_tn;        // 1: gaib_sgemm_ex (transA = 1, transB = 0, no GAIB_RELU) and gaib_sgemm_drelu hand a weight gradient that gaib_sgemm_split_tn covers to it before any other route
   int sgemm_variant;         // 0 = auto
   int gat_fast;              // reserved
   int gat_chunk_colsum;      // GAT backward column sums by ordered chunks: -1 = dense graphs, 0 never, 1 always

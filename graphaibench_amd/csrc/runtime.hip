@@ -80,6 +80,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->gemm_bf16_kernel = 1;
   c->sgemm_split = 0;
   c->sgemm_split_kernel = 1;
+  c->sgemm_split_tn = 0;
   c->agg_zs = 1;
   c->agg_zs_wide = 0;
   c->agg_zs_paused = 0;
@@ -553,6 +554,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "gemm_bf16_kernel")) *h_value = ctx->gemm_bf16_kernel;
   else if (!strcmp(key, "sgemm_split")) *h_value = ctx->sgemm_split;
   else if (!strcmp(key, "sgemm_split_kernel")) *h_value = ctx->sgemm_split_kernel;
+  else if (!strcmp(key, "sgemm_split_tn")) *h_value = ctx->sgemm_split_tn;
   else if (!strcmp(key, "agg_zs")) *h_value = ctx->agg_zs;
   else if (!strcmp(key, "capturing")) *h_value = ctx->capturing;  // a recording is open (gaib_capture_begin)
   else if (!strcmp(key, "agg_zs_wide")) *h_value = ctx->agg_zs_wide;
@@ -655,6 +657,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "sgemm_split_kernel")) {
     GAIB_CHECK(value == 0 || value == 1, "sgemm_split_kernel must be 0 or 1");
     ctx->sgemm_split_kernel = (int)value;
+  } else if (!strcmp(key, "sgemm_split_tn")) {
+    GAIB_CHECK(value == 0 || value == 1, "sgemm_split_tn must be 0 (fp32 matrix cores) or 1 (covered weight gradients on exactly split bf16 planes)");
+    ctx->sgemm_split_tn = (int)value;
   } else if (!strcmp(key, "agg_zs")) {
     GAIB_CHECK(value == 0 || value == 1, "agg_zs must be 0 (dense gradient tables) or 1 (zero-suppressed)");
     ctx->agg_zs = (int)value;

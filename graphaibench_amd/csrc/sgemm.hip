@@ -29,6 +29,9 @@ int gaib_sgemm_wide_tn_try(gaib_ctx* ctx, int64_t M, int64_t N, int64_t K, const
 // sgemm_split.hip: true when the option sgemm_split is on and gaib_sgemm_split covers the call (shape, pointers, no aliasing)
 bool gaib_sgemm_split_takes(gaib_ctx* ctx, int transA, int transB, int64_t N, int64_t K, const float* d_A, const float* d_B,
                             const float* d_C);
+// sgemm_split_tn.hip: true when the option sgemm_split_tn is on, `shape_side` holds and gaib_sgemm_split_tn covers the call
+bool gaib_sgemm_split_tn_takes(gaib_ctx* ctx, bool shape_side, int64_t M, int64_t N, int64_t K, const float* d_A, const float* d_G,
+                               const float* d_mask, const float* d_C);
 
 namespace {
 
@@ -1061,6 +1064,9 @@ extern "C" int gaib_sgemm_ex(gaib_ctx* ctx, int transA, int transB, int64_t M, i
   // option sgemm_split (default 0): a covered product with transA = 0 runs on the bf16 matrix cores, both operands split exactly
   if (gaib_sgemm_split_takes(ctx, transA, transB, N, K, d_A, d_B, d_C))
     return gaib_sgemm_split(ctx, transB, M, (int)N, (int)K, K, d_A, d_B, flags, d_C);
+  // option sgemm_split_tn (default 0): a covered weight gradient (transA = 1) likewise, the table rows being the reduction
+  if (gaib_sgemm_split_tn_takes(ctx, transA && !transB && !(flags & GAIB_RELU), M, N, K, d_A, d_B, nullptr, d_C))
+    return gaib_sgemm_split_tn(ctx, M, N, K, d_A, const_cast<float*>(d_B), nullptr, flags, d_C);
   {  // round 6: the products whose output or inner width is the class / input feature count (sgemm_skinny.hip)
     int handled = 0;
     GAIB_TRY(gaib_sgemm_skinny_try(ctx, transA, transB, M, N, K, d_A, d_B, flags, d_C, &handled));
@@ -1154,6 +1160,8 @@ extern "C" int gaib_sgemm_drelu(gaib_ctx* ctx, int64_t M, int64_t N, int64_t K, 
     return gaib_sgemm(ctx, 1, 0, M, N, K, d_A, d_G, accum, d_C);
   }
   GAIB_CHECK(d_C && d_A, "gaib_sgemm_drelu: A/C is NULL");
+  if (gaib_sgemm_split_tn_takes(ctx, true, M, N, K, d_A, d_G, d_mask, d_C))  // option sgemm_split_tn (default 0)
+    return gaib_sgemm_split_tn(ctx, M, N, K, d_A, d_G, d_mask, accum ? GAIB_ACCUMULATE : 0, d_C);
   if (ctx->sgemm_variant != 67) {  // round 6: 16 x 16 tiles, 7 of them for a 100-wide input, a deeper ring (sgemm_skinny.hip)
     int handled = 0;
     GAIB_TRY(gaib_sgemm_wide_tn_try(ctx, M, N, K, d_A, d_G, d_mask, accum ? GAIB_ACCUMULATE : 0, d_C, &handled));

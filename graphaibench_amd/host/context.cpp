@@ -70,15 +70,17 @@ void gpu_context::set(int device, void* hip_stream) {
   }
   // the dense self products of the SAGE layers under bf16 tables: fp32 rows (default) or the bf16 table with exactly split
   // weights (option gemm_bf16; without GAIB_AGG_DTYPE=bf16 there is no table and nothing changes); split: every fp32 product
-  // that gaib_sgemm_split covers on the bf16 matrix cores with both operands split exactly (option sgemm_split; gemm_bf16 stays 0)
+  // that gaib_sgemm_split covers on the bf16 matrix cores with both operands split exactly (option sgemm_split; gemm_bf16 stays 0);
+  // split_wgrad: that and the weight gradients gaib_sgemm_split_tn covers (option sgemm_split_tn)
   if (const char* d = getenv("GAIB_GEMM_DTYPE")) {
     const std::string dt(d);
-    if (dt != "fp32" && dt != "bf16" && dt != "split") {
-      fprintf(stderr, "GAIB_GEMM_DTYPE=%s: expected fp32, bf16 or split\n", d);
+    if (dt != "fp32" && dt != "bf16" && dt != "split" && dt != "split_wgrad") {
+      fprintf(stderr, "GAIB_GEMM_DTYPE=%s: expected fp32, bf16, split or split_wgrad\n", d);
       exit(EXIT_FAILURE);
     }
     check(gaib_set_option(g_ctx, "gemm_bf16", dt == "bf16" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
-    check(gaib_set_option(g_ctx, "sgemm_split", dt == "split" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
+    check(gaib_set_option(g_ctx, "sgemm_split", dt == "split" || dt == "split_wgrad" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
+    check(gaib_set_option(g_ctx, "sgemm_split_tn", dt == "split_wgrad" ? 1 : 0), "gaib_set_option (GAIB_GEMM_DTYPE)");
   }
   // relu-masked gradients of 256 columns gathered zero-suppressed on the K-slab route (option agg_zs_wide; off by default)
   if (const char* d = getenv("GAIB_AGG_ZS_WIDE")) {

@@ -242,7 +242,8 @@ struct Trainer {
                          : "fp32")
                 << "\n";
     if (aggregator::gemm_bf16_products() && root()) std::cout << "dense self products: bf16 tables\n";
-    if (gaib_host::option("sgemm_split") != 0 && root()) std::cout << "dense products: split bf16 planes\n";
+    if (gaib_host::option("sgemm_split") != 0 && root())
+      std::cout << (gaib_host::option("sgemm_split_tn") != 0 ? "dense products: split bf16 planes, weight gradients included\n" : "dense products: split bf16 planes\n");
     if (world == 1 && !bf16 && !fp8 && ARCH != gnn_arch::GAT && root())
       std::cout << "relu-masked gradients of 128 columns are gathered " << (aggregator::zs_tables() ? "zero-suppressed (agg_zs = 1)" : "dense (agg_zs = 0)") << "\n";
     if (world == 1 && !bf16 && !fp8 && ARCH != gnn_arch::GAT && root() && aggregator::zs_wide_tables())

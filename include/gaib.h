@@ -744,6 +744,29 @@ int gaib_sgemm_split(gaib_ctx* ctx, int transB, int64_t M, int N, int K, int64_t
 /* 1 when the call above would run (shape, stride and option "sgemm_split_kernel" only; no pointer, no launch), else 0 */
 int gaib_sgemm_split_cover(gaib_ctx* ctx, int transB, int N, int K, int64_t lda);
 
+/* ---- fp32 weight gradient on the bf16 matrix cores, both operands split exactly (sgemm_split_tn.hip) ----
+ * C[M x N] (=|+=) A^T . G for fp32 A [K x M] and G [K x N], both row-major and dense; flags = GAIB_ACCUMULATE or 0.
+ * d_mask != NULL ([K x N]): gaib_sgemm_drelu's contract -- d_G <- (d_mask > 0 ? d_G : +0.0) IN PLACE (a select: a NaN or an
+ * infinity behind the mask reaches neither G nor C), then the product of the masked G.  d_mask may be d_G itself.
+ * Both operands are split in registers, by truncation, into three bf16 planes whose sum is the value exactly (gaib_sgemm_split's
+ * rule and range: finite, |x| >= 2^-100); the nine plane products of every term are exact in fp32 and enter an fp32 accumulator
+ * of the bf16 matrix cores.  The table rows are dealt to gaib_sgemm_split_tn_parts workgroups in steps of 32 rows; with more than
+ * one, each writes a partial M x N slab to the context's workspace and the slabs are summed in fixed order (old C first, slabs
+ * ascending).  No atomics: two runs of one call give the same bits.  Not bit-identical to any fp32 call.  A non-finite element
+ * of A (or of the masked G) makes the outputs of its column non-finite; an infinity surfaces as NaN.
+ * Cover: 4 <= M, N <= 256, M % 4 == 0, N % 4 == 0, K >= 1; d_A, d_G and d_mask on 16-byte boundaries, d_C on a 4-byte one, C no
+ * alias of an operand, d_A != d_G.  Anything else, any other flag included: GAIB_ERR_UNSUPPORTED with nothing written -- use
+ * gaib_sgemm_ex (transA = 1) or gaib_sgemm_drelu.  The workspace grows as in those calls: inside gaib_capture_begin/end the call
+ * needs a workspace that is already large enough (run the sequence once before recording it).
+ * Profile: key "sgemm_split_tn", tag MxNxK; bytes 4 K (M + N) (+ 8 K N masked) + 4 M N (1 + accum), flops 2 M N K. */
+int gaib_sgemm_split_tn(gaib_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* d_A, float* d_G, const float* d_mask,
+                        int flags, float* d_C);
+/* 1 when the call above would run this shape (no pointer, no launch), else 0 */
+int gaib_sgemm_split_tn_cover(gaib_ctx* ctx, int64_t M, int64_t N);
+/* partial slabs summed into each output element of the call above: min(num_cus, ceil(K / 32) / 4), at least 1 (1: C is written
+ * directly, no workspace); 0 for a shape outside the cover */
+int gaib_sgemm_split_tn_parts(gaib_ctx* ctx, int64_t M, int64_t N, int64_t K);
+
 /* weight gradient with the layer's d_relu folded in (d_relu_gpu on grad_in followed by matmul(transA),
  * gcn_layer.cpp:33-52): d_G <- d_G where d_mask > 0 else 0 (IN PLACE, what d_relu_gpu leaves behind) and
  * C[M x N] (=|+=) A^T . G for A [K x M], G / mask [K x N].  One pass over G instead of two. */
@@ -1013,6 +1036,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * route: the layer library's matmul, the dense routes of the fused aggregation, GAT's X . W, the class products of partitions;
  * weight gradients (transA = 1) and uncovered shapes keep their routes; "sgemm_split_kernel" (default 1; readable): 0 =
  * gaib_sgemm_split refuses every call (GAIB_ERR_UNSUPPORTED), gaib_sgemm_split_cover says 0, and "sgemm_split" = 1 changes nothing;
+ * "sgemm_split_tn" (default 0; readable): 1 = gaib_sgemm_ex and gaib_sgemm hand a weight gradient (transA = 1, transB = 0, no
+ * GAIB_RELU) that gaib_sgemm_split_tn covers to it before any other route, and gaib_sgemm_drelu its masked kernel's calls; inside a
+ * capture whose workspace would have to grow the fp32 route runs; "sgemm_split" keeps its meaning (transA = 0 only);
  * "gat_bf16" (default 0): 1 = the layer library's GAT aggregation casts h (forward) and grad (backward) into bf16 buffers of its
  * own and runs gaib_gat_forward_fused_bf16 / gaib_gat_backward_fused_bf16 where the one-sweep kernels apply (whole graphs), and
  * gaib_gat_forward_fused_drop_bf16 / gaib_gat_backward_fused_drop_bf16 where attention dropout stays in the sweep ("gat_fused_drop"
@@ -1043,7 +1069,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sgemm_split", "sgemm_split_kernel", "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
+ * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -6,6 +6,12 @@ the other's by more than the two min - max spreads together.  The k
 the library's gfx950 code objects.  Fails without a GPU.
 
     python scripts/sgemm_split.py OUT.json [ROWS]
+
+--tn: the weight gradients instead -- gaib_sgemm_split_tn (C = A^T . G over ROWS table rows, plain and with gaib_sgemm_drelu's
+mask) against the fp32 route of the same call (gaib_sgemm_ex with transA = 1 / gaib_sgemm_drelu, option sgemm_split_tn off), and
+the SAGE 256 -> 256 and GCN 128 -> 128 layer steps under sgemm_split alone and with sgemm_split_tn as well.
+
+    python scripts/sgemm_split.py OUT.json [ROWS] --tn
 """
 import json
 import re
@@ -20,9 +26,12 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from graphaibench_amd import capi, layers as L, synth  # noqa: E402
 
-ROWS = int(sys.argv[2]) if len(sys.argv) > 2 else 2_449_029
+TN = "--tn" in sys.argv
+ARGV = [a for a in sys.argv if a != "--tn"]
+ROWS = int(ARGV[2]) if len(ARGV) > 2 else 2_449_029
 ITERS, WARM = 20, 3
 PAIRS = [(128, 128), (256, 256), (100, 128), (128, 256)]  # (K, N)
+TN_PAIRS = [(128, 128), (256, 256), (100, 256)]  # (M, N) of the weight gradient
 LLVM = Path("/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
@@ -58,7 +67,7 @@ def verdict(new, old):
     return "within the spread"
 
 
-def kernel_registers():
+def kernel_registers(which="sgemm_split_kernel"):
     """{kernel: dict(vgpr, agpr, vgpr_spill, sgpr_spill)} of the sgemm_split kernels: every offload bundle of libgaib_hip.so's
     .hip_fatbin section, its gfx950 code object, the notes; "not measured" where the llvm tools are absent"""
     tools = [LLVM / "llvm-objcopy", LLVM / "clang-offload-bundler", LLVM / "llvm-readelf"]
@@ -80,15 +89,75 @@ def kernel_registers():
             notes = subprocess.run([str(tools[2]), "--notes", str(co)], capture_output=True, text=True).stdout
             for k in re.findall(r"- \.agpr_count:.*?\.wavefront_size:", notes, re.S):
                 name = re.search(r"\.name:\s+(\S+)", k)
-                if name and "sgemm_split_kernel" in name.group(1):
+                if name and which in name.group(1):
                     num = {f: int(re.search(rf"\.{f}:\s+(\d+)", k).group(1)) for f in ("agpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count")}
                     found[name.group(1)] = dict(vgpr=num["vgpr_count"] - num["agpr_count"], agpr=num["agpr_count"], total=num["vgpr_count"],
                                                 vgpr_spill=num["vgpr_spill_count"], sgpr_spill=num["sgpr_spill_count"])
     return found or "not measured"
 
 
+def main_tn():
+    ctx = L.init(0)
+    rec = dict(rows=ROWS, iters=ITERS, kernels=kernel_registers("sgemm_split_tn_kernel"), stream_copy_gbs_before=ctx.probe_stream_copy(),
+               products=[], layers=[])
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for M, N in TN_PAIRS:
+        A = torch.randn(ROWS, M, device="cuda", generator=gen)
+        G = torch.randn(ROWS, N, device="cuda", generator=gen) * 0.05
+        mask = torch.sign(torch.randn(ROWS, N, device="cuda", generator=gen))
+        Cf, Cs = torch.zeros(M, N, device="cuda"), torch.zeros(M, N, device="cuda")
+        for masked in (False, True):  # (the masked call leaves G masked: every later call of either leg reads the same G)
+            if masked:
+                r = alternate(dict(fp32=lambda: ctx.sgemm_drelu(A, G, mask, Cf), split=lambda: ctx.sgemm_split_tn(A, G, Cs, mask=mask)))
+            else:
+                r = alternate(dict(fp32=lambda: ctx.sgemm(A, G, Cf, transA=True), split=lambda: ctx.sgemm_split_tn(A, G, Cs)))
+            by = 4.0 * ROWS * (M + N * (3 if masked else 1)) + 4.0 * M * N
+            row = dict(M=M, N=N, K=ROWS, form="masked" if masked else "plain", parts=ctx.sgemm_split_tn_parts(M, N, ROWS), **r,
+                       split_alg_gbs=by / r["split"]["median_ms"] / 1e6, split_useful_tflops=2.0 * ROWS * N * M / r["split"]["median_ms"] / 1e9,
+                       max_diff_rel=float((Cf - Cs).abs().max() / Cf.abs().max()), split_vs_fp32=verdict(r["split"], r["fp32"]))
+            print(json.dumps(row), flush=True)
+            rec["products"].append(row)
+        del A, G, mask
+        torch.cuda.empty_cache()
+    sg = synth.make("ogbn-products", device="cuda", scale=ROWS / 2_449_029)
+    g = ctx.graph(sg.rowptr, sg.colidx)
+    ctx.sync()
+    nv = g.nv
+    lg = L.LGraph.adopt(g)
+    opt = L.adam(0.01)
+    for kind, d, name in ((L.SAGE, 256, "sage_256_256"), (L.GCN, 128, "gcn_128_128")):
+        layer = L.Layer(kind, 1, nv, d, d, lg, True)
+        layer.write(L.FEAT_IN, torch.randn(nv, d, device="cuda"))
+        layer.write(L.GRAD_IN, torch.randn(nv, d, device="cuda"))
+        out, gout = torch.empty(nv, d, device="cuda"), torch.empty(nv, d, device="cuda")
+
+        def step(on):
+            ctx.set_option("sgemm_split_tn", on)
+            layer.forward(out)
+            layer.backward(out, gout)
+            layer.update_weight(opt)
+
+        ctx.set_option("sgemm_split", 1)
+        try:
+            r = alternate(dict(split=lambda: step(0), split_wgrad=lambda: step(1)))
+        finally:
+            ctx.set_option("sgemm_split", 0)
+            ctx.set_option("sgemm_split_tn", 0)
+        rec["layers"].append(dict(layer=name, nv=nv, **r, split_wgrad_vs_split=verdict(r["split_wgrad"], r["split"])))
+        print(json.dumps(rec["layers"][-1]), flush=True)
+        layer.close()
+        del out, gout
+        torch.cuda.empty_cache()
+    rec["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    L.adam_free(opt)
+    Path(ARGV[1]).parent.mkdir(parents=True, exist_ok=True)
+    Path(ARGV[1]).write_text(json.dumps(rec, indent=1) + "\n")
+
+
 def main():
     assert torch.cuda.is_available(), "this measurement needs the GPU"
+    if TN:
+        return main_tn()
     ctx = L.init(0)
     rec = dict(rows=ROWS, iters=ITERS, kernels=kernel_registers(), stream_copy_gbs_before=ctx.probe_stream_copy(), products=[], layers=[])
     gen = torch.Generator(device="cuda").manual_seed(1)
@@ -137,8 +206,8 @@ def main():
         torch.cuda.empty_cache()
     rec["stream_copy_gbs_after"] = ctx.probe_stream_copy()
     L.adam_free(opt)
-    Path(sys.argv[1]).parent.mkdir(parents=True, exist_ok=True)
-    Path(sys.argv[1]).write_text(json.dumps(rec, indent=1) + "\n")
+    Path(ARGV[1]).parent.mkdir(parents=True, exist_ok=True)
+    Path(ARGV[1]).write_text(json.dumps(rec, indent=1) + "\n")
 
 
 if __name__ == "__main__":
