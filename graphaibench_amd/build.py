@@ -21,7 +21,7 @@ INCLUDE = ROOT / "include"
 ORACLE = ROOT / "oracle"
 REFERENCE = Path("/root/reference")
 
-HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_fp8.hip", "spmm_gemm_fp8.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "sgemm_split.hip", "sgemm_split_tn.hip", "elementwise.hip", "probe.hip", "comm.hip"]
+HIP_SOURCES = ["runtime.hip", "graph.hip", "induce.hip", "spmm.hip", "spmm_part.hip", "spmm_part_bf16.hip", "spmm_gemm_bf16.hip", "spmm_fp8.hip", "spmm_gemm_fp8.hip", "spmm_gemm_zs.hip", "gat.hip", "gat_fused.hip", "gat_bf16.hip", "gat_head.hip", "sgemm.hip", "sgemm_skinny.hip", "gemm_bf16.hip", "sgemm_split.hip", "sgemm_split_tn.hip", "elementwise.hip", "probe.hip", "comm.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -36,9 +36,10 @@ HIPCC_FLAGS = [
     "-Werror=pass-failed",
 ]
 # per translation unit, on top of HIPCC_FLAGS: the register split of sgemm_split.hip and sgemm_split_tn.hip is scalar fp32
-# arithmetic by design (one subtraction per value and plane) -- the compiler forms no packed fp32 instructions there
+# arithmetic by design (one subtraction per value and plane) -- the compiler forms no packed fp32 instructions there; gat_head.hip:
+# its chains are scalar FMAs per lane (d4's), its per-edge quantities wave-uniform: nothing in it comes in pairs
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIPCC_EXTRA = {"sgemm_split.hip": _NO_PACKED_FP32, "sgemm_split_tn.hip": _NO_PACKED_FP32}
+HIPCC_EXTRA = {"sgemm_split.hip": _NO_PACKED_FP32, "sgemm_split_tn.hip": _NO_PACKED_FP32, "gat_head.hip": _NO_PACKED_FP32}
 
 
 def _hipcc() -> str:
@@ -65,7 +66,7 @@ def build_hip(force: bool = False) -> Path:
     LIB.mkdir(exist_ok=True)
     out = LIB / "libgaib_hip.so"
     hipcc = _hipcc()
-    headers = [CSRC / "common.h", CSRC / "spmm_core.h", CSRC / "spmm_kernels.h", CSRC / "gat_kernels.h", CSRC / "gat_fused_seq.h", CSRC / "split_planes.h", INCLUDE / "gaib.h"]
+    headers = [CSRC / "common.h", CSRC / "spmm_core.h", CSRC / "spmm_kernels.h", CSRC / "gat_kernels.h", CSRC / "gat_head_kernels.h", CSRC / "gat_fused_seq.h", CSRC / "split_planes.h", INCLUDE / "gaib.h"]
     objs, jobs = [], []
     for src in HIP_SOURCES:
         s = CSRC / src

@@ -117,6 +117,7 @@ SIGNATURES = {
     "gaib_gat_backward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_fused_slabs": (_i, [_i, _i, C.POINTER(C.c_int)]),
+    "gaib_gat_fused_head_cpl": (_i, [_i, _i]),
     "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
@@ -377,6 +378,12 @@ def gat_fused_slabs(length: int, heads: int) -> tuple[int, int]:
     w = C.c_int(0)
     S = load().gaib_gat_fused_slabs(length, heads, C.byref(w))
     return w.value, S
+
+
+def gat_fused_head_cpl(length: int, heads: int) -> int:
+    """the columns a lane owns in the one-sweep kernels for ONE head of 256 or 512 columns (context option gat_fused_head = 1):
+    4 for (256, 1), 8 for (512, 1), else 0"""
+    return load().gaib_gat_fused_head_cpl(length, heads)
 
 
 _lib = None

@@ -30,16 +30,28 @@
 //   _drop_win fp32; _drop_bf16, narrow    | <G,H,8,E,true,true>      | <G,H,U,true,E,true,true>
 //   any, wide, undropped                  | <G,H,8,E,false,true>/slab| <G,H,U,true,E> with ld = len
 //   any, wide, dropped                    | <G,H,8,E,true,true>/slab | <G,H,U,true,E,true,true>
+//   fused fp32, one head of 256 columns   | gat_head_fwd_chunk_kernel<4,8>  | gat_head_bwd_chunk_kernel<4,4>   (option gat_fused_head,
+//   fused fp32, one head of 512 columns   | gat_head_fwd_chunk_kernel<8,4>  | gat_head_bwd_chunk_kernel<8,2>    row statistics only)
 //
 // The narrow _drop_bf16 call is the WINDOW form with ld = len and the window (heads, 0) ON PURPOSE: it is what a dropped bf16 slab
 // runs, so bf16 tables have no <.., DROP> instantiation without WIDE / WIN, where fp32 keeps its own narrow _drop form.  Whether
 // the narrow fp32 calls could run the strided forms too is a speed question with its own measurement; nothing here decides it.
 // The helper kernels follow `strided` (slab and window calls): the WIDE rowdot, records, reduce and alpha_partial kernels there,
 // the plain ones in the narrow calls.  gat_bwd_pk and gat_interleave are read by the narrow undropped row-statistics calls only.
+// The single wide head (gat_head_route) is a sequence of its own below: kernels with another lane layout (gat_head_kernels.h,
+// instantiated by gat_head.hip) and reduce kernels to match, between the narrow calls' plain rowdot, record and alpha kernels.
 #pragma once
 #include <type_traits>
 
 #include "gat_kernels.h"
+
+// gat_head.hip: the sweeps for one head of 256 or 512 columns (cpl = gaib_gat_fused_head_cpl) with their per-row reductions
+int gat_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* h, int ld,
+                         const float* alpha_l, const float* alpha_r, float eps, int relu, float* out_partial, float* ms_partial,
+                         float* out, float* row_stats, int stats_ld);
+int gat_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* feat,
+                          const float* grad, int ld, const float* rec, int rec_ld, const float* alpha_l, const float* alpha_r,
+                          float eps, float* out_partial, float* rc_partial, float* grad_out, float* rs, float* cs);
 
 namespace {
 
@@ -156,6 +168,16 @@ int gat_wide_route(const gaib_ctx* ctx, int len, int heads, int* w) {
   return S;
 }
 
+// option gat_fused_head: the columns per lane (4, 8) of a single head of 256 or 512 columns on fp32 tables, else 0.  `other`: the
+// call is a _rect, _drop or window call, or a backward without row statistics -- those answer at these shapes as without the option
+int gat_head_route(const gaib_ctx* ctx, int len, int heads, bool other) {
+  return ctx->gat_fused_head == 1 && !other ? gaib_gat_fused_head_cpl(len, heads) : 0;
+}
+// the narrow calls' other conditions (gat_fused_applies on a whole graph) at a shape gat_head_route admits
+bool gat_head_applies(const gaib_graph* g, int knob, uintptr_t align_or) {
+  return g->nc == g->nv && g->ne > 0 && (align_or & 15) == 0 && knob != 0;
+}
+
 // four chunks per workgroup (0 on a rank whose rows have no edges: nothing to sweep); option gat_chunk_xcd: see the kernels' per_xcd
 void chunk_grid(const gaib_ctx* ctx, const gaib_graph* g, bool xcd_walk, unsigned* grid, int* per_xcd) {
   *grid = (unsigned)cdiv64(g->n_chunks, 4);
@@ -256,6 +278,22 @@ int gat_fwd_reduce(gaib_ctx* ctx, const gaib_graph* g, const GatFwd<E>& q, const
   return GAIB_OK;
 }
 
+// one head of 256 or 512 columns (cpl columns per lane): the narrow call's workspace at width len, sweep and row combine
+template <typename E>  // (E = float: a template so that the bf16 translation unit instantiates nothing of it)
+int gat_head_forward_seq(gaib_ctx* ctx, gaib_graph* g, const GatFwd<E>& a, int cpl) {
+  const uintptr_t align_or = (uintptr_t)a.h | (uintptr_t)a.out | (uintptr_t)a.row_stats | (uintptr_t)a.alpha_l | (uintptr_t)a.alpha_r;
+  if (!gat_head_applies(g, ctx->gat_fused_fwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
+  FwdWs ws;
+  GAIB_TRY(gat_forward_ws(ctx, g, a.len, 1, &ws));
+  ProfScope ps(ctx, "gat_fwd_fused", gat_prof_bytes_fwd(g, a.len, 1, 1), 4.0 * (double)g->ne * a.len);
+  unsigned grid;
+  int per_xcd;
+  chunk_grid(ctx, g, true, &grid, &per_xcd);
+  return gat_head_forward_run(ctx, g, cpl, grid, per_xcd, a.h, a.len, a.alpha_l, a.alpha_r, a.eps, a.relu, ws.out_partial,
+                              reinterpret_cast<float*>(ws.ms_partial), a.out, a.row_stats, 1);
+}
+
 // a public forward call: a.len / a.heads are the full row's
 template <typename E>
 int gat_forward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatFwd<E> a) {
@@ -270,6 +308,8 @@ int gat_forward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatFwd<E> a) {
   }
   GAIB_TRY(gat_check_ptrs(a));
   GAIB_HIP(hipSetDevice(ctx->device));
+  if constexpr (std::is_same<E, float>::value)
+    if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || a.drop)) return gat_head_forward_seq(ctx, g, a, cpl);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win) ? 1 : gat_wide_route(ctx, len, heads, &w);  // whole graphs only: _rect keeps its answer
   const int Hs = heads / S;
@@ -401,6 +441,25 @@ int gat_bwd_epilogue(gaib_ctx* ctx, const gaib_graph* g, const GatBwd<E>& q, con
   return launch_alpha_grads<E, WIDE>(ctx, g->nv, q.len, q.heads, q.feat, ws.rs, ws.cs, ws.partial, q.alpha_lgrad, q.alpha_rgrad, q.ld);
 }
 
+// one head of 256 or 512 columns, from the row statistics: the narrow call's workspace, rowdot, records and alpha reduction at
+// width len around the sweep and row sums of gat_head.hip
+template <typename E>  // (E = float, as the forward's)
+int gat_head_backward_seq(gaib_ctx* ctx, gaib_graph* g, const GatBwd<E>& a, int cpl) {
+  const uintptr_t align_or = (uintptr_t)a.feat | (uintptr_t)a.grad | (uintptr_t)a.row_stats | (uintptr_t)a.grad_out;
+  if (!gat_head_applies(g, ctx->gat_fused_bwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
+  BwdWs ws;
+  GAIB_TRY(gat_backward_ws(ctx, g, a.len, 1, true, 0, &ws));
+  ProfScope ps(ctx, "gat_bwd_fused", gat_prof_bytes_bwd(g, a.len, 1, 1), 8.0 * (double)g->ne * a.len);
+  unsigned grid;
+  int per_xcd;
+  chunk_grid(ctx, g, true, &grid, &per_xcd);
+  GAIB_TRY((gat_bwd_prologue<E, false>(ctx, g->nv, a.len, 1, a.len, 1, a.grad, a.fwd_out, a.row_stats, ws.rowdot, ws.rec)));
+  GAIB_TRY(gat_head_backward_run(ctx, g, cpl, grid, per_xcd, a.feat, a.grad, a.len, reinterpret_cast<const float*>(ws.rec), 1,
+                                 a.alpha_l, a.alpha_r, a.eps, ws.out_partial, ws.rc_partial, a.grad_out, ws.rs, ws.cs));
+  return launch_alpha_grads<E, false>(ctx, g->nv, a.len, 1, a.feat, ws.rs, ws.cs, ws.partial, a.alpha_lgrad, a.alpha_rgrad);
+}
+
 // a public backward call: a.len / a.heads are the full row's
 template <typename E>
 int gat_backward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatBwd<E> a) {
@@ -419,6 +478,8 @@ int gat_backward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatBwd<E> a) {
   GAIB_TRY(gat_check_ptrs(a));
   if (a.drop && g->nc != g->nv) return gat_refuse(who, len, heads);  // (no _rect form)
   GAIB_HIP(hipSetDevice(ctx->device));
+  if constexpr (fp32)
+    if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || a.drop || !a.row_stats)) return gat_head_backward_seq(ctx, g, a, cpl);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win || !a.row_stats) ? 1 : gat_wide_route(ctx, len, heads, &w);  // the row-statistics form only
   const int Hs = heads / S;

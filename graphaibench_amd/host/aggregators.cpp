@@ -563,6 +563,11 @@ void GAT_Aggregator::init(int l, int nv, int ne, float lr, float drop_rate) {
   d_norm_scores_t = gaib_host::dmalloc<float>(num_edges);
   epsilon = 0.2f;
   alpha_opt = new adam(lr);
+  if (wide_rows_expected()) {  // one head of 256 or 512 columns under option gat_fused_head: see set_num_heads()
+    float** arrays[] = {&d_norm_scores, &d_norm_scores_grad, &d_norm_scores_t, &d_temp_scores};
+    for (float** a : arrays) float_free_device(*a);
+    num_edges = 0;
+  }
 }
 
 // d_norm_scores (the softmax of this forward) -> p . mask . scale in a buffer of its own: backward needs both the
@@ -653,6 +658,8 @@ void GAT_Aggregator::set_num_heads(int h) {
 }
 
 bool GAT_Aggregator::wide_rows_expected() const {
+  // option gat_fused_head: a single head of 256 or 512 columns, without attention dropout (the _drop calls refuse the shape)
+  if (gaib_host::option("gat_fused_head") == 1 && attn_drop == 0.f && gaib_gat_fused_head_cpl(length, heads) > 0) return true;
   return gaib_host::option("gat_fused_wide") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
 }
 

@@ -131,6 +131,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gat_fused_wide", v), "gaib_set_option (GAIB_GAT_WIDE)");
   }
+  // GAT layers with ONE head of 256 or 512 columns (the reference's configuration at those hidden widths): the one-sweep kernels
+  // with the whole wave on one edge (option gat_fused_head; off by default)
+  if (const char* d = getenv("GAIB_GAT_HEAD_WIDE")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GAT_HEAD_WIDE=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gat_fused_head", v), "gaib_set_option (GAIB_GAT_HEAD_WIDE)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

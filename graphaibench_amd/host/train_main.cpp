@@ -534,6 +534,13 @@ struct Trainer {
         if (S >= 2 && (score_drop == 0.f || drop_sweep == 1) && world == 1) std::cout << "GAT wide rows: one sweep, " << S << " slabs of " << w << "\n";
         else std::cout << "GAT wide rows: staged\n";
       }
+      // option gat_fused_head (GAIB_GAT_HEAD_WIDE=1): a hidden layer of ONE head of 256 or 512 columns in the one-sweep kernels
+      // with the wave on one edge (whole graphs, no attention dropout), else staged
+      if (gaib_host::option("gat_fused_head") == 1 && root()) {
+        const char* hs = getenv("GAIB_GAT_HEADS");
+        const bool sweep = gaib_gat_fused_head_cpl(dim_hid, hs ? atoi(hs) : 1) > 0 && score_drop == 0.f && world == 1;
+        std::cout << "GAT single wide head: " << (sweep ? "one sweep" : "staged") << "\n";
+      }
     }
 #endif
     if (use_l2norm) l2 = new l2norm_layer(nv, dim_hid);

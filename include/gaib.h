@@ -375,6 +375,21 @@ int gaib_gat_forward_fused(gaib_ctx* ctx, gaib_graph* g, int len, int heads, con
  * there).  Not covered, today's behaviour at these shapes whatever the option says: the _rect calls, gaib_gat_score_signs, a
  * single head wider than 128 columns, the packed-math sweep. */
 int gaib_gat_fused_slabs(int len, int heads, int* width);
+/* ONE HEAD OF 256 OR 512 COLUMNS (option "gat_fused_head", default 0): the reference's single-head GAT at the hidden widths its
+ * scripts train with.  No column slab is an independent problem there (scores and backward dots run over the whole head), so these
+ * shapes have one-sweep kernels of their own with the whole wave on one edge per step (csrc/gat_head_kernels.h).
+ * gaib_gat_fused_head_cpl is the shape rule, a pure function (no context, no device): the columns a lane owns, 4 for (256, 1),
+ * 8 for (512, 1), else 0.  gaib_gat_fused_slabs is not concerned: it keeps answering 0 at these shapes.
+ * With the option at 1, gaib_gat_forward_fused and gaib_gat_backward_fused (row-statistics form: d_row_stats != NULL) accept the
+ * two shapes on square graphs, fp32 tables, under the narrow calls' other conditions (16-byte aligned buffers, "gat_fused_fwd" /
+ * "gat_fused_bwd" != 0, ne > 0; else GAIB_ERR_UNSUPPORTED with nothing touched); with the option at 0 they answer as they always
+ * did, whatever "gat_fused_wide" says.  Outputs and d_row_stats as at the narrow shapes (rows without an edge: zeros, statistics
+ * (-1e30, 0)); held to the fp64 reference by the narrow sweeps' bars, not bit-identical to any other path.  Deterministic.
+ * "gat_chunk_xcd" is honoured; "gat_bwd_pk", "gat_interleave" and "gat_fused_unroll" are ignored.  Profile: one record per call
+ * under "gat_fwd_fused" / "gat_bwd_fused" with the narrow byte formula at (len, 1).
+ * Not covered, today's answer at these shapes whatever the option says: the _drop, _bf16 and _rect calls, backward from the
+ * attention array (d_row_stats == NULL), rectangular graphs, slabs of wide heads (512 x 2, 1024 x 4). */
+int gaib_gat_fused_head_cpl(int len, int heads);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
  * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
@@ -1050,6 +1065,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "gat_fused_wide" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head
  * rows wider than 128 columns as column slabs of the one-sweep kernels (gaib_gat_fused_slabs); the layer library keeps attention
  * dropout in the sweep there only with "gat_fused_drop" = 1 as well; the _bf16 / _drop_bf16 calls ("gat_bf16") run the same slabs; partitions stay as they are;
+ * "gat_fused_head" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) run a single head
+ * of 256 or 512 columns in one-sweep kernels of its own (gaib_gat_fused_head_cpl); the layer library then holds no [ne][heads] array
+ * for such a layer without attention dropout; attention dropout, bf16 tables and partitions stay as they are;
  * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
  * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
  * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;
@@ -1069,7 +1087,8 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * environment or the communicator's default, clamped; "comm_reserve_cus_raw": what the caller set, -1 = unset),
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
- * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "drop_seed_dev" */
+ * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "gat_fused_head",
+ * "drop_seed_dev" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

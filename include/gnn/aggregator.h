@@ -218,6 +218,11 @@ class GAT_Aggregator : public aggregator {
   // the [ne][heads] arrays; grow_edge_arrays() allocates them for the staged piece that first needs them, apply_attn_dropout()
   // mask and dropped attention.  Attention dropout without "gat_fused_drop", bf16 tables and partitions stay as they are at
   // these widths.
+  // extension: ONE head of 256 or 512 columns in one-sweep kernels of its own (context option "gat_fused_head" = 1, or
+  // GAIB_GAT_HEAD_WIDE=1, set BEFORE the layer is built).  Again nothing changes in aggregate() / d_aggregate(): the two calls
+  // accept the shape.  wide_rows_expected() also holds with that option at a shape with gaib_gat_fused_head_cpl > 0 and no
+  // attention dropout; init() then drops the [ne] arrays it made for the single head a layer starts with.  Attention dropout,
+  // bf16 tables and partitions stay as they are at these widths.
   bool wide_rows_expected() const;
   void grow_edge_arrays(size_t ne);
   bool drop_fused_last = false;  // the last forward was the dropped one sweep under drop_seed_last
