@@ -118,12 +118,12 @@ struct gaib_ctx {
   int gat_fused_fwd;         // the one-sweep forward (scores + online softmax + aggregation): -1 = dense graphs, 0 never, 1 whenever the shape fits
   int gat_fused_unroll;      // gathers in flight per lane and table in the fused backward sweep: 4 (default; measured 10.7 vs 10.9 ms) or 8
   int gat_bwd_pk;            // one-sweep GAT backward: 1 = the packed-math kernel over the element-interleaved table (round 6), 0 (default) = the round-5 kernel
-  int gat_bf16;              // 1: the layer library's GAT aggregation runs its one-sweep forward and backward on bf16 copies of h and grad (gaib_gat_*_fused_bf16)
+  int gat_bf16;              // 1: the layer library's GAT aggregation runs its one-sweep forward and backward on bf16 copies of h and grad (gaib_gat_*_fused_bf16); read here by gat_head_route alone
   int gat_interleave;        // one-sweep GAT backward: 1 = gather from ONE interleaved [h | grad | records] row per vertex (built per call), 0 = three tables
-  int gat_fused_drop;        // 1: the layer library's GAT aggregation keeps the one sweep under attention dropout (gaib_gat_*_fused_drop), 0 (default) = staged
+  int gat_fused_drop;        // 1: the layer library's GAT aggregation keeps the one sweep under attention dropout (gaib_gat_*_fused_drop), 0 (default) = staged; read here by gat_head_route alone
   int drop_seed_dev;         // 1: the layer library's feature dropout and staged attention dropout read their mask seeds from device memory (gaib_dropout_dev), 0 (default) = by value
   int gat_fused_wide;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused and their _drop forms run multi-head rows wider than 128 columns as column slabs (gat_fused_seq.h), 0 (default) = GAIB_ERR_UNSUPPORTED there
-  int gat_fused_head;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused (row statistics) run ONE head of 256 or 512 columns in the one-sweep kernels of gat_head.hip (gaib_gat_fused_head_cpl), 0 (default) = GAIB_ERR_UNSUPPORTED there
+  int gat_fused_head;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused (row statistics) run ONE head of 256 or 512 columns in the one-sweep kernels of gat_head.hip (gaib_gat_fused_head_cpl), 0 (default) = GAIB_ERR_UNSUPPORTED there; the _drop calls with gat_fused_drop = 1 as well, the _bf16 calls with gat_bf16 = 1 as well, _drop_bf16 with all three
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort
   int sampler_device;        // read by the trainer: 1 = sampled subgraphs are induced on the device (gaib_graph_induce), 0 (default) = on the host

@@ -30,8 +30,17 @@
 //   _drop_win fp32; _drop_bf16, narrow    | <G,H,8,E,true,true>      | <G,H,U,true,E,true,true>
 //   any, wide, undropped                  | <G,H,8,E,false,true>/slab| <G,H,U,true,E> with ld = len
 //   any, wide, dropped                    | <G,H,8,E,true,true>/slab | <G,H,U,true,E,true,true>
-//   fused fp32, one head of 256 columns   | gat_head_fwd_chunk_kernel<4,8>  | gat_head_bwd_chunk_kernel<4,4>   (option gat_fused_head,
-//   fused fp32, one head of 512 columns   | gat_head_fwd_chunk_kernel<8,4>  | gat_head_bwd_chunk_kernel<8,2>    row statistics only)
+//
+// ONE HEAD OF 256 / 512 COLUMNS (option gat_fused_head; gat_head_fwd_chunk_kernel / gat_head_bwd_chunk_kernel<CPL, U, E, DROP>, row
+// statistics only; each cell: the instantiation at 256 columns, then at 512):
+//
+//   call                         | also needs         | forward sweep                    | backward sweep
+//   -----------------------------+--------------------+----------------------------------+-----------------------------------------
+//   fused fp32                   |                    | <4,8> <8,4>                      | <4,4> <8,2>
+//   _drop fp32                   | gat_fused_drop     | <4,8,float,true> <8,4,..>        | <4,4,float,true> <8,2,..>
+//   _bf16                        | gat_bf16           | <4,8,uint16_t> <8,4,..>          | <4,4,uint16_t> <8,2,..>
+//   _drop_bf16                   | both               | <4,8,uint16_t,true> <8,4,..>     | <4,4,uint16_t,true> <8,2,..>
+//   _drop_win, _rect, no stats   | refused in every setting, as without the option
 //
 // The narrow _drop_bf16 call is the WINDOW form with ld = len and the window (heads, 0) ON PURPOSE: it is what a dropped bf16 slab
 // runs, so bf16 tables have no <.., DROP> instantiation without WIDE / WIN, where fp32 keeps its own narrow _drop form.  Whether
@@ -45,13 +54,17 @@
 
 #include "gat_kernels.h"
 
-// gat_head.hip: the sweeps for one head of 256 or 512 columns (cpl = gaib_gat_fused_head_cpl) with their per-row reductions
-int gat_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* h, int ld,
+// gat_head.hip: the sweeps for one head of 256 or 512 columns (cpl = gaib_gat_fused_head_cpl) with their per-row reductions, on
+// tables of element type E (float, uint16_t: instantiated there and nowhere else); drop: NULL, or rate, scale and seed of the call
+// (its window fields are not read: one head); backward under dropout reads g->rev
+template <typename E>
+int gat_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const E* h, int ld,
                          const float* alpha_l, const float* alpha_r, float eps, int relu, float* out_partial, float* ms_partial,
-                         float* out, float* row_stats, int stats_ld);
-int gat_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* feat,
-                          const float* grad, int ld, const float* rec, int rec_ld, const float* alpha_l, const float* alpha_r,
-                          float eps, float* out_partial, float* rc_partial, float* grad_out, float* rs, float* cs);
+                         float* out, float* row_stats, int stats_ld, const DropWin* drop);
+template <typename E>
+int gat_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const E* feat, const E* grad,
+                          int ld, const float* rec, int rec_ld, const float* alpha_l, const float* alpha_r, float eps,
+                          float* out_partial, float* rc_partial, float* grad_out, float* rs, float* cs, const DropWin* drop);
 
 namespace {
 
@@ -64,13 +77,6 @@ __global__ void gat_rec_wide_kernel(int64_t n, int Hs, int stats_ld, const float
     rec[t] = f4{rowdot[t], st.x, st.y, 0.f};
   }
 }
-
-// attention dropout: rate, scale and seed of the call, and the sweep's window into the [ne][mask_heads] mask array
-struct DropWin {
-  float rate, scale;
-  uint64_t seed;
-  int mask_heads, mask_head0;
-};
 
 // the public calls' arguments, and -- with (len, heads) = (w, Hs), the pointers at the slab's first column / head -- one slab's.
 // ld / stats_ld: row strides of the caller's tables and of d_row_stats (float2 records); strided: the WIDE / WIN kernel forms.
@@ -168,10 +174,14 @@ int gat_wide_route(const gaib_ctx* ctx, int len, int heads, int* w) {
   return S;
 }
 
-// option gat_fused_head: the columns per lane (4, 8) of a single head of 256 or 512 columns on fp32 tables, else 0.  `other`: the
-// call is a _rect, _drop or window call, or a backward without row statistics -- those answer at these shapes as without the option
-int gat_head_route(const gaib_ctx* ctx, int len, int heads, bool other) {
-  return ctx->gat_fused_head == 1 && !other ? gaib_gat_fused_head_cpl(len, heads) : 0;
+// option gat_fused_head: the columns per lane (4, 8) of a single head of 256 or 512 columns, else 0.  The plain fp32 call needs
+// that option alone; a dropped call (_drop, _drop_bf16) option gat_fused_drop = 1 as well, a call on bf16 tables (_bf16,
+// _drop_bf16) option gat_bf16 = 1 as well -- the layer library's three switches composed, so with gat_fused_head alone those calls
+// answer as they did without it.  `other`: a _rect or window call, or a backward without row statistics -- those answer at these
+// shapes as without the option, whatever else is set
+int gat_head_route(const gaib_ctx* ctx, int len, int heads, bool other, bool drop, bool bf16) {
+  if (ctx->gat_fused_head != 1 || other || (drop && ctx->gat_fused_drop != 1) || (bf16 && ctx->gat_bf16 != 1)) return 0;
+  return gaib_gat_fused_head_cpl(len, heads);
 }
 // the narrow calls' other conditions (gat_fused_applies on a whole graph) at a shape gat_head_route admits
 bool gat_head_applies(const gaib_graph* g, int knob, uintptr_t align_or) {
@@ -278,11 +288,14 @@ int gat_fwd_reduce(gaib_ctx* ctx, const gaib_graph* g, const GatFwd<E>& q, const
   return GAIB_OK;
 }
 
-// one head of 256 or 512 columns (cpl columns per lane): the narrow call's workspace at width len, sweep and row combine
-template <typename E>  // (E = float: a template so that the bf16 translation unit instantiates nothing of it)
+// one head of 256 or 512 columns (cpl columns per lane): the narrow call's workspace at width len, sweep and row combine.  The
+// kernels live in gat_head.hip for both element types; under dropout the reverse-edge permutation is made here too (not read:
+// forward and backward must decide alike)
+template <typename E>
 int gat_head_forward_seq(gaib_ctx* ctx, gaib_graph* g, const GatFwd<E>& a, int cpl) {
-  const uintptr_t align_or = (uintptr_t)a.h | (uintptr_t)a.out | (uintptr_t)a.row_stats | (uintptr_t)a.alpha_l | (uintptr_t)a.alpha_r;
+  const uintptr_t align_or = table_align(a.h) | (uintptr_t)a.out | (uintptr_t)a.row_stats | (uintptr_t)a.alpha_l | (uintptr_t)a.alpha_r;
   if (!gat_head_applies(g, ctx->gat_fused_fwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  if (a.drop) GAIB_TRY(gaib_graph_ensure_rev(ctx, g));
   GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
   FwdWs ws;
   GAIB_TRY(gat_forward_ws(ctx, g, a.len, 1, &ws));
@@ -290,8 +303,8 @@ int gat_head_forward_seq(gaib_ctx* ctx, gaib_graph* g, const GatFwd<E>& a, int c
   unsigned grid;
   int per_xcd;
   chunk_grid(ctx, g, true, &grid, &per_xcd);
-  return gat_head_forward_run(ctx, g, cpl, grid, per_xcd, a.h, a.len, a.alpha_l, a.alpha_r, a.eps, a.relu, ws.out_partial,
-                              reinterpret_cast<float*>(ws.ms_partial), a.out, a.row_stats, 1);
+  return gat_head_forward_run<E>(ctx, g, cpl, grid, per_xcd, a.h, a.len, a.alpha_l, a.alpha_r, a.eps, a.relu, ws.out_partial,
+                                 reinterpret_cast<float*>(ws.ms_partial), a.out, a.row_stats, 1, a.drop);
 }
 
 // a public forward call: a.len / a.heads are the full row's
@@ -308,8 +321,8 @@ int gat_forward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatFwd<E> a) {
   }
   GAIB_TRY(gat_check_ptrs(a));
   GAIB_HIP(hipSetDevice(ctx->device));
-  if constexpr (std::is_same<E, float>::value)
-    if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || a.drop)) return gat_head_forward_seq(ctx, g, a, cpl);
+  if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win, a.drop != nullptr, !std::is_same<E, float>::value))
+    return gat_head_forward_seq(ctx, g, a, cpl);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win) ? 1 : gat_wide_route(ctx, len, heads, &w);  // whole graphs only: _rect keeps its answer
   const int Hs = heads / S;
@@ -443,10 +456,11 @@ int gat_bwd_epilogue(gaib_ctx* ctx, const gaib_graph* g, const GatBwd<E>& q, con
 
 // one head of 256 or 512 columns, from the row statistics: the narrow call's workspace, rowdot, records and alpha reduction at
 // width len around the sweep and row sums of gat_head.hip
-template <typename E>  // (E = float, as the forward's)
+template <typename E>
 int gat_head_backward_seq(gaib_ctx* ctx, gaib_graph* g, const GatBwd<E>& a, int cpl) {
-  const uintptr_t align_or = (uintptr_t)a.feat | (uintptr_t)a.grad | (uintptr_t)a.row_stats | (uintptr_t)a.grad_out;
+  const uintptr_t align_or = table_align(a.feat) | table_align(a.grad) | (uintptr_t)a.row_stats | (uintptr_t)a.grad_out;
   if (!gat_head_applies(g, ctx->gat_fused_bwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  if (a.drop) GAIB_TRY(gaib_graph_ensure_rev(ctx, g));  // the reverse edges' masks
   GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
   BwdWs ws;
   GAIB_TRY(gat_backward_ws(ctx, g, a.len, 1, true, 0, &ws));
@@ -455,8 +469,8 @@ int gat_head_backward_seq(gaib_ctx* ctx, gaib_graph* g, const GatBwd<E>& a, int 
   int per_xcd;
   chunk_grid(ctx, g, true, &grid, &per_xcd);
   GAIB_TRY((gat_bwd_prologue<E, false>(ctx, g->nv, a.len, 1, a.len, 1, a.grad, a.fwd_out, a.row_stats, ws.rowdot, ws.rec)));
-  GAIB_TRY(gat_head_backward_run(ctx, g, cpl, grid, per_xcd, a.feat, a.grad, a.len, reinterpret_cast<const float*>(ws.rec), 1,
-                                 a.alpha_l, a.alpha_r, a.eps, ws.out_partial, ws.rc_partial, a.grad_out, ws.rs, ws.cs));
+  GAIB_TRY(gat_head_backward_run<E>(ctx, g, cpl, grid, per_xcd, a.feat, a.grad, a.len, reinterpret_cast<const float*>(ws.rec), 1,
+                                    a.alpha_l, a.alpha_r, a.eps, ws.out_partial, ws.rc_partial, a.grad_out, ws.rs, ws.cs, a.drop));
   return launch_alpha_grads<E, false>(ctx, g->nv, a.len, 1, a.feat, ws.rs, ws.cs, ws.partial, a.alpha_lgrad, a.alpha_rgrad);
 }
 
@@ -478,8 +492,8 @@ int gat_backward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatBwd<E> a) {
   GAIB_TRY(gat_check_ptrs(a));
   if (a.drop && g->nc != g->nv) return gat_refuse(who, len, heads);  // (no _rect form)
   GAIB_HIP(hipSetDevice(ctx->device));
-  if constexpr (fp32)
-    if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || a.drop || !a.row_stats)) return gat_head_backward_seq(ctx, g, a, cpl);
+  if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || !a.row_stats, a.drop != nullptr, !fp32))
+    return gat_head_backward_seq(ctx, g, a, cpl);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win || !a.row_stats) ? 1 : gat_wide_route(ctx, len, heads, &w);  // the row-statistics form only
   const int Hs = heads / S;

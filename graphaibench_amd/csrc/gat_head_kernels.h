@@ -44,6 +44,28 @@ __device__ __forceinline__ HeadRow<Q> head_load(const float* row_lane_ptr) {
   for (int q = 0; q < Q; ++q) r.p[q] = *reinterpret_cast<const f4*>(row_lane_ptr + q * 256);
   return r;
 }
+// the same pieces AS LOADED from a table of element type E (Row4<E>::Raw: 16 bytes of fp32, 8 bytes of raw bf16 bits -- columns
+// q 256 + 4 lane are then one 8-byte load and a load instruction of the wave covers one contiguous 512 B): a gathered row waits
+// packed, half the registers per row in flight, and is widened exactly (Row4<E>::widen) where it is consumed, behind the batch's
+// sched_barrier.  For E = float both are the identity and the kernels are the fp32 kernels as they were.
+template <int Q, typename E>
+struct HeadRaw {
+  typename Row4<E>::Raw p[Q];
+};
+template <int Q, typename E>
+__device__ __forceinline__ HeadRaw<Q, E> head_load_raw(const E* row_lane_ptr) {
+  HeadRaw<Q, E> r;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) r.p[q] = load_row4(row_lane_ptr + q * 256);
+  return r;
+}
+template <int Q, typename E>
+__device__ __forceinline__ HeadRow<Q> head_widen(const HeadRaw<Q, E>& r) {
+  HeadRow<Q> w;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) w.p[q] = Row4<E>::widen(r.p[q]);
+  return w;
+}
 // <a, b> over this lane's columns: one FMA chain through the pieces (d4's order inside a piece)
 template <int Q>
 __device__ __forceinline__ float head_dot(const HeadRow<Q>& a, const HeadRow<Q>& b) {
@@ -147,12 +169,25 @@ __device__ __forceinline__ bool head_chunk(int64_t n_chunks, const uint32_t* chu
   return true;
 }
 
+// DROP: the masks of the chunk's 64 edges as one wave-uniform 64-bit word, bit t = step t.  With one head the mask of edge e is
+// element e of the [ne] array gaib_dropout fills under the same seed, u01(seed, e) > rate, and the wave is on one edge per step:
+// lane t hashes the index it is handed ONCE, ahead of the edge loop (the chunk's own edge eb + t; in backward also rev[eb + t]), and
+// a ballot leaves the 64 bits in a scalar pair -- lanes past the end of the chunk contribute 0.  In the loop the weight of step t
+// is a scalar bit test against a compile-time t and a select between scale and 0: one hash per lane and chunk, where
+// gat_drop_bits shares a head's steps among its lanes and ORs them together.
+__device__ __forceinline__ uint64_t head_drop_mask(int lane, int n, uint64_t index, uint64_t seed, float rate) {
+  return __ballot(lane < n && u01_of_key(u01_key(seed, index)) > rate);  // (the index in 64 bits, as gaib_dropout's)
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
-template <int CPL, int U>
+// E: the element type of feat.  DROP: out_i = sum_e p_e w_e h_c with w = mask . scale (head_drop_mask); the running sum, the maximum
+// and so the row statistics do not see the mask.  The three trailing arguments are the DROP form's.
+template <int CPL, int U, typename E = float, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_head_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                  const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                                 const float* feat, int ld, const float* alpha_l, const float* alpha_r,
-                                                                 float eps, float* out_partial, float2* ms_partial, int per_xcd) {
+                                                                 const E* feat, int ld, const float* alpha_l, const float* alpha_r,
+                                                                 float eps, float* out_partial, float2* ms_partial, int per_xcd,
+                                                                 float drop_rate = 0.0f, float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   static_assert((CPL == 4 || CPL == 8) && 64 % U == 0, "one head of 256 or 512 columns");
   constexpr int Q = CPL / 4, LEN = 64 * CPL;
   HeadChunk ck;
@@ -161,7 +196,10 @@ __global__ __launch_bounds__(256) void gat_head_fwd_chunk_kernel(int64_t n_chunk
   const int loff = 4 * lane;
   const int cl = (int)col[ck.eb + (lane < n ? lane : 0)];  // (lanes past the end: the chunk's first edge)
   const HeadRow<Q> ar = head_load<Q>(alpha_r + loff);
-  const double sl_i = head_sum64(head_dot64<Q>(head_load<Q>(alpha_l + loff), head_load<Q>(feat + ck.row * (int64_t)ld + loff)));
+  const double sl_i =
+      head_sum64(head_dot64<Q>(head_load<Q>(alpha_l + loff), head_widen<Q, E>(head_load_raw<Q, E>(feat + ck.row * (int64_t)ld + loff))));
+  uint64_t mb = 0;
+  if constexpr (DROP) mb = head_drop_mask(lane, n, (uint64_t)(ck.eb + lane), drop_seed, drop_rate);
   const double eps64 = (double)eps;
   double m = (double)GAT_NEG;  // (fp64: see head_dot64)
   float ssum = 0.f;
@@ -171,16 +209,17 @@ __global__ __launch_bounds__(256) void gat_head_fwd_chunk_kernel(int64_t n_chunk
 #pragma unroll
   for (int j = 0; j < 64; j += U) {
     if (j >= n) continue;  // (wave-uniform: no edge of the chunk is left)
-    HeadRow<Q> xh[U];
+    HeadRaw<Q, E> xh_raw[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane(cl, j + u);
-      xh[u] = head_load<Q>(feat + (int64_t)cj * ld + loff);
+      xh_raw[u] = head_load_raw<Q, E>(feat + (int64_t)cj * ld + loff);
     }
     __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first one is consumed
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const double sr_c = head_sum64(head_dot64<Q>(ar, xh[u]));
+      const HeadRow<Q> xh = head_widen<Q, E>(xh_raw[u]);
+      const double sr_c = head_sum64(head_dot64<Q>(ar, xh));
       if (j + u < n) {  // (wave-uniform; a step past the end looked at the chunk's first edge: nothing of it is added)
         const double t0 = sl_i + sr_c;
         const double t = t0 > 0.0 ? t0 : eps64 * t0;
@@ -189,10 +228,12 @@ __global__ __launch_bounds__(256) void gat_head_fwd_chunk_kernel(int64_t n_chunk
         const float ex = __expf(d > 0.f ? -d : d);
         const float sc = d > 0.f ? ex : 1.f, e = d > 0.f ? 1.f : ex;
         ssum = __builtin_fmaf(ssum, sc, e);
+        float ew = e;
+        if constexpr (DROP) ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);  // (a scalar bit test and select)
 #pragma unroll
         for (int q = 0; q < Q; ++q)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(e, xh[u].p[q][k], acc.p[q][k] * sc);
+          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(ew, xh.p[q][k], acc.p[q][k] * sc);
         m = d > 0.f ? t : m;
       }
     }
@@ -253,12 +294,21 @@ __global__ __launch_bounds__(256) void gat_head_fwd_reduce_kernel(int64_t nv, co
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------------
 // rec: (rowdot, row maximum, 1 / row sum, 0) per vertex (gat_rec_kernel), rows of rec_ld records
-template <int CPL, int U>
+// E: the element type of feat and grad.  DROP: the expressions of gat_bwd_fused_chunk_kernel<.., DROP = true> -- dp_e = w_e <grad_i,
+// h_c>, dp_r = w_r <grad_c, h_i>, out_i += p_r w_r grad_c with r = rev(e) -- under two masks, the chunk's edges' and their reverse
+// edges' (rev: one coalesced 256 B per chunk).  Where the reverse edge is dropped nothing of grad_c is used, so that step's grad
+// gather is REDIRECTED to the chunk's own row (a scalar select of the row id ahead of the load: a line that is resident instead
+// of one from HBM; the loads of a batch stay unconditional, the vmcnt waits exact) and dp_r and the weight of grad_c are SELECTED
+// to 0 on the bit -- no product with what the redirected load returned reaches a result.  The four trailing arguments are the
+// DROP form's.
+template <int CPL, int U, typename E = float, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_head_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                  const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                                 const float* feat, const float* grad, int ld, const f4* rec, int rec_ld,
+                                                                 const E* feat, const E* grad, int ld, const f4* rec, int rec_ld,
                                                                  const float* alpha_l, const float* alpha_r, float eps,
-                                                                 float* out_partial, float* rc_partial, int per_xcd) {
+                                                                 float* out_partial, float* rc_partial, int per_xcd,
+                                                                 const uint32_t* rev = nullptr, float drop_rate = 0.0f,
+                                                                 float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   static_assert((CPL == 4 || CPL == 8) && 64 % U == 0, "one head of 256 or 512 columns");
   constexpr int Q = CPL / 4, LEN = 64 * CPL;
   HeadChunk ck;
@@ -266,8 +316,13 @@ __global__ __launch_bounds__(256) void gat_head_bwd_chunk_kernel(int64_t n_chunk
   const int lane = threadIdx.x & 63, n = ck.n;
   const int loff = 4 * lane;
   const int cl = (int)col[ck.eb + (lane < n ? lane : 0)];  // (lanes past the end: the chunk's first edge)
-  const HeadRow<Q> gi = head_load<Q>(grad + ck.row * (int64_t)ld + loff);
-  const HeadRow<Q> hi = head_load<Q>(feat + ck.row * (int64_t)ld + loff);
+  const HeadRow<Q> gi = head_widen<Q, E>(head_load_raw<Q, E>(grad + ck.row * (int64_t)ld + loff));
+  const HeadRow<Q> hi = head_widen<Q, E>(head_load_raw<Q, E>(feat + ck.row * (int64_t)ld + loff));
+  uint64_t mb_e = 0, mb_r = 0;  // DROP: the masks of the chunk's edges and of their reverse edges
+  if constexpr (DROP) {
+    mb_e = head_drop_mask(lane, n, (uint64_t)(ck.eb + lane), drop_seed, drop_rate);
+    mb_r = head_drop_mask(lane, n, (uint64_t)rev[ck.eb + (lane < n ? lane : 0)], drop_seed, drop_rate);
+  }
   const HeadRow<Q> al = head_load<Q>(alpha_l + loff), ar = head_load<Q>(alpha_r + loff);
   // the per-vertex dots a_l.h_v, a_r.h_v are formed again from the gathered rows; only rowdot comes from a table
   float sl_i = head_dot<Q>(al, hi), sr_i = head_dot<Q>(ar, hi);
@@ -281,20 +336,29 @@ __global__ __launch_bounds__(256) void gat_head_bwd_chunk_kernel(int64_t n_chunk
 #pragma unroll
   for (int j = 0; j < 64; j += U) {
     if (j >= n) continue;  // (wave-uniform: no edge of the chunk is left)
-    HeadRow<Q> xg[U], xh[U];
+    HeadRaw<Q, E> xg_raw[U], xh_raw[U];
     f4 rc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane(cl, j + u);
-      xg[u] = head_load<Q>(grad + (int64_t)cj * ld + loff);
-      xh[u] = head_load<Q>(feat + (int64_t)cj * ld + loff);
+      uint32_t cg = cj;  // DROP: a dropped reverse edge gathers the chunk's own grad row (see above)
+      if constexpr (DROP) cg = ((mb_r >> (j + u)) & 1u) ? cj : (uint32_t)ck.row;
+      xg_raw[u] = head_load_raw<Q, E>(grad + (int64_t)cg * ld + loff);
+      xh_raw[u] = head_load_raw<Q, E>(feat + (int64_t)cj * ld + loff);
       rc[u] = rec[(int64_t)cj * rec_ld];
     }
     __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first one is consumed
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      float dpe = head_dot<Q>(gi, xh[u]), dpr = head_dot<Q>(xg[u], hi), sl_c = head_dot<Q>(al, xh[u]), sr_c = head_dot<Q>(ar, xh[u]);
+      const HeadRow<Q> xg = head_widen<Q, E>(xg_raw[u]), xh = head_widen<Q, E>(xh_raw[u]);
+      float dpe = head_dot<Q>(gi, xh), dpr = head_dot<Q>(xg, hi), sl_c = head_dot<Q>(al, xh), sr_c = head_dot<Q>(ar, xh);
       head_sum4(dpe, dpr, sl_c, sr_c);
+      bool keep_r = true;
+      if constexpr (DROP) {
+        keep_r = ((mb_r >> (j + u)) & 1u) != 0;
+        dpe *= ((mb_e >> (j + u)) & 1u) ? drop_scale : 0.0f;
+        dpr = keep_r ? dpr * drop_scale : 0.0f;
+      }
       const float t_e = sl_i + sr_c, t_r = sl_c + sr_i;  // pre-activation scores of (i -> c) and (c -> i)
       const float a = __expf((t_e > 0.0f ? t_e : eps * t_e) - m_i) * is_i;
       const float b = __expf((t_r > 0.0f ? t_r : eps * t_r) - rc[u][1]) * rc[u][2];
@@ -305,10 +369,20 @@ __global__ __launch_bounds__(256) void gat_head_bwd_chunk_kernel(int64_t n_chunk
       if (j + u < n) {  // (wave-uniform; a step past the end looked at the chunk's first edge: nothing of it is added)
         s_e += ge;
         s_r += gr;
+        if constexpr (DROP) {  // the gradient flows back along the DROPPED attention p_r w_r: nothing where the bit is 0
+          if (keep_r) {
+            const float bw = b * drop_scale;
 #pragma unroll
-        for (int q = 0; q < Q; ++q)
+            for (int q = 0; q < Q; ++q)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(b, xg[u].p[q][k], acc.p[q][k]);
+              for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(bw, xg.p[q][k], acc.p[q][k]);
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < Q; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(b, xg.p[q][k], acc.p[q][k]);
+        }
       }
     }
   }

@@ -12,6 +12,14 @@
 #pragma once
 #include "common.h"
 
+// attention dropout: rate, scale and seed of a call, and the sweep's window into the [ne][mask_heads] mask array.  Outside the
+// unnamed namespace: gat_head.hip's launch functions, called from other translation units, take it
+struct DropWin {
+  float rate, scale;
+  uint64_t seed;
+  int mask_heads, mask_head0;
+};
+
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));

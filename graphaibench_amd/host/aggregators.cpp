@@ -658,8 +658,10 @@ void GAT_Aggregator::set_num_heads(int h) {
 }
 
 bool GAT_Aggregator::wide_rows_expected() const {
-  // option gat_fused_head: a single head of 256 or 512 columns, without attention dropout (the _drop calls refuse the shape)
-  if (gaib_host::option("gat_fused_head") == 1 && attn_drop == 0.f && gaib_gat_fused_head_cpl(length, heads) > 0) return true;
+  // option gat_fused_head: a single head of 256 or 512 columns, without attention dropout or with it kept in the sweep
+  // (gat_fused_drop: the _drop calls take the shape only then)
+  if (gaib_host::option("gat_fused_head") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_head_cpl(length, heads) > 0)
+    return true;
   return gaib_host::option("gat_fused_wide") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
 }
 

@@ -535,11 +535,13 @@ struct Trainer {
         else std::cout << "GAT wide rows: staged\n";
       }
       // option gat_fused_head (GAIB_GAT_HEAD_WIDE=1): a hidden layer of ONE head of 256 or 512 columns in the one-sweep kernels
-      // with the wave on one edge (whole graphs, no attention dropout), else staged
+      // with the wave on one edge (whole graphs; under attention dropout only with option gat_fused_drop as well), else staged;
+      // the sweep gathers bf16 tables with GAIB_GAT_DTYPE=bf16 (option gat_bf16)
       if (gaib_host::option("gat_fused_head") == 1 && root()) {
         const char* hs = getenv("GAIB_GAT_HEADS");
-        const bool sweep = gaib_gat_fused_head_cpl(dim_hid, hs ? atoi(hs) : 1) > 0 && score_drop == 0.f && world == 1;
-        std::cout << "GAT single wide head: " << (sweep ? "one sweep" : "staged") << "\n";
+        const bool sweep = gaib_gat_fused_head_cpl(dim_hid, hs ? atoi(hs) : 1) > 0 && (score_drop == 0.f || drop_sweep == 1) && world == 1;
+        const bool bf16 = sweep && gaib_host::option("gat_bf16") == 1;
+        std::cout << "GAT single wide head: " << (sweep ? (bf16 ? "one sweep, bf16 tables" : "one sweep") : "staged") << "\n";
       }
     }
 #endif

@@ -387,7 +387,15 @@ int gaib_gat_fused_slabs(int len, int heads, int* width);
  * (-1e30, 0)); held to the fp64 reference by the narrow sweeps' bars, not bit-identical to any other path.  Deterministic.
  * "gat_chunk_xcd" is honoured; "gat_bwd_pk", "gat_interleave" and "gat_fused_unroll" are ignored.  Profile: one record per call
  * under "gat_fwd_fused" / "gat_bwd_fused" with the narrow byte formula at (len, 1).
- * Not covered, today's answer at these shapes whatever the option says: the _drop, _bf16 and _rect calls, backward from the
+ * The other calls compose the layer library's switches: gaib_gat_*_fused_drop take the two shapes with "gat_fused_drop" = 1 as
+ * well, gaib_gat_*_fused_bf16 with "gat_bf16" = 1 as well, gaib_gat_*_fused_drop_bf16 with all three; with "gat_fused_head" = 1
+ * alone they answer as without it.  bf16 tables: 8-byte aligned, a lane's four columns one 8-byte load, widened exactly -- every
+ * output has the BITS of the fp32 head call on the widened tables.  Attention dropout: the mask of edge e is element e of the
+ * [ne] array gaib_dropout fills under the same seed, formed inside the sweep (one hash per lane and 64-edge chunk, a wave
+ * ballot); d_row_stats has the undropped call's bits; rate 0 with scale 1 returns the undropped call's bits; backward reads the
+ * graph's reverse-edge permutation (a graph without one is refused by forward and backward alike), and a dropped reverse edge
+ * gathers no grad row.
+ * Not covered, today's answer at these shapes whatever the options say: the _drop_win and _rect calls, backward from the
  * attention array (d_row_stats == NULL), rectangular graphs, slabs of wide heads (512 x 2, 1024 x 4). */
 int gaib_gat_fused_head_cpl(int len, int heads);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
@@ -1067,7 +1075,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * dropout in the sweep there only with "gat_fused_drop" = 1 as well; the _bf16 / _drop_bf16 calls ("gat_bf16") run the same slabs; partitions stay as they are;
  * "gat_fused_head" (default 0; readable): 1 = gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) run a single head
  * of 256 or 512 columns in one-sweep kernels of its own (gaib_gat_fused_head_cpl); the layer library then holds no [ne][heads] array
- * for such a layer without attention dropout; attention dropout, bf16 tables and partitions stay as they are;
+ * for such a layer without attention dropout; with "gat_fused_drop" = 1 as well the _drop calls run those kernels and a layer under
+ * attention dropout holds neither that array nor mask nor dropped attention; with "gat_bf16" = 1 as well the _bf16 calls (with all
+ * three, the _drop_bf16 calls) run them on bf16 tables; partitions stay as they are;
  * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
  * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
  * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;

@@ -1,15 +1,20 @@
 """The one-sweep GAT for ONE head of 256 or 512 columns (option gat_fused_head) against the staged path.
 
 Graph: the reddit-shaped graph of bench.py --workload gat-reddit (synth.make("reddit", seed=7), self loops added).  Shapes:
-1 head x 256 and 1 head x 512.  Per shape ONE child process under its own `timeout`; inside it option 0 and option 1 alternate
-(iteration i runs both legs once, so drift of the box hits them alike), 20 timed iterations after warm-up, median (min - max) in
-ms, the stream-copy rate of the run beside them:
-  layer step  GAT layer D -> D with one head, no attention dropout, training forward + backward, one layer per setting
-  memory      device memory each setting holds after its first step: free memory before the layer is built and after the step
-              (as tests/test_gpu_lifecycle.py measures it), one layer per setting, built and released in turn
+1 head x 256 and 1 head x 512.  Per shape ONE child process under its own `timeout`; inside it the legs alternate (iteration i
+runs every leg once, so drift of the box hits them alike), 20 timed iterations after warm-up, median (min - max) in ms, the
+stream-copy rate of the run beside them:
+  layer step  GAT layer D -> D with one head, training forward + backward, one layer per leg
+  memory      device memory each leg holds after its first step: free memory before the layer is built and after the step
+              (as tests/test_gpu_lifecycle.py measures it), one layer per leg, built and released in turn
+The legs are settings of (gat_fused_head, gat_fused_drop, gat_bf16):
+  default       gat_fused_head_0 (0, 0, 0: staged) and gat_fused_head_1 (1, 0, 0), no attention dropout
+  --drop RATE   the layers drop attention at RATE: staged (0, 0, 0) against one_sweep (1, 1, 0); also the forward and the backward
+                call alone (gaib_gat_*_fused_drop at this shape) at rates 0.3 and 0.9 under "calls"
+  --dtype bf16  bf16 tables: staged (0, 0, 0) and one_sweep_fp32 (1, D, 0) against one_sweep_bf16 (1, D, 1), D = 1 with --drop
 A shape whose child fails or runs into its time limit ends the run: no further child is started.
 
-    python scripts/gat_head.py OUT.json [--iters 20] [--shapes 256x1,512x1] [--timeout 600]
+    python scripts/gat_head.py OUT.json [--iters 20] [--shapes 256x1,512x1] [--timeout 600] [--drop RATE] [--dtype bf16]
 """
 import argparse
 import json
@@ -22,8 +27,19 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "scripts"))
 
+KEYS = ("gat_fused_head", "gat_fused_drop", "gat_bf16")
 
-def child(shape, iters, out_path):
+
+def legs_of(drop, dtype):
+    d = 1 if drop > 0 else 0
+    if dtype == "bf16":
+        return {"staged": (0, 0, 0), "one_sweep_fp32": (1, d, 0), "one_sweep_bf16": (1, d, 1)}
+    if d:
+        return {"staged": (0, 0, 0), "one_sweep": (1, 1, 0)}
+    return {"gat_fused_head_0": (0, 0, 0), "gat_fused_head_1": (1, 0, 0)}
+
+
+def child(shape, iters, out_path, drop, dtype):
     import torch
 
     from bf16_gat import time_legs
@@ -36,27 +52,32 @@ def child(shape, iters, out_path):
     g0.close()
     nv, ne = g.nv, g.ne
     rp, ci = g.rowptr(), g.colidx()
-    g.close()
     D, H = (int(v) for v in shape.split("x"))
     cpl = capi.gat_fused_head_cpl(D, H)
     assert cpl > 0, (D, H)
-    r = dict(len=D, heads=H, columns_per_lane=cpl, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    legs = legs_of(drop, dtype)
+    r = dict(len=D, heads=H, columns_per_lane=cpl, nv=nv, ne=ne, iters=iters, score_drop=drop, dtype=dtype,
+             legs={k: dict(zip(KEYS, v)) for k, v in legs.items()}, stream_copy_gbs_before=ctx.probe_stream_copy())
     gen = torch.Generator(device="cuda").manual_seed(1)
     h = torch.randn(nv, D, device="cuda", generator=gen)
     grad = torch.randn(nv, D, device="cuda", generator=gen)
     lout, lgo = torch.empty(nv, D, device="cuda"), torch.empty(nv, D, device="cuda")
+
+    def set_options(values):
+        for k, v in zip(KEYS, values):
+            ctx.set_option(k, v)
 
     def free_bytes():
         L.sync()
         torch.cuda.synchronize()
         return torch.cuda.mem_get_info()[0]
 
-    def make_layer(option):
+    def make_layer(values):
         """(layer, its graph, bytes it holds after one training step)"""
-        ctx.set_option("gat_fused_head", option)
+        set_options(values)
         before = free_bytes()
         lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
-        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True)
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True, score_drop=drop)
         ld.set_heads(H)
         ld.write(L.FEAT_IN, h)
         ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
@@ -65,29 +86,42 @@ def child(shape, iters, out_path):
         ld.backward(lout, lgo)
         return ld, lg_graph, before - free_bytes()
 
-    def step(ld, option):
+    def step(ld, values):
         def run():
-            ctx.set_option("gat_fused_head", option)
+            set_options(values)
             ld.forward(lout)
             ld.backward(lout, lgo)
         return run
 
     # a throw-away layer first: the context's workspace and the allocator's caches reach their size before anything is measured
-    ld, lgr, _ = make_layer(0)
+    ld, lgr, _ = make_layer((0, 0, 0))
     ld.close()
     lgr.close()
     r["held_bytes"] = {}
-    for option in (0, 1):
-        ld, lgr, held = make_layer(option)
-        r["held_bytes"][f"gat_fused_head_{option}"] = held
+    for name, values in legs.items():
+        ld, lgr, held = make_layer(values)
+        r["held_bytes"][name] = held
         ld.close()
         lgr.close()
-    l0, g0_, _ = make_layer(0)
-    l1, g1_, _ = make_layer(1)
-    r["layer_step"] = time_legs({"gat_fused_head_0": step(l0, 0), "gat_fused_head_1": step(l1, 1)}, iters)
-    ctx.set_option("gat_fused_head", 0)
-    for x in (l0, l1, g0_, g1_):
-        x.close()
+    made = {name: make_layer(values) for name, values in legs.items()}
+    r["layer_step"] = time_legs({name: step(made[name][0], values) for name, values in legs.items()}, iters)
+    for ld, lgr, _ in made.values():
+        ld.close()
+        lgr.close()
+    if drop > 0:  # the two calls alone: what a dropped reverse edge's redirected gather is worth shows between the two rates
+        set_options((1, 1, 1 if dtype == "bf16" else 0))
+        sfx = "_bf16" if dtype == "bf16" else ""
+        th, tg = (h.to(torch.bfloat16), grad.to(torch.bfloat16)) if dtype == "bf16" else (h, grad)
+        al, ar = (0.05 * torch.randn(D, device="cuda", generator=gen) for _ in range(2))
+        stats, lg_, rg_ = torch.empty(nv, H, 2, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
+        fwd, bwd = getattr(ctx, "gat_forward_fused_drop" + sfx), getattr(ctx, "gat_backward_fused_drop" + sfx)
+        calls = {}
+        for rate in (0.3, 0.9):
+            calls[f"forward_{rate}"] = lambda rate=rate: fwd(g, th, al, ar, lout, stats, rate, 7, heads=H) or sys.exit("forward refused")
+            calls[f"backward_{rate}"] = lambda rate=rate: bwd(g, th, tg, lout, al, ar, lgo, lg_, rg_, stats, rate, 7, heads=H) or sys.exit("backward refused")
+        r["calls"] = time_legs(calls, iters)
+    set_options((0, 0, 0))
+    g.close()
     r["stream_copy_gbs_after"] = ctx.probe_stream_copy()
     Path(out_path).write_text(json.dumps(r) + "\n")
     print(json.dumps(r), flush=True)
@@ -99,18 +133,21 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default="256x1,512x1")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
+    ap.add_argument("--drop", type=float, default=0.0, help="attention dropout rate of the layers (0: none)")
+    ap.add_argument("--dtype", default="fp32", choices=("fp32", "bf16"), help="bf16: a leg with gat_bf16 = 1")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child(args.child, args.iters, args.out)
+        child(args.child, args.iters, args.out, args.drop, args.dtype)
         return
     rec = dict(what="GAT layer with ONE head of 256 / 512 columns: one-sweep kernels with the wave on one edge (gat_fused_head = 1) "
-                    "against the staged path (0, the baseline)", graph="reddit synth (seed 7) + self loops", shapes=[])
+                    "against the staged path (the baseline)", graph="reddit synth (seed 7) + self loops", score_drop=args.drop,
+               dtype=args.dtype, shapes=[])
     with tempfile.TemporaryDirectory() as tmp:
         for shape in args.shapes.split(","):
             part = Path(tmp) / f"{shape}.json"
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
-                   "--iters", str(args.iters)]
+                   "--iters", str(args.iters), "--drop", str(args.drop), "--dtype", args.dtype]
             rc = subprocess.run(cmd).returncode
             if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
                 rec["stopped"] = dict(shape=shape, exit_status=rc)
