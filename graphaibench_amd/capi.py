@@ -118,6 +118,8 @@ SIGNATURES = {
     "gaib_gat_forward_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_fused_slabs": (_i, [_i, _i, C.POINTER(C.c_int)]),
     "gaib_gat_fused_head_cpl": (_i, [_i, _i]),
+    "gaib_gatv2_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "gaib_gatv2_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
@@ -940,6 +942,25 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gat_backward_fused")
+        return True
+
+    def gatv2_forward(self, g, h, a, out, row_stats, eps: float = 0.2, heads: int = 1, relu: bool = False) -> bool:
+        """GATv2 in one sweep: scores a . leaky_relu(h_i + h_j) per head, edge softmax, out = act(P h); row_stats [nv, heads, 2] =
+        (row maximum, 1 / row sum).  False = outside the cover (GAIB_ERR_UNSUPPORTED, nothing touched)"""
+        rc = self.lib.gaib_gatv2_forward(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(a), eps, int(relu), _ptr(out), _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_forward")
+        return True
+
+    def gatv2_backward(self, g, feat, grad, fwd_out, a, row_stats, grad_out, a_grad, eps: float = 0.2, heads: int = 1) -> bool:
+        """the exact input gradient and a's gradient of gatv2_forward in one sweep (structurally symmetric graphs: else the
+        reverse-edge permutation's error is raised).  False = outside the cover (nothing touched)"""
+        rc = self.lib.gaib_gatv2_backward(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out), _ptr(a),
+                                          _ptr(row_stats), eps, _ptr(grad_out), _ptr(a_grad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_backward")
         return True
 
     def gat_forward_fused_bf16(self, g, h, alpha_l, alpha_r, out, row_stats, eps: float = 0.2, heads: int = 1,

@@ -554,7 +554,8 @@ void GAT_Aggregator::init(int l, int nv, int ne, float lr, float drop_rate) {
   d_alpha_lgrad = gaib_host::dmalloc<float>(l);
   d_alpha_rgrad = gaib_host::dmalloc<float>(l);
   copy_float_device(l, al.data(), d_alpha_l);
-  copy_float_device(l, ar.data(), d_alpha_r);
+  if (gat_v2_option()) GAIB_OR_DIE(gaib_fill_f32(C(), l, 0.f, d_alpha_r));  // GATv2 has one vector: a = alpha_l
+  else copy_float_device(l, ar.data(), d_alpha_r);
   GAIB_OR_DIE(gaib_fill_f32(C(), l, 0.f, d_alpha_lgrad));
   GAIB_OR_DIE(gaib_fill_f32(C(), l, 0.f, d_alpha_rgrad));
   d_temp_scores = gaib_host::dmalloc<float>(num_edges);
@@ -809,6 +810,20 @@ void GAT_Aggregator::d_aggregate_partition(int len, Graph& g, const float* grad_
 
 bool GAT_Aggregator::gat_fused_drop_option() { return gaib_host::option("gat_fused_drop") != 0; }
 bool GAT_Aggregator::gat_bf16_tables() { return gaib_host::option("gat_bf16") != 0; }
+bool GAT_Aggregator::gat_v2_option() { return gaib_host::option("gat_v2") != 0; }
+// GATv2 has no staged path to fall back to: what the two one-sweep calls do not cover is a configuration error
+void GAT_Aggregator::v2_check(int len, Graph& g) const {
+  int w = 0;
+  const char* why = NULL;
+  if (gaib_gat_fused_slabs(len, heads, &w) != 1 || w != len) why = "this shape";
+  else if (attn_drop > 0.f) why = "attention dropout (score_drop > 0)";
+  else if (g.gat_full_graph() || g.has_halo()) why = "a partitioned graph";
+  else if (gat_bf16_tables()) why = "gat_bf16 (GAIB_GAT_DTYPE=bf16)";
+  if (!why) return;
+  fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1) does not cover %s (len %d, heads %d): GATv2 runs rows of 32, 64 or 128 columns "
+          "with 1, 2, 4, 8 or 16 heads of at least 4 columns, whole graphs, fp32 tables, no attention dropout\n", why, len, heads);
+  exit(EXIT_FAILURE);
+}
 // bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32
 static void no_gat_bf16_partition() {
   fprintf(stderr, "GPU error: gat_bf16 (GAIB_GAT_DTYPE=bf16) on a partitioned GAT graph: the one-sweep kernels over bf16 tables "
@@ -825,6 +840,15 @@ const uint16_t* GAT_Aggregator::cast_hb16(size_t elems, const float* in) {
 
 void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
   count_edges(g);
+  if (gat_v2_option()) {  // GATv2: one sweep, row statistics only (of ITS scores: nothing of the static scores is valid after it)
+    v2_check(len, g);
+    grow(d_row_stats, stats_floats, (size_t)g.size() * heads * 2);
+    OpTimer t(OP_SPARSEMM);
+    GAIB_OR_DIE(gaib_gatv2_forward(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, out, d_row_stats));
+    fuse_relu = false;
+    stats_valid = dropped_last = drop_fused_last = fwd_bf16 = false;
+    return;
+  }
   if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
   if (g.gat_full_graph()) {
     aggregate_partition(len, g, in, out);
@@ -912,6 +936,23 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
 void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const float* grad_in,
                                  float* grad_out) {
   count_edges(g);
+  if (gat_v2_option()) {  // GATv2: the whole input gradient and a's gradient in one sweep (feat_in and grad_out alias: d_tbuf)
+    v2_check(len, g);
+    if (!fwd_out) {
+      fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1): backward needs the layer's forward output (use_forward_output_once)\n");
+      exit(EXIT_FAILURE);
+    }
+    OpTimer t(OP_ATTN);
+    const size_t need = (size_t)g.size() * len;
+    grow(d_tbuf, tbuf_floats, need);
+    GAIB_OR_DIE(gaib_gatv2_backward(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon, d_tbuf,
+                                    d_alpha_lgrad));
+    GAIB_OR_DIE(gaib_fill_f32(C(), length, 0.f, d_alpha_rgrad));
+    fwd_out = NULL;
+    fwd_out_given = false;
+    GAIB_OR_DIE(gaib_memcpy_d2d(C(), grad_out, d_tbuf, sizeof(float) * need));
+    return;
+  }
   if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
   if (g.gat_full_graph()) {
     d_aggregate_partition(len, g, grad_in, grad_out);
@@ -1020,5 +1061,5 @@ float* GAT_Aggregator::norm_scores_ptr() {
 
 void GAT_Aggregator::update_weights(optimizer*) {
   alpha_opt->update_gpu(length, d_alpha_lgrad, d_alpha_l);
-  alpha_opt->update_gpu(length, d_alpha_rgrad, d_alpha_r);
+  if (!gat_v2_option()) alpha_opt->update_gpu(length, d_alpha_rgrad, d_alpha_r);  // (GATv2: a alone; the second vector stays zero)
 }

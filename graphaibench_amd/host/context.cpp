@@ -141,6 +141,15 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gat_fused_head", v), "gaib_set_option (GAIB_GAT_HEAD_WIDE)");
   }
+  // GAT layers with GATv2 scores a . phi(h_i + h_j) in one-sweep kernels of their own (option gat_v2; off by default)
+  if (const char* d = getenv("GAIB_GAT_V2")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GAT_V2=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gat_v2", v), "gaib_set_option (GAIB_GAT_V2)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

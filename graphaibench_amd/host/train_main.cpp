@@ -210,6 +210,15 @@ struct Trainer {
       std::cerr << "GAIB_AGG_DTYPE=fp8 (agg_fp8) runs on one GPU only: fp8 feature tables have no halo exchange and no row-class kernels\n";
       exit(EXIT_FAILURE);
     }
+    // GATv2 scores (GAIB_GAT_V2=1, context option gat_v2) take whole graphs: refused on more than one rank before the communicator
+    // is built, like fp8 tables
+    if (ARCH == gnn_arch::GAT && gaib_host::option("gat_v2") == 1) {
+      if (env_int("GAIB_WORLD", "WORLD_SIZE", 1) > 1) {
+        std::cerr << "GAIB_GAT_V2=1 (gat_v2) runs on one GPU only: the one-sweep GATv2 kernels take whole graphs\n";
+        exit(EXIT_FAILURE);
+      }
+      std::cout << "GAT scores: v2, one sweep\n";
+    }
     init_comm();
     if (ARCH == gnn_arch::GAT) {
       // GAT's own tables: fp32, or bf16 with GAIB_GAT_DTYPE=bf16 (context option gat_bf16; whole graphs only)

@@ -398,6 +398,31 @@ int gaib_gat_fused_slabs(int len, int heads, int* width);
  * Not covered, today's answer at these shapes whatever the options say: the _drop_win and _rect calls, backward from the
  * attention array (d_row_stats == NULL), rectangular graphs, slabs of wide heads (512 x 2, 1024 x 4). */
 int gaib_gat_fused_head_cpl(int len, int heads);
+/* GATv2 (Brody, Alon, Yahav: dynamic attention) in one sweep each way.  The leaky relu phi(x) = x > 0 ? x : epsilon x sits INSIDE
+ * the dot product and one vector d_a [len] serves both ends, so the score is symmetric.  Head k owns the columns
+ * C_k = [k len / heads, (k + 1) len / heads); N(i) is row i of the CSR, self loops are ordinary edges.
+ *   forward:   s_ij^k = sum_{c in C_k} a_c phi(h_ic + h_jc)                 j in N(i)
+ *              p_ij^k = exp(s_ij^k - m_i^k) / l_i^k                         m = row maximum, l = sum_j exp(s - m)
+ *              d_out_ic = act(sum_j p_ij^k(c) h_jc)                         act = identity or relu (`relu`, as gaib_gat_forward_fused)
+ *              d_row_stats[i][k] = (m_i^k, 1 / l_i^k)                       [nv][heads][2]; a row without an edge: zeros, (-1e30, 0)
+ *   backward:  d_feat = h, d_grad = the gradient of d_out (already masked by the caller where relu was fused), d_fwd_out, d_a and
+ *              d_row_stats of that forward;
+ *              delta_i^k = sum_{c in C_k} g_ic out_ic       dp_ij^k = sum_{c in C_k} g_ic h_jc       ds_ij^k = p_ij^k (dp_ij^k - delta_i^k)
+ *              d_grad_out_jc = sum_{i in N(j)} [ p_ij^k g_ic + (ds_ij^k + ds_ji^k) a_c phi'(h_ic + h_jc) ]       k = k(c)
+ *              d_a_grad_c    = sum_j sum_{i in N(j)} ds_ji^k phi(h_jc + h_ic)
+ *              (a self loop (j, j) stands once in N(j) and counts 2 ds_jj: d s_jj / d h_j = 2 a phi'(2 h_j)).  The input gradient
+ *              is exact, both ends of the score path included, from ONE sweep over row j's own edges: the graph must be
+ *              structurally symmetric, else the call returns gaib_graph_ensure_rev's error.  d_grad_out and d_a_grad are overwritten.
+ * Nothing per edge is written or read in either call; no atomics; results are bit-identical from run to run.
+ * Cover: len 32, 64 or 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns (the shapes of gaib_gat_forward_fused), fp32.
+ * Refused with nothing touched -- GAIB_ERR_UNSUPPORTED: other shapes, a rectangular (partition) graph, tables of 4 GB or more;
+ * GAIB_ERR_INVALID: a buffer off a 16-byte boundary, d_grad_out aliasing an input, a NULL pointer.  There is no staged GATv2 to
+ * fall back to.  Option "gat_chunk_xcd" is honoured.  Profile: one record per call under "gatv2_fwd" / "gatv2_bwd". */
+int gaib_gatv2_forward(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_a, float epsilon, int relu,
+                       float* d_out, float* d_row_stats);
+int gaib_gatv2_backward(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
+                        const float* d_fwd_out, const float* d_a, const float* d_row_stats, float epsilon, float* d_grad_out,
+                        float* d_a_grad);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
  * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
@@ -1078,6 +1103,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * for such a layer without attention dropout; with "gat_fused_drop" = 1 as well the _drop calls run those kernels and a layer under
  * attention dropout holds neither that array nor mask nor dropped attention; with "gat_bf16" = 1 as well the _bf16 calls (with all
  * three, the _drop_bf16 calls) run them on bf16 tables; partitions stay as they are;
+ * "gat_v2" (default 0; readable): 1 = the layer library's GAT aggregation computes GATv2 (gaib_gatv2_forward / gaib_gatv2_backward):
+ * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover, attention dropout, a
+ * partitioned graph and "gat_bf16" = 1 are refused there with a message, not served by another path;
  * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
  * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
  * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;
@@ -1098,7 +1126,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
  * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "gat_fused_head",
- * "drop_seed_dev" */
+ * "drop_seed_dev", "gat_v2" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -224,6 +224,14 @@ class GAT_Aggregator : public aggregator {
   // attention dropout; init() then drops the [ne] arrays it made for the single head a layer starts with.  Attention dropout,
   // bf16 tables and partitions stay as they are at these widths.
   bool wide_rows_expected() const;
+  // extension: GATv2 scores s_ij = a . phi(h_i + h_j) (context option "gat_v2" = 1, or GAIB_GAT_V2=1; read per call).  aggregate()
+  // and d_aggregate() are gaib_gatv2_forward / gaib_gatv2_backward: d_alpha_l holds a, d_alpha_r and its gradient stay zero (init()
+  // under the option does not draw it) and update_weights() steps a alone.  Only the row statistics are kept; no [ne][heads] array
+  // is read (norm_scores_ptr() keeps serving the static scores' array, which is not this model's).  The option has NO staged
+  // form: a shape outside len 32 / 64 / 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns, attention dropout (score_drop > 0),
+  // a partitioned graph, "gat_bf16" = 1 and a backward without the layer's forward output end the process with a message.
+  static bool gat_v2_option();
+  void v2_check(int len, Graph& g) const;
   void grow_edge_arrays(size_t ne);
   bool drop_fused_last = false;  // the last forward was the dropped one sweep under drop_seed_last
   uint64_t drop_seed_last = 0;

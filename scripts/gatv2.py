@@ -1,0 +1,114 @@
+"""The one-sweep GATv2 (context option gat_v2) next to the one-sweep GAT of the same tree.
+
+Graph: the reddit-shaped graph of bench.py --workload gat-reddit (synth.make("reddit", seed=7), self loops added).  Shapes: 8 heads
+x 8 columns and 1 head x 64.  Per shape ONE child process under its own `timeout`; inside it the two legs alternate (iteration i
+runs both, so drift of the box hits them alike), 20 timed iterations after warm-up, median (min - max) in ms, the stream-copy
+rate of the run beside them:
+  layer step  GAT layer D -> D, training forward + backward, one layer per leg: gat_v2_0 (the v1 one-sweep kernels) and gat_v2_1
+  calls       the forward and the backward call alone: gaib_gat_forward_fused / gaib_gat_backward_fused (row statistics) and
+              gaib_gatv2_forward / gaib_gatv2_backward on the same tables
+The two legs compute different models: the comparison says what the dynamic score costs, not which path to take.
+A shape whose child fails or runs into its time limit ends the run: no further child is started.
+
+    python scripts/gatv2.py OUT.json [--iters 20] [--shapes 64x8,64x1] [--timeout 600]
+"""
+import argparse
+import json
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "scripts"))
+
+
+def child(shape, iters, out_path):
+    import torch
+
+    from bf16_gat import time_legs
+    from graphaibench_amd import layers as L, synth
+
+    ctx = L.init(0)
+    sg = synth.make("reddit", seed=7, device="cuda")
+    g0 = ctx.graph(sg.rowptr, sg.colidx)
+    g = g0.add_selfloop()
+    g0.close()
+    nv, ne = g.nv, g.ne
+    rp, ci = g.rowptr(), g.colidx()
+    D, H = (int(v) for v in shape.split("x"))
+    r = dict(len=D, heads=H, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    h = torch.randn(nv, D, device="cuda", generator=gen)
+    grad = torch.randn(nv, D, device="cuda", generator=gen)
+    lout, lgo = torch.empty(nv, D, device="cuda"), torch.empty(nv, D, device="cuda")
+
+    def make_layer(v2):
+        ctx.set_option("gat_v2", v2)
+        lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True)
+        ld.set_heads(H)
+        ld.write(L.FEAT_IN, h)
+        ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
+        ld.set_phase(0)
+        return ld, lg_graph
+
+    def step(ld, v2):
+        def run():
+            ctx.set_option("gat_v2", v2)
+            ld.forward(lout)
+            ld.backward(lout, lgo)
+        return run
+
+    made = {f"gat_v2_{v2}": (make_layer(v2), v2) for v2 in (0, 1)}
+    r["layer_step"] = time_legs({name: step(ld, v2) for name, ((ld, _), v2) in made.items()}, iters)
+    for (ld, lgr), _ in made.values():
+        ld.close()
+        lgr.close()
+    ctx.set_option("gat_v2", 0)
+    al, ar = (0.05 * torch.randn(D, device="cuda", generator=gen) for _ in range(2))
+    stats, lg_, rg_ = torch.empty(nv, H, 2, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
+    ok = lambda done: done or sys.exit("a call was refused")  # noqa: E731
+    r["calls"] = time_legs({
+        "v1_forward": lambda: ok(ctx.gat_forward_fused(g, h, al, ar, lout, stats, heads=H)),
+        "v2_forward": lambda: ok(ctx.gatv2_forward(g, h, al, lout, stats, heads=H)),
+        "v1_backward": lambda: ok(ctx.gat_backward_fused(g, h, grad, lout, al, ar, None, lgo, lg_, rg_, heads=H, row_stats=stats)),
+        "v2_backward": lambda: ok(ctx.gatv2_backward(g, h, grad, lout, al, stats, lgo, lg_, heads=H)),
+    }, iters)
+    g.close()
+    r["stream_copy_gbs_after"] = ctx.probe_stream_copy()
+    Path(out_path).write_text(json.dumps(r) + "\n")
+    print(json.dumps(r), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--shapes", default="64x8,64x1")
+    ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        child(args.child, args.iters, args.out)
+        return
+    rec = dict(what="GAT layer step and the two calls alone: GATv2 scores in one sweep (gat_v2 = 1) next to the one-sweep GAT "
+                    "(gat_v2 = 0) of the same tree", graph="reddit synth (seed 7) + self loops", shapes=[])
+    with tempfile.TemporaryDirectory() as tmp:
+        for shape in args.shapes.split(","):
+            part = Path(tmp) / f"{shape}.json"
+            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
+                   "--iters", str(args.iters)]
+            rc = subprocess.run(cmd).returncode
+            if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
+                rec["stopped"] = dict(shape=shape, exit_status=rc)
+                break
+            rec["shapes"].append(json.loads(part.read_text()))
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(rec, indent=1) + "\n")
+    sys.exit(1 if "stopped" in rec else 0)
+
+
+if __name__ == "__main__":
+    main()
