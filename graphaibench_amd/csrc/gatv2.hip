@@ -4,32 +4,158 @@
 //   backward:  rowdot_kernel, gat_rec_kernel (records (delta, m, 1 / l)), gatv2_bwd_chunk_kernel, gat_fused_reduce_kernel (the
 //              partial rows in chunk order), gatv2_agrad_strip_kernel, gatv2_agrad_final_kernel (a's gradient, two fixed levels)
 // Cover: gat_fused_shape(len, heads) on whole graphs, fp32 tables below 4 GB (the sweeps address a row by a 32-bit byte offset).
-// There is NO staged GATv2: outside the cover the calls return GAIB_ERR_UNSUPPORTED with nothing touched and the caller has to
-// say so.  Option gat_chunk_xcd is honoured.  Deterministic, no atomics.
+// With option gatv2_wide = 1 (gatv2_route) also
+//   * every multi-head row gaib_gat_fused_slabs cuts into S >= 2 column slabs of w columns and Hs = heads / S heads: the sequence
+//     above once per slab, on the column window [s w, (s + 1) w) and the head window [s Hs, (s + 1) Hs) of the caller's arrays IN
+//     PLACE (the <.., WIDE> sweeps and the WIDE rowdot, record and row-reduction kernels of gat_kernels.h / gat_fused_seq.h, row
+//     strides len and heads).  The workspace is at the slab's width and the next slab reuses it (same stream).  Heads are
+//     independent, and the chunk list, the grid and the strips of a's gradient follow from the graph alone: every output of slab s
+//     has the BITS of the narrow call at (w, Hs) on contiguous copies of its windows;
+//   * one head of 256 or 512 columns (gaib_gat_fused_head_cpl): the sweeps of gatv2_head.hip between the narrow call's rowdot,
+//     record and a-gradient kernels at (len, 1).
+// The narrow call launches what it launched without the option.  There is NO staged GATv2: outside the cover the calls return
+// GAIB_ERR_UNSUPPORTED with nothing touched and the caller has to say so.  Option gat_chunk_xcd is honoured.  Deterministic, no
+// atomics.
 #include "gat_fused_seq.h"
+#include "gatv2_head_kernels.h"
 #include "gatv2_kernels.h"
 
 namespace {
 
-// forward: 8 steps in flight (the v1 forward's); backward: 4 at every width (three gathers per step; 100 - 108 VGPRs, no spill,
-// four waves per SIMD -- the 128-column instance needed no lower unroll)
-#define GAIB_V2_FWD(GG, HH)                                                                                                    \
-  gatv2_fwd_chunk_kernel<GG, HH, 8><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
-                                                                   g->rowptr, g->colidx, d_h, d_a, eps, ws.out_partial,        \
-                                                                   ws.ms_partial, per_xcd)
-#define GAIB_V2_BWD(GG, HH)                                                                                                    \
-  gatv2_bwd_chunk_kernel<GG, HH, 4><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
-                                                                   g->rowptr, g->colidx, d_feat, d_grad, rec, d_a, eps,        \
-                                                                   out_partial, ag_partial, per_xcd)
+// how a call runs: S slabs of w columns and Hs heads (S = 1: the narrow call), or cpl != 0: one head of 64 cpl columns
+struct V2Route {
+  int S, w, Hs, cpl;
+};
 
 // what both calls refuse before they touch anything: 0 = go on
-int gatv2_check(const char* who, gaib_ctx* ctx, gaib_graph* g, int len, int heads, uintptr_t align_or) {
-  if (!gat_fused_shape(len, heads) || g->nc != g->nv || (uint64_t)g->nv * (uint64_t)len * 4u >= ((uint64_t)1 << 32)) {
-    gaib_set_error("%s: covers len 32, 64 or 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns on a whole graph over tables below "
-                   "4 GB (len %d, heads %d, %lld x %lld)", who, len, heads, (long long)g->nv, (long long)g->nc);
+int gatv2_route(const char* who, gaib_ctx* ctx, gaib_graph* g, int len, int heads, uintptr_t align_or, V2Route* r) {
+  *r = V2Route{1, len, heads, 0};
+  bool ok = gat_fused_shape(len, heads);
+  if (!ok && ctx->gatv2_wide == 1) {
+    int w = 0;
+    const int S = gaib_gat_fused_slabs(len, heads, &w);
+    if ((r->cpl = gaib_gat_fused_head_cpl(len, heads)) != 0) ok = true;
+    else if (S >= 2) *r = V2Route{S, w, heads / S, 0}, ok = true;
+  }
+  // (the sweeps' 32-bit byte offsets run over the caller's full rows: the bound is on nv * len, slabs or not)
+  if (!ok || g->nc != g->nv || (uint64_t)g->nv * (uint64_t)len * 4u >= ((uint64_t)1 << 32)) {
+    gaib_set_error("%s: covers len 32, 64 or 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with option gatv2_wide = 1 also "
+                   "column slabs of those shapes (gaib_gat_fused_slabs) and one head of 256 or 512 columns -- on a whole graph over "
+                   "tables below 4 GB (len %d, heads %d, %lld x %lld)", who, len, heads, (long long)g->nv, (long long)g->nc);
     return GAIB_ERR_UNSUPPORTED;
   }
   GAIB_CHECK((align_or & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  return GAIB_OK;
+}
+
+// profile bytes of S sweeps at (w, Hs); the column ids and the chunks' partials once per slab
+// forward: per edge the column id and one gathered row; per chunk the partial (acc, m, l) written and read; per row its own h, out and
+// the statistics.  flops: per edge and column z, phi, the score's fma, and the accumulator's
+double v2_bytes_fwd(const gaib_graph* g, int w, int Hs, int S) {
+  return S * ((double)g->ne * (4.0 + 4.0 * w) + (double)g->n_chunks * (4.0 * w + 8.0 * Hs) * 2 + (double)g->nv * (2 * 4.0 * w + 8.0 * Hs));
+}
+// backward: per edge the column id, two gathered rows and the 12 bytes of a record per head; per chunk the partial row written and
+// read; per row h, grad and the forward output read, grad_out written and 20 bytes per head of statistics and record; per workgroup
+// its a-gradient partial written and read.  flops: per edge and column the score (5), two dots (4), the three accumulators (6)
+double v2_bytes_bwd(const gaib_graph* g, int w, int Hs, int S, unsigned grid) {
+  return S * ((double)g->ne * (4.0 + 2 * 4.0 * w + 12.0 * Hs) + (double)g->n_chunks * 4.0 * w * 2 +
+              (double)g->nv * (4 * 4.0 * w + 20.0 * Hs) + (double)grid * 4.0 * w * 2);
+}
+
+// Steps in flight: forward 8 (the v1 forward's); backward 4 at every width (three gathers per step; 100 - 108 VGPRs, no spill,
+// four waves per SIMD -- the 128-column instance needed no lower unroll).
+// One forward sweep and its row combine at (len, heads); WIDE: on windows of rows of ld floats and stats_ld records
+template <bool WIDE>
+int v2_forward_sweep(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, int ld, int stats_ld, const float* d_h, const float* d_a,
+                     float eps, int relu, const FwdWs& ws, float* d_out, float* d_row_stats) {
+  unsigned grid;
+  int per_xcd;
+  chunk_grid(ctx, g, true, &grid, &per_xcd);
+#define GAIB_V2_FWD(GG, HH)                                                                                                          \
+  gatv2_fwd_chunk_kernel<GG, HH, 8, WIDE><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
+                                                                         g->rowptr, g->colidx, d_h, d_a, eps, ws.out_partial,        \
+                                                                         ws.ms_partial, per_xcd, ld)
+  if (grid > 0) {
+    GAIB_GAT_DISPATCH(GAIB_V2_FWD);
+    GAIB_LAUNCH_CHECK();
+  }
+#undef GAIB_V2_FWD
+  // (rows without an edge: zeros and statistics (-1e30, 0), as in v1)
+#define GAIB_V2_FR(GG)                                                                                                              \
+  gat_fwd_reduce_kernel<GG, WIDE><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, heads, g->chunk_start, ws.out_partial,      \
+                                                                           ws.ms_partial, relu ? 1 : 0, d_out,                     \
+                                                                           reinterpret_cast<float2*>(d_row_stats), ld, stats_ld)
+  if (len == 32) GAIB_V2_FR(8);
+  else if (len == 64) GAIB_V2_FR(16);
+  else GAIB_V2_FR(32);
+#undef GAIB_V2_FR
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+// the backward's workspace at (w, Hs): records [nv][Hs] x 16 B | rowdot [nv][Hs] | partial rows [n_chunks][w] | a-gradient partials
+// [grid][w] | their strips [nstrips][w]
+struct V2BwdWs {
+  f4* rec;
+  float *rowdot, *out_partial, *ag_partial, *ag_strip;
+  unsigned grid;
+  int per_xcd, nstrips;
+};
+int v2_backward_ws(gaib_ctx* ctx, const gaib_graph* g, int w, int Hs, V2BwdWs* ws) {
+  chunk_grid(ctx, g, true, &ws->grid, &ws->per_xcd);
+  const unsigned grid = ws->grid;
+  ws->nstrips = grid == 0 ? 0 : (int)(grid < 4096 ? cdiv64(grid, 4) : 1024);
+  const size_t n_v = up4((size_t)g->nv * Hs), n_op = up4((size_t)g->n_chunks * w);
+  const size_t n_ag = (size_t)grid * w, n_st = (size_t)ws->nstrips * w;
+  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (5 * n_v + n_op + n_ag + n_st)));
+  ws->rec = reinterpret_cast<f4*>(ctx->ws);
+  ws->rowdot = (float*)ctx->ws + 4 * n_v;
+  ws->out_partial = ws->rowdot + n_v;
+  ws->ag_partial = ws->out_partial + n_op;
+  ws->ag_strip = ws->ag_partial + n_ag;
+  return GAIB_OK;
+}
+
+// a's gradient from the workgroups' partial vectors [grid][len], two fixed levels
+int v2_agrad(gaib_ctx* ctx, const V2BwdWs& ws, int len, float* d_a_grad) {
+  if (ws.grid > 0) {
+    gatv2_agrad_strip_kernel<<<ws.nstrips, 256, 0, ctx->stream>>>((int64_t)ws.grid, len, ws.ag_partial, cdiv64(ws.grid, ws.nstrips),
+                                                                  ws.ag_strip);
+    GAIB_LAUNCH_CHECK();
+  }
+  gatv2_agrad_final_kernel<<<(unsigned)cdiv64(len, 4), 256, 0, ctx->stream>>>(ws.nstrips, len, ws.ag_strip, d_a_grad);
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+// one backward sweep with its prologue and reductions at (len, heads); WIDE: on windows of rows of ld floats and stats_ld records
+template <bool WIDE>
+int v2_backward_sweep(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, int ld, int stats_ld, const float* d_feat,
+                      const float* d_grad, const float* d_fwd_out, const float* d_a, const float* d_row_stats, float eps,
+                      const V2BwdWs& ws, float* d_grad_out, float* d_a_grad) {
+  GAIB_TRY((gat_bwd_prologue<float, WIDE>(ctx, g->nv, len, heads, ld, stats_ld, d_grad, d_fwd_out, d_row_stats, ws.rowdot, ws.rec)));
+  const unsigned grid = ws.grid;
+  const int per_xcd = ws.per_xcd;
+#define GAIB_V2_BWD(GG, HH)                                                                                                          \
+  gatv2_bwd_chunk_kernel<GG, HH, 4, WIDE><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
+                                                                         g->rowptr, g->colidx, d_feat, d_grad, ws.rec, d_a, eps,     \
+                                                                         ws.out_partial, ws.ag_partial, per_xcd, ld)
+  if (grid > 0) {
+    GAIB_GAT_DISPATCH(GAIB_V2_BWD);
+    GAIB_LAUNCH_CHECK();
+  }
+#undef GAIB_V2_BWD
+  GAIB_TRY(v2_agrad(ctx, ws, len, d_a_grad));
+  // the rows' partial sums in chunk order (H = 0: the kernel's row / column sums of v1 have no part here, nothing of them is read
+  // or written)
+#define GAIB_V2_RD(GG)                                                                                                               \
+  gat_fused_reduce_kernel<GG, WIDE><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, 0, g->chunk_start, ws.out_partial, nullptr, \
+                                                                             d_grad_out, nullptr, nullptr, ld)
+  if (len == 32) GAIB_V2_RD(8);
+  else if (len == 64) GAIB_V2_RD(16);
+  else GAIB_V2_RD(32);
+#undef GAIB_V2_RD
+  GAIB_LAUNCH_CHECK();
   return GAIB_OK;
 }
 
@@ -40,35 +166,25 @@ extern "C" int gaib_gatv2_forward(gaib_ctx* ctx, gaib_graph* g, int len, int hea
   const char* who = "gaib_gatv2_forward";
   GAIB_CHECK(ctx && g, "%s: NULL ctx/graph", who);
   GAIB_TRY(check_heads(who, len, heads));
-  GAIB_TRY(gatv2_check(who, ctx, g, len, heads, (uintptr_t)d_h | (uintptr_t)d_a | (uintptr_t)d_out | (uintptr_t)d_row_stats));
+  V2Route r;
+  GAIB_TRY(gatv2_route(who, ctx, g, len, heads, (uintptr_t)d_h | (uintptr_t)d_a | (uintptr_t)d_out | (uintptr_t)d_row_stats, &r));
   if (g->nv == 0) return GAIB_OK;
   GAIB_CHECK(d_h && d_a && d_out && d_row_stats && d_out != d_h, "%s: NULL or aliased pointer", who);
   GAIB_HIP(hipSetDevice(ctx->device));
   GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
   FwdWs ws;
-  GAIB_TRY(gat_forward_ws(ctx, g, len, heads, &ws));
-  // bytes: per edge the column id and one gathered row; per chunk the partial (acc, m, l) written and read; per row its own h,
-  // out and the statistics.  flops: per edge and column z, phi, the score's fma, and the accumulator's
-  ProfScope ps(ctx, "gatv2_fwd", (double)g->ne * (4.0 + 4.0 * len) + (double)g->n_chunks * (4.0 * len + 8.0 * heads) * 2 +
-                                     (double)g->nv * (2 * 4.0 * len + 8.0 * heads),
-               7.0 * (double)g->ne * len);
-  unsigned grid;
-  int per_xcd;
-  chunk_grid(ctx, g, true, &grid, &per_xcd);
-  if (grid > 0) {
-    GAIB_GAT_DISPATCH(GAIB_V2_FWD);
-    GAIB_LAUNCH_CHECK();
+  GAIB_TRY(gat_forward_ws(ctx, g, r.w, r.Hs, &ws));
+  ProfScope ps(ctx, "gatv2_fwd", v2_bytes_fwd(g, r.w, r.Hs, r.S), 7.0 * (double)g->ne * len);
+  if (r.cpl) {
+    unsigned grid;
+    int per_xcd;
+    chunk_grid(ctx, g, true, &grid, &per_xcd);
+    return gatv2_head_forward_run(ctx, g, r.cpl, grid, per_xcd, d_h, d_a, eps, relu, ws.out_partial, ws.ms_partial, d_out, d_row_stats);
   }
-  // (rows without an edge: zeros and statistics (-1e30, 0), as in v1)
-#define GAIB_V2_FR(GG)                                                                                                        \
-  gat_fwd_reduce_kernel<GG><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, heads, g->chunk_start, ws.out_partial,      \
-                                                                     ws.ms_partial, relu ? 1 : 0, d_out,                     \
-                                                                     reinterpret_cast<float2*>(d_row_stats))
-  if (len == 32) GAIB_V2_FR(8);
-  else if (len == 64) GAIB_V2_FR(16);
-  else GAIB_V2_FR(32);
-#undef GAIB_V2_FR
-  GAIB_LAUNCH_CHECK();
+  if (r.S == 1) return v2_forward_sweep<false>(ctx, g, len, heads, len, heads, d_h, d_a, eps, relu, ws, d_out, d_row_stats);
+  for (int s = 0; s < r.S; ++s)
+    GAIB_TRY(v2_forward_sweep<true>(ctx, g, r.w, r.Hs, len, heads, d_h + s * r.w, d_a + s * r.w, eps, relu, ws, d_out + s * r.w,
+                                    d_row_stats + 2 * s * r.Hs));
   return GAIB_OK;
 }
 
@@ -78,9 +194,11 @@ extern "C" int gaib_gatv2_backward(gaib_ctx* ctx, gaib_graph* g, int len, int he
   const char* who = "gaib_gatv2_backward";
   GAIB_CHECK(ctx && g, "%s: NULL ctx/graph", who);
   GAIB_TRY(check_heads(who, len, heads));
-  GAIB_TRY(gatv2_check(who, ctx, g, len, heads,
+  V2Route r;
+  GAIB_TRY(gatv2_route(who, ctx, g, len, heads,
                        (uintptr_t)d_feat | (uintptr_t)d_grad | (uintptr_t)d_fwd_out | (uintptr_t)d_a | (uintptr_t)d_row_stats |
-                           (uintptr_t)d_grad_out | (uintptr_t)d_a_grad));
+                           (uintptr_t)d_grad_out | (uintptr_t)d_a_grad,
+                       &r));
   GAIB_CHECK(d_a_grad, "%s: NULL pointer", who);
   if (g->nv == 0) return zero_alpha_grads(ctx, len, d_a_grad, nullptr);
   GAIB_CHECK(d_feat && d_grad && d_fwd_out && d_a && d_row_stats && d_grad_out, "%s: NULL pointer", who);
@@ -90,45 +208,22 @@ extern "C" int gaib_gatv2_backward(gaib_ctx* ctx, gaib_graph* g, int len, int he
   // an error, the permutation's own (the sweep does not read it)
   GAIB_TRY(gaib_graph_ensure_rev(ctx, g));
   GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
-  unsigned grid;
-  int per_xcd;
-  chunk_grid(ctx, g, true, &grid, &per_xcd);
-  const int nstrips = grid == 0 ? 0 : (int)(grid < 4096 ? cdiv64(grid, 4) : 1024);
-  // workspace: records [nv][heads] x 16 B | rowdot [nv][heads] | partial rows [n_chunks][len] | a-gradient partials [grid][len] |
-  // their strips [nstrips][len]
-  const size_t n_v = up4((size_t)g->nv * heads), n_op = up4((size_t)g->n_chunks * len);
-  const size_t n_ag = (size_t)grid * len, n_st = (size_t)nstrips * len;
-  GAIB_TRY(gaib_ws_reserve(ctx, sizeof(float) * (5 * n_v + n_op + n_ag + n_st)));
-  f4* rec = reinterpret_cast<f4*>(ctx->ws);
-  float* rowdot = (float*)ctx->ws + 4 * n_v;
-  float* out_partial = rowdot + n_v;
-  float* ag_partial = out_partial + n_op;
-  float* ag_strip = ag_partial + n_ag;
-  // bytes: per edge the column id, two gathered rows and the 12 bytes of a record per head; per chunk the partial row written and
-  // read; per row h, grad and the forward output read, grad_out written and 20 bytes per head of statistics and record; per
-  // workgroup its a-gradient partial written and read.  flops: per edge and column the score (5), two dots (4), the three
-  // accumulators (6)
-  ProfScope ps(ctx, "gatv2_bwd", (double)g->ne * (4.0 + 2 * 4.0 * len + 12.0 * heads) + (double)g->n_chunks * 4.0 * len * 2 +
-                                     (double)g->nv * (4 * 4.0 * len + 20.0 * heads) + (double)grid * 4.0 * len * 2,
-               15.0 * (double)g->ne * len);
-  GAIB_TRY((gat_bwd_prologue<float, false>(ctx, g->nv, len, heads, len, heads, d_grad, d_fwd_out, d_row_stats, rowdot, rec)));
-  if (grid > 0) {
-    GAIB_GAT_DISPATCH(GAIB_V2_BWD);
-    GAIB_LAUNCH_CHECK();
-    gatv2_agrad_strip_kernel<<<nstrips, 256, 0, ctx->stream>>>((int64_t)grid, len, ag_partial, cdiv64(grid, nstrips), ag_strip);
-    GAIB_LAUNCH_CHECK();
+  V2BwdWs ws;
+  GAIB_TRY(v2_backward_ws(ctx, g, r.w, r.Hs, &ws));
+  ProfScope ps(ctx, "gatv2_bwd", v2_bytes_bwd(g, r.w, r.Hs, r.S, ws.grid), 15.0 * (double)g->ne * len);
+  if (r.cpl) {
+    GAIB_TRY((gat_bwd_prologue<float, false>(ctx, g->nv, len, 1, len, 1, d_grad, d_fwd_out, d_row_stats, ws.rowdot, ws.rec)));
+    GAIB_TRY(gatv2_head_backward_run(ctx, g, r.cpl, ws.grid, ws.per_xcd, d_feat, d_grad, ws.rec, d_a, eps, ws.out_partial,
+                                     ws.ag_partial, d_grad_out));
+    return v2_agrad(ctx, ws, len, d_a_grad);
   }
-  gatv2_agrad_final_kernel<<<(unsigned)cdiv64(len, 4), 256, 0, ctx->stream>>>(nstrips, len, ag_strip, d_a_grad);
-  GAIB_LAUNCH_CHECK();
-  // the rows' partial sums in chunk order (H = 0: the kernel's row / column sums of v1 have no part here, nothing of them is read
-  // or written)
-#define GAIB_V2_RD(GG)                                                                                                              \
-  gat_fused_reduce_kernel<GG><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, len, 0, g->chunk_start, out_partial, nullptr, d_grad_out, \
-                                                                       nullptr, nullptr)
-  if (len == 32) GAIB_V2_RD(8);
-  else if (len == 64) GAIB_V2_RD(16);
-  else GAIB_V2_RD(32);
-#undef GAIB_V2_RD
-  GAIB_LAUNCH_CHECK();
+  if (r.S == 1)
+    return v2_backward_sweep<false>(ctx, g, len, heads, len, heads, d_feat, d_grad, d_fwd_out, d_a, d_row_stats, eps, ws, d_grad_out,
+                                    d_a_grad);
+  for (int s = 0; s < r.S; ++s) {
+    const int c = s * r.w;
+    GAIB_TRY(v2_backward_sweep<true>(ctx, g, r.w, r.Hs, len, heads, d_feat + c, d_grad + c, d_fwd_out + c, d_a + c,
+                                     d_row_stats + 2 * s * r.Hs, eps, ws, d_grad_out + c, d_a_grad + c));
+  }
   return GAIB_OK;
 }

@@ -1,0 +1,51 @@
+// gatv2_head.hip -- the one-sweep GATv2 for a single head of 256 or 512 columns (option "gatv2_wide"): the launches of
+// gatv2_head_kernels.h.  gaib_gatv2_forward / gaib_gatv2_backward (gatv2.hip) check the call, lay out the workspace as the narrow
+// call's at (len, 1) and run the narrow call's own rowdot, record and a-gradient kernels around the sweep.  Every GATv2 head kernel
+// is instantiated here and nowhere else.
+// Edges in flight per wave, from the register report: forward 8 at 256 columns and 4 at 512, backward 4 and 2 -- 32
+// row pieces of 16 bytes per lane in every case, the static-score head sweeps' values.
+#include "gatv2_head_kernels.h"
+
+// chunk sweep, then the per-row combine: out = act(P h), row_stats [nv][2] = (m, 1 / l)
+int gatv2_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* h, const float* a,
+                           float eps, int relu, float* out_partial, float2* ms_partial, float* out, float* row_stats) {
+#define GAIB_V2HF(CPL, U)                                                                                                            \
+  do {                                                                                                                               \
+    if (grid > 0) {                                                                                                                  \
+      gatv2_head_fwd_chunk_kernel<CPL, U><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
+                                                                         g->rowptr, g->colidx, h, a, eps, out_partial, ms_partial,   \
+                                                                         per_xcd);                                                   \
+      GAIB_LAUNCH_CHECK();                                                                                                           \
+    }                                                                                                                                \
+    gat_head_fwd_reduce_kernel<CPL><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, g->chunk_start, out_partial, ms_partial,         \
+                                                                             relu ? 1 : 0, out, 64 * CPL,                            \
+                                                                             reinterpret_cast<float2*>(row_stats), 1);               \
+  } while (0)
+  if (cpl == 4) GAIB_V2HF(4, 8);
+  else GAIB_V2HF(8, 4);
+#undef GAIB_V2HF
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}
+
+// chunk sweep over the records rec [nv], then the rows' sums in chunk order: grad_out; agrad_partial [grid][len] is left for the
+// caller's two-level sum
+int gatv2_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* feat,
+                            const float* grad, const f4* rec, const float* a, float eps, float* out_partial, float* agrad_partial,
+                            float* grad_out) {
+#define GAIB_V2HB(CPL, U)                                                                                                            \
+  do {                                                                                                                               \
+    if (grid > 0) {                                                                                                                  \
+      gatv2_head_bwd_chunk_kernel<CPL, U><<<grid, 256, 0, ctx->stream>>>(g->n_chunks, g->chunk_row, g->chunk_ebase, g->chunk_start,  \
+                                                                         g->rowptr, g->colidx, feat, grad, rec, a, eps, out_partial, \
+                                                                         agrad_partial, per_xcd);                                    \
+      GAIB_LAUNCH_CHECK();                                                                                                           \
+    }                                                                                                                                \
+    gatv2_head_rows_kernel<CPL><<<rowgrid(g->nv), 256, 0, ctx->stream>>>(g->nv, g->chunk_start, out_partial, grad_out);              \
+  } while (0)
+  if (cpl == 4) GAIB_V2HB(4, 4);
+  else GAIB_V2HB(8, 2);
+#undef GAIB_V2HB
+  GAIB_LAUNCH_CHECK();
+  return GAIB_OK;
+}

@@ -43,11 +43,14 @@ __device__ __forceinline__ f4 gatv2_row4(const char* tab, uint32_t v, uint32_t r
 // U edges.  The NG groups and then the row's chunks meet by the same rule; the partials (m, l) [slot][H] and acc [slot][len] have
 // gat_fwd_fused_chunk_kernel's format, so gat_fwd_reduce_kernel merges them in chunk order and writes out and row_stats.
 // Nothing per edge is written.
-template <int G, int H, int U>
+// WIDE: feat has rows of ld floats of which this launch sweeps the len = 4 G at `feat` (one column slab of a wider multi-head row,
+// option gatv2_wide); a is the slab's piece and the partials stay len wide.  A template flag with a trailing, defaulted argument read
+// only behind `WIDE ? ld : len`: the narrow instantiations compile to the instructions they had.
+template <int G, int H, int U, bool WIDE = false>
 __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                               const float* feat, const float* a, float eps, float* out_partial,
-                                                              float2* ms_partial, int per_xcd) {
+                                                              float2* ms_partial, int per_xcd, int ld = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -68,7 +71,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
   if constexpr (G == 32) cl1 = col[eb + (my_e1 < n ? my_e1 : 0)];
   const int coff = sl * 4, head = sl / LH;
   const char* tab = reinterpret_cast<const char*>(feat);
-  const uint32_t row_bytes = (uint32_t)len * 4u, lane_off = (uint32_t)coff * 4u;
+  // (WIDE: the FULL row's bytes -- v * row_bytes + lane_off is below nv * ld * 4, which the host holds under 4 GB)
+  const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * 4u, lane_off = (uint32_t)coff * 4u;
   const f4 hi = gatv2_row4(tab, (uint32_t)row, row_bytes, lane_off);
   const f4 a4 = *reinterpret_cast<const f4*>(a + coff);
   float m = GAT_NEG, l = 0.f;
@@ -130,11 +134,13 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
 // chunk order (gat_fused_reduce_kernel); a's gradient lives in four registers per lane across the chunk, meets over the lane
 // groups and the workgroup's four waves in a fixed order and leaves as ONE partial vector per workgroup (agrad_partial
 // [gridDim.x][len], summed by gatv2_agrad_strip_kernel / gatv2_agrad_final_kernel).  No atomics, nothing per edge is written.
-template <int G, int H, int U>
+// WIDE: feat and grad have rows of ld floats (see the forward); the records [nv][H] and both partials are the slab's own.
+template <int G, int H, int U, bool WIDE = false>
 __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                               const float* feat, const float* grad, const f4* rec, const float* a,
-                                                              float eps, float* out_partial, float* agrad_partial, int per_xcd) {
+                                                              float eps, float* out_partial, float* agrad_partial, int per_xcd,
+                                                              int ld = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
     const char* ftab = reinterpret_cast<const char*>(feat);
     const char* gtab = reinterpret_cast<const char*>(grad);
     const char* rtab = reinterpret_cast<const char*>(rec);
-    const uint32_t row_bytes = (uint32_t)len * 4u, lane_off = (uint32_t)coff * 4u;
+    const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * 4u, lane_off = (uint32_t)coff * 4u;
     const uint32_t rec_bytes = (uint32_t)H * 16u, rec_off = (uint32_t)head * 16u;
     const f4 hi = gatv2_row4(ftab, (uint32_t)row, row_bytes, lane_off);
     const f4 gi = gatv2_row4(gtab, (uint32_t)row, row_bytes, lane_off);
@@ -225,12 +231,21 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
 }
 
 // strip[b][c] = sum of partial[v][c] over the rows v of strip b, rows_per_block each: thread t owns column t % len of every
-// (256 / len)-th row, the 256 / len sub-sums meet in LDS in a fixed order (the pattern of alpha_partial_kernel)
+// (256 / len)-th row, the 256 / len sub-sums meet in LDS in a fixed order (the pattern of alpha_partial_kernel).  One head of 256 or
+// 512 columns: column passes of 256, thread t owns column pass * 256 + t of EVERY row of the strip, in row order
 __global__ __launch_bounds__(256) void gatv2_agrad_strip_kernel(int64_t n, int len, const float* partial, int64_t rows_per_block,
                                                                 float* strip) {
   __shared__ float sm[256];
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  if (len > 128) {  // (uniform over the grid: no thread of it reaches the barrier below)
+    for (int c = threadIdx.x; c < len; c += 256) {
+      float s = 0.f;
+      for (int64_t v = r0; v < r1; ++v) s += partial[v * len + c];
+      strip[(int64_t)blockIdx.x * len + c] = s;
+    }
+    return;
+  }
   const int rpp = 256 / len, tc = threadIdx.x % len, tr = threadIdx.x / len;  // (len <= 128: at least two rows per pass)
   float s = 0.f;
   for (int64_t v = r0 + tr; v < r1; v += rpp) s += partial[v * len + tc];

@@ -815,13 +815,17 @@ bool GAT_Aggregator::gat_v2_option() { return gaib_host::option("gat_v2") != 0; 
 void GAT_Aggregator::v2_check(int len, Graph& g) const {
   int w = 0;
   const char* why = NULL;
-  if (gaib_gat_fused_slabs(len, heads, &w) != 1 || w != len) why = "this shape";
+  const int S = gaib_gat_fused_slabs(len, heads, &w);
+  // option gatv2_wide: also column slabs of a multi-head row and one head of 256 or 512 columns
+  const bool wide = gaib_host::option("gatv2_wide") == 1 && (S >= 2 || gaib_gat_fused_head_cpl(len, heads) > 0);
+  if (!(S == 1 && w == len) && !wide) why = "this shape";
   else if (attn_drop > 0.f) why = "attention dropout (score_drop > 0)";
   else if (g.gat_full_graph() || g.has_halo()) why = "a partitioned graph";
   else if (gat_bf16_tables()) why = "gat_bf16 (GAIB_GAT_DTYPE=bf16)";
   if (!why) return;
   fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1) does not cover %s (len %d, heads %d): GATv2 runs rows of 32, 64 or 128 columns "
-          "with 1, 2, 4, 8 or 16 heads of at least 4 columns, whole graphs, fp32 tables, no attention dropout\n", why, len, heads);
+          "with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with gatv2_wide (GAIB_GATV2_WIDE=1) also column slabs of such rows and one "
+          "head of 256 or 512 columns --, whole graphs, fp32 tables, no attention dropout\n", why, len, heads);
   exit(EXIT_FAILURE);
 }
 // bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32

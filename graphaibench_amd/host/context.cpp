@@ -150,6 +150,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gat_v2", v), "gaib_set_option (GAIB_GAT_V2)");
   }
+  // GATv2 on rows wider than 128 columns: column slabs of multi-head rows and one head of 256 or 512 columns (option gatv2_wide;
+  // off by default)
+  if (const char* d = getenv("GAIB_GATV2_WIDE")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GATV2_WIDE=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gatv2_wide", v), "gaib_set_option (GAIB_GATV2_WIDE)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

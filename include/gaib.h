@@ -415,6 +415,11 @@ int gaib_gat_fused_head_cpl(int len, int heads);
  *              structurally symmetric, else the call returns gaib_graph_ensure_rev's error.  d_grad_out and d_a_grad are overwritten.
  * Nothing per edge is written or read in either call; no atomics; results are bit-identical from run to run.
  * Cover: len 32, 64 or 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns (the shapes of gaib_gat_forward_fused), fp32.
+ * With option "gatv2_wide" = 1 (default 0) also rows wider than 128 columns: every (len, heads) gaib_gat_fused_slabs cuts into
+ * S >= 2 column slabs -- (256, 8), (512, 8), (256, 64), (256, 2) ... -- as S sweeps on the column and head windows of the caller's
+ * arrays in place, every slab's outputs with the bits of the narrow call at (w, heads / S) on contiguous copies of its windows;
+ * and ONE head of 256 or 512 columns (gaib_gat_fused_head_cpl != 0) in sweeps of its own with the whole wave on one edge.  The
+ * 4 GB bound is on nv * len * 4, slabs or not.  (512, 2), (1024, 1), (384, 1) and their like stay refused.
  * Refused with nothing touched -- GAIB_ERR_UNSUPPORTED: other shapes, a rectangular (partition) graph, tables of 4 GB or more;
  * GAIB_ERR_INVALID: a buffer off a 16-byte boundary, d_grad_out aliasing an input, a NULL pointer.  There is no staged GATv2 to
  * fall back to.  Option "gat_chunk_xcd" is honoured.  Profile: one record per call under "gatv2_fwd" / "gatv2_bwd". */
@@ -1106,6 +1111,9 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "gat_v2" (default 0; readable): 1 = the layer library's GAT aggregation computes GATv2 (gaib_gatv2_forward / gaib_gatv2_backward):
  * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover, attention dropout, a
  * partitioned graph and "gat_bf16" = 1 are refused there with a message, not served by another path;
+ * "gatv2_wide" (default 0; readable): 1 = gaib_gatv2_forward / gaib_gatv2_backward also run multi-head rows wider than 128 columns
+ * as column slabs (gaib_gat_fused_slabs gives S >= 2) and a single head of 256 or 512 columns (gaib_gat_fused_head_cpl) in sweeps
+ * of its own; the layer library's "gat_v2" layers accept those shapes then; 0 = GAIB_ERR_UNSUPPORTED there, as before;
  * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
  * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
  * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;
@@ -1126,7 +1134,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
  * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "gat_fused_head",
- * "drop_seed_dev", "gat_v2" */
+ * "drop_seed_dev", "gat_v2", "gatv2_wide" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

@@ -230,6 +230,8 @@ class GAT_Aggregator : public aggregator {
   // is read (norm_scores_ptr() keeps serving the static scores' array, which is not this model's).  The option has NO staged
   // form: a shape outside len 32 / 64 / 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns, attention dropout (score_drop > 0),
   // a partitioned graph, "gat_bf16" = 1 and a backward without the layer's forward output end the process with a message.
+  // With context option "gatv2_wide" = 1 (GAIB_GATV2_WIDE=1) v2_check() also accepts what the two calls then cover: multi-head
+  // rows wider than 128 columns that gaib_gat_fused_slabs cuts into slabs, and one head of 256 or 512 columns.
   static bool gat_v2_option();
   void v2_check(int len, Graph& g) const;
   void grow_edge_arrays(size_t ne);

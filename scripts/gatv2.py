@@ -8,9 +8,12 @@ rate of the run beside them:
   calls       the forward and the backward call alone: gaib_gat_forward_fused / gaib_gat_backward_fused (row statistics) and
               gaib_gatv2_forward / gaib_gatv2_backward on the same tables
 The two legs compute different models: the comparison says what the dynamic score costs, not which path to take.
+Rows wider than 128 columns (256x1, 512x1, 256x8 = 8 heads x 32: DESIGN.md 3.3.6) run both legs on their opt-in one-sweep paths:
+gat_fused_head = gat_fused_wide = 1 for the static scores, gatv2_wide = 1 for GATv2, set for the whole child and recorded.
 A shape whose child fails or runs into its time limit ends the run: no further child is started.
 
     python scripts/gatv2.py OUT.json [--iters 20] [--shapes 64x8,64x1] [--timeout 600]
+    python scripts/gatv2.py OUT.json --shapes 256x1,512x1,256x8
 """
 import argparse
 import json
@@ -39,6 +42,10 @@ def child(shape, iters, out_path):
     rp, ci = g.rowptr(), g.colidx()
     D, H = (int(v) for v in shape.split("x"))
     r = dict(len=D, heads=H, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    if D > 128:  # the wide rows' one-sweep paths of both models, before a layer is built
+        r["options"] = dict(gat_fused_head=1, gat_fused_wide=1, gatv2_wide=1)
+        for k, v in r["options"].items():
+            ctx.set_option(k, v)
     gen = torch.Generator(device="cuda").manual_seed(1)
     h = torch.randn(nv, D, device="cuda", generator=gen)
     grad = torch.randn(nv, D, device="cuda", generator=gen)
