@@ -120,6 +120,8 @@ SIGNATURES = {
     "gaib_gat_fused_head_cpl": (_i, [_i, _i]),
     "gaib_gatv2_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gatv2_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "gaib_gatv2_forward_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
+    "gaib_gatv2_backward_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp]),
     "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
@@ -961,6 +963,37 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gatv2_backward")
+        return True
+
+    def gatv2_forward_drop(self, g, h, a, out, row_stats, rate: float, seed: int, scale=None, eps: float = 0.2, heads: int = 1,
+                           relu: bool = False) -> bool:
+        """gatv2_forward under attention dropout: the mask of (edge e, head k) is the one `dropout` draws for element
+        e * heads + k with the same seed; scale defaults to 1 / (1 - rate) in fp32; row_stats do not see the mask.
+        False = outside the cover (nothing touched)"""
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gatv2_forward_drop(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(a), eps, int(relu), rate, scale, seed,
+                                              _ptr(out), _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_forward_drop")
+        return True
+
+    def gatv2_backward_drop(self, g, feat, grad, fwd_out, a, row_stats, grad_out, a_grad, rate: float, seed: int, scale=None,
+                            eps: float = 0.2, heads: int = 1) -> bool:
+        """gatv2_backward through the masks of gatv2_forward_drop with the same rate and seed; fwd_out is that forward's
+        (dropped) output.  False = outside the cover (nothing touched)"""
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gatv2_backward_drop(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out), _ptr(a),
+                                               _ptr(row_stats), eps, rate, scale, seed, _ptr(grad_out), _ptr(a_grad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_backward_drop")
         return True
 
     def gat_forward_fused_bf16(self, g, h, alpha_l, alpha_r, out, row_stats, eps: float = 0.2, heads: int = 1,

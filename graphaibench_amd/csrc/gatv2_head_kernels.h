@@ -22,12 +22,14 @@
 
 // gatv2_head.hip: the sweeps for ONE head of 256 or 512 columns (cpl = gaib_gat_fused_head_cpl; gatv2_head_kernels.h) with their
 // per-row reductions.  forward: d_out and d_row_stats [nv][1][2]; backward: d_grad_out and the workgroups' partial vectors of a's
-// gradient, agrad_partial [grid][len], for gatv2_agrad_strip_kernel
+// gradient, agrad_partial [grid][len], for gatv2_agrad_strip_kernel.  drop: NULL, or rate, scale and seed of the call (its window
+// fields are not read: one head); backward under dropout reads g->rev
 int gatv2_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* h, const float* a,
-                           float eps, int relu, float* out_partial, float2* ms_partial, float* out, float* row_stats);
+                           float eps, int relu, float* out_partial, float2* ms_partial, float* out, float* row_stats,
+                           const DropWin* drop);
 int gatv2_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* feat,
                             const float* grad, const f4* rec, const float* a, float eps, float* out_partial, float* agrad_partial,
-                            float* grad_out);
+                            float* grad_out, const DropWin* drop);
 
 namespace {
 
@@ -55,11 +57,15 @@ __device__ __forceinline__ float gatv2_head_score(const HeadRow<Q>& a, const Hea
 // rescale of (m, l, acc) and U + 1 exponentials, as gatv2_fwd_chunk_kernel.  Every per-edge quantity is wave-uniform: nothing meets
 // at the end of a chunk.  Partials in the format of gat_head_fwd_chunk_kernel -- out_partial [n_chunks][len], ms_partial
 // [n_chunks] = (m, l) -- for gat_head_fwd_reduce_kernel, which writes out and row_stats.
-template <int CPL, int U>
+// DROP: out_i = act(sum_j p_ij w_ij h_j), w = mask . scale of element e of the [ne] array gaib_dropout fills (head_drop_mask: one
+// hash per lane and chunk, then a ballot); the weight of a step is a wave-uniform scalar, and m, l and the row statistics do not
+// see it.  The three trailing arguments are the DROP form's.
+template <int CPL, int U, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                    const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                                    const float* feat, const float* a, float eps, float* out_partial,
-                                                                   float2* ms_partial, int per_xcd) {
+                                                                   float2* ms_partial, int per_xcd, float drop_rate = 0.0f,
+                                                                   float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   static_assert((CPL == 4 || CPL == 8) && U % 4 == 0 && 64 % U == 0, "one head of 256 or 512 columns, four scores per wave sum");
   constexpr int Q = CPL / 4, LEN = 64 * CPL;
   HeadChunk ck;
@@ -69,6 +75,8 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
   const int cl = (int)col[ck.eb + (lane < n ? lane : 0)];  // (lanes past the end: the chunk's first edge)
   const HeadRow<Q> a4 = head_load<Q>(a + loff);
   const HeadRow<Q> hi = head_load<Q>(feat + ck.row * (int64_t)LEN + loff);
+  uint64_t mb = 0;  // DROP: the masks of the chunk's edges, bit t = step t
+  if constexpr (DROP) mb = head_drop_mask(lane, n, (uint64_t)(ck.eb + lane), drop_seed, drop_rate);
   float m = GAT_NEG, l = 0.f;
   HeadRow<Q> acc;
 #pragma unroll
@@ -103,11 +111,13 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
     for (int u = 0; u < U; ++u) {
       if (j + u < n) {  // (wave-uniform)
         const float e = __expf(s[u] - mx);
-        l += e;
+        l += e;  // (undropped under DROP too)
+        float ew = e;
+        if constexpr (DROP) ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);  // (a scalar bit test and select)
 #pragma unroll
         for (int q = 0; q < Q; ++q)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(e, xh[u].p[q][k], acc.p[q][k]);
+          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(ew, xh[u].p[q][k], acc.p[q][k]);
       }
     }
     m = mx;
@@ -126,11 +136,19 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
 // chunk (gatv2_head_rows_kernel adds them per row in chunk order); ag meets over the workgroup's four waves in LDS, in wave order
 // (4 x len floats: 8 KB at 512 columns), and leaves as ONE partial vector per workgroup, agrad_partial [gridDim.x][len].
 // Registers at 512 columns: a, h_j, g_j, acc and ag are 40 loop-invariant VGPRs, every edge in flight 16 more (xh, xg).
-template <int CPL, int U>
+// DROP: the expressions of gatv2_bwd_chunk_kernel<.., DROP> under two ballots, the chunk's edges' masks (w_ji) and their reverse
+// edges' (w_ij, over rev[eb + lane]: one coalesced 256 B per chunk).  The three sums still meet in one head_sum4 and the two dots
+// are scaled AFTER it (scale 1: the undropped bits).  Where w_ij = 0 nothing of g_i is used: that step's grad gather is redirected
+// to the chunk's own row (a scalar select of the row id ahead of the load, a resident line; the loads of a batch stay
+// unconditional), dp_ij is SELECTED to 0 and the p w g term is skipped -- no product with what the redirected load returned
+// reaches a result.  The four trailing arguments are the DROP form's.
+template <int CPL, int U, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                    const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                                    const float* feat, const float* grad, const f4* rec, const float* a,
-                                                                   float eps, float* out_partial, float* agrad_partial, int per_xcd) {
+                                                                   float eps, float* out_partial, float* agrad_partial, int per_xcd,
+                                                                   const uint32_t* rev = nullptr, float drop_rate = 0.0f,
+                                                                   float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   static_assert((CPL == 4 || CPL == 8) && 64 % U == 0, "one head of 256 or 512 columns");
   constexpr int Q = CPL / 4, LEN = 64 * CPL;
   __shared__ float sm[4 * LEN];
@@ -147,6 +165,11 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
     const HeadRow<Q> hi = head_load<Q>(feat + ck.row * (int64_t)LEN + loff);
     const HeadRow<Q> gi = head_load<Q>(grad + ck.row * (int64_t)LEN + loff);
     const f4 ri = rec[ck.row];  // (delta_j, m_j, 1 / l_j)
+    uint64_t mb_e = 0, mb_r = 0;  // DROP: the masks of the chunk's edges and of their reverse edges, bit t = step t
+    if constexpr (DROP) {
+      mb_e = head_drop_mask(lane, n, (uint64_t)(ck.eb + lane), drop_seed, drop_rate);
+      mb_r = head_drop_mask(lane, n, (uint64_t)rev[ck.eb + (lane < n ? lane : 0)], drop_seed, drop_rate);
+    }
     HeadRow<Q> acc;
 #pragma unroll
     for (int q = 0; q < Q; ++q) acc.p[q] = f4{0.f, 0.f, 0.f, 0.f};
@@ -158,8 +181,10 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane(cl, j + u);
+        uint32_t cg = cj;  // DROP: a dropped reverse edge gathers the chunk's own grad row (see above)
+        if constexpr (DROP) cg = ((mb_r >> (j + u)) & 1u) ? cj : (uint32_t)ck.row;
         xh[u] = head_load<Q>(feat + (int64_t)cj * LEN + loff);
-        xg[u] = head_load<Q>(grad + (int64_t)cj * LEN + loff);
+        xg[u] = head_load<Q>(grad + (int64_t)cg * LEN + loff);
         rc[u] = rec[cj];
       }
       __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first one is consumed
@@ -169,17 +194,25 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
         float s = gatv2_head_score<Q>(a4, hi, xh[u], eps, z, pz);  // the forward's bits, from either end
         float dp_ji = head_dot<Q>(gi, xh[u]), dp_ij = head_dot<Q>(xg[u], hi), none = 0.f;
         head_sum4(s, dp_ji, dp_ij, none);
+        bool keep_ij = true;
+        if constexpr (DROP) {
+          keep_ij = ((mb_r >> (j + u)) & 1u) != 0;
+          dp_ji *= ((mb_e >> (j + u)) & 1u) ? drop_scale : 0.0f;
+          dp_ij = keep_ij ? dp_ij * drop_scale : 0.0f;
+        }
         const float p_ji = __expf(s - ri[1]) * ri[2];
         const float p_ij = __expf(s - rc[u][1]) * rc[u][2];
         const float ds_ji = p_ji * (dp_ji - ri[0]);
         const float ds_ij = p_ij * (dp_ij - rc[u][0]);
         const float ds = ds_ij + ds_ji, dse = ds * eps;
+        float pw_ij = p_ij;  // the gradient flows back along the DROPPED attention p_ij w_ij: nothing where the bit is 0
+        if constexpr (DROP) pw_ij = p_ij * drop_scale;
         if (j + u < n) {  // (wave-uniform; a step past the end looked at the chunk's first edge: nothing of it is added)
 #pragma unroll
           for (int q = 0; q < Q; ++q)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              acc.p[q][k] = __builtin_fmaf(p_ij, xg[u].p[q][k], acc.p[q][k]);
+              if (keep_ij) acc.p[q][k] = __builtin_fmaf(pw_ij, xg[u].p[q][k], acc.p[q][k]);  // (wave-uniform)
               acc.p[q][k] = __builtin_fmaf(z.p[q][k] > 0.0f ? ds : dse, a4.p[q][k], acc.p[q][k]);
               ag.p[q][k] = __builtin_fmaf(ds_ji, pz.p[q][k], ag.p[q][k]);
             }
@@ -194,9 +227,14 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
 #pragma unroll
   for (int q = 0; q < Q; ++q) *reinterpret_cast<f4*>(sm + wv * LEN + q * 256 + loff) = ag.p[q];
   __syncthreads();
+  // DROP: the vector is stored at the index of the workgroup's CHUNKS (head_chunk's blk), so a's sum does not depend on the per_xcd
+  // walk (gatv2.hip)
+  int64_t slot_ag = blockIdx.x;
+  if constexpr (DROP)
+    if (per_xcd > 0) slot_ag = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
 #pragma unroll
   for (int t = threadIdx.x; t < LEN; t += 256)
-    agrad_partial[(int64_t)blockIdx.x * LEN + t] = ((sm[t] + sm[LEN + t]) + sm[2 * LEN + t]) + sm[3 * LEN + t];
+    agrad_partial[slot_ag * LEN + t] = ((sm[t] + sm[LEN + t]) + sm[2 * LEN + t]) + sm[3 * LEN + t];
 }
 
 // out[row] = sum of the row's chunk partials in chunk order (gat_head_bwd_reduce_kernel without its pair of sums).  One wave per row.

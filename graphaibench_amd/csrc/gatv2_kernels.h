@@ -46,11 +46,18 @@ __device__ __forceinline__ f4 gatv2_row4(const char* tab, uint32_t v, uint32_t r
 // WIDE: feat has rows of ld floats of which this launch sweeps the len = 4 G at `feat` (one column slab of a wider multi-head row,
 // option gatv2_wide); a is the slab's piece and the partials stay len wide.  A template flag with a trailing, defaulted argument read
 // only behind `WIDE ? ld : len`: the narrow instantiations compile to the instructions they had.
-template <int G, int H, int U, bool WIDE = false>
+// DROP: attention dropout inside the sweep, out_i = act(sum_j p_ij w_ij h_j) with w = mask . scale of element e heads + k of the
+// [ne][heads] array gaib_dropout fills (gat_drop_bits: one bit word per chunk, formed ahead of the edge loop; under WIDE the slab's
+// head window mask_heads / mask_head0 of the full row).  The softmax does not see the mask: the maximum, l and so the row
+// statistics are the undropped sweep's; only the accumulator's weight e becomes e w, a bit test and a select.  The five trailing
+// arguments are read behind the flag only.
+template <int G, int H, int U, bool WIDE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                               const float* feat, const float* a, float eps, float* out_partial,
-                                                              float2* ms_partial, int per_xcd, int ld = 0) {
+                                                              float2* ms_partial, int per_xcd, int ld = 0, float drop_rate = 0.0f,
+                                                              float drop_scale = 1.0f, uint64_t drop_seed = 0, int mask_heads = 0,
+                                                              int mask_head0 = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -75,6 +82,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
   const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * 4u, lane_off = (uint32_t)coff * 4u;
   const f4 hi = gatv2_row4(tab, (uint32_t)row, row_bytes, lane_off);
   const f4 a4 = *reinterpret_cast<const f4*>(a + coff);
+  uint32_t mb = 0;  // DROP: the masks of the chunk's edges for this lane's head, bit t = step t
+  if constexpr (DROP) mb = gat_drop_bits<G, H, false, WIDE>(lane, n, eb, nullptr, drop_seed, drop_rate, mask_heads, mask_head0);
   float m = GAT_NEG, l = 0.f;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -98,9 +107,11 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const float e = CL::step_edge(lane, j + u) < n ? __expf(s[u] - mx) : 0.0f;
-      l += e;
+      l += e;  // (undropped under DROP too)
+      float ew = e;
+      if constexpr (DROP) ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = __builtin_fmaf(e, xh[u][q], acc[q]);
+      for (int q = 0; q < 4; ++q) acc[q] = __builtin_fmaf(ew, xh[u][q], acc[q]);
     }
     m = mx;
   }
@@ -135,12 +146,22 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
 // groups and the workgroup's four waves in a fixed order and leaves as ONE partial vector per workgroup (agrad_partial
 // [gridDim.x][len], summed by gatv2_agrad_strip_kernel / gatv2_agrad_final_kernel).  No atomics, nothing per edge is written.
 // WIDE: feat and grad have rows of ld floats (see the forward); the records [nv][H] and both partials are the slab's own.
-template <int G, int H, int U, bool WIDE = false>
+// DROP: the forward was out_i = act(sum_j p_ij w_ij h_j).  delta_i = <g_i, out_i> with the DROPPED output is still sum_j p_ij dp_ij,
+// so the records are unchanged, and
+//   dp_ij = w_ij <g_i, h_j>      dp_ji = w_ji <g_j, h_i>      grad_out_j += p_ij w_ij g_i + (ds_ij + ds_ji) a phi'(h_i + h_j)
+// -- a dropped edge still enters ds through -p delta.  The two directions of an edge carry DIFFERENT masks while the score stays
+// symmetric bit for bit, so the one sweep still suffices: row j's chunk holds e = e(j -> i), w_ji is element e heads + k (the row
+// side of gat_drop_bits, whose key advances by addition) and w_ij element rev[e] heads + k (rev read at the lane's own steps, 256
+// contiguous bytes per chunk).  Two bit words per chunk, formed ahead of the edge loop; in the loop two bit tests and selects.
+// The six trailing arguments are read behind the flag only.
+template <int G, int H, int U, bool WIDE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
                                                               const float* feat, const float* grad, const f4* rec, const float* a,
                                                               float eps, float* out_partial, float* agrad_partial, int per_xcd,
-                                                              int ld = 0) {
+                                                              int ld = 0, const uint32_t* rev = nullptr, float drop_rate = 0.0f,
+                                                              float drop_scale = 1.0f, uint64_t drop_seed = 0, int mask_heads = 0,
+                                                              int mask_head0 = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
   constexpr int NG = CL::NG;
@@ -173,6 +194,11 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
     const f4 ri = gatv2_row4(rtab, (uint32_t)row, rec_bytes, rec_off);  // (delta_j, m_j, 1 / l_j)
     const f4 a4 = *reinterpret_cast<const f4*>(a + coff);
     const f4 ae4 = a4 * eps;  // a phi' where z <= 0
+    uint32_t mb_e = 0, mb_r = 0;  // DROP: the masks of the chunk's edges (w_ji) and of their reverse edges (w_ij), bit t = step t
+    if constexpr (DROP) {
+      mb_e = gat_drop_bits<G, H, false, WIDE>(lane, n, eb, nullptr, drop_seed, drop_rate, mask_heads, mask_head0);
+      mb_r = gat_drop_bits<G, H, true, WIDE>(lane, n, eb, rev, drop_seed, drop_rate, mask_heads, mask_head0);
+    }
     auto d4 = [](const f4& x, const f4& y) {
       return __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], x[0] * y[0])));
     };
@@ -193,17 +219,25 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
       for (int u = 0; u < U; ++u) {
         f4 z, pz;
         const float s = gatv2_score<LH>(a4, hi, xh[u], eps, z, pz);  // the forward's bits, from either end
-        const float dp_ji = lanes_sum_w<LH>(d4(gi, xh[u]));
-        const float dp_ij = lanes_sum_w<LH>(d4(xg[u], hi));
+        float dp_ji = lanes_sum_w<LH>(d4(gi, xh[u]));
+        float dp_ij = lanes_sum_w<LH>(d4(xg[u], hi));
+        float w_ij = 1.0f;
+        if constexpr (DROP) {  // (the sums are scaled after they met: with rate 0 and scale 1 the undropped bits)
+          dp_ji *= ((mb_e >> (j + u)) & 1u) ? drop_scale : 0.0f;
+          w_ij = ((mb_r >> (j + u)) & 1u) ? drop_scale : 0.0f;
+          dp_ij *= w_ij;
+        }
         const float p_ji = __expf(s - ri[1]) * ri[2];
         const float p_ij = __expf(s - rc[u][1]) * rc[u][2];
         const float ds_ji = p_ji * (dp_ji - ri[0]);
         const float ds_ij = p_ij * (dp_ij - rc[u][0]);
         const float ds = ds_ij + ds_ji;
+        float pw_ij = p_ij;  // the gradient flows back along the DROPPED attention p_ij w_ij
+        if constexpr (DROP) pw_ij = p_ij * w_ij;
         if (CL::step_edge(lane, j + u) < n) {  // (lanes past the end of a short chunk looked at its first edge: nothing is added)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            acc[q] = __builtin_fmaf(p_ij, xg[u][q], acc[q]);
+            acc[q] = __builtin_fmaf(pw_ij, xg[u][q], acc[q]);
             acc[q] = __builtin_fmaf(ds, z[q] > 0.0f ? a4[q] : ae4[q], acc[q]);
             ag[q] = __builtin_fmaf(ds_ji, pz[q], ag[q]);
           }
@@ -226,7 +260,9 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
   __syncthreads();
   if (threadIdx.x < len) {
     const int t = threadIdx.x;
-    agrad_partial[(int64_t)blockIdx.x * len + t] = ((sm[t] + sm[len + t]) + sm[2 * len + t]) + sm[3 * len + t];
+    // DROP: the vector is stored at the index of the workgroup's CHUNKS, so a's sum does not depend on the per_xcd walk (gatv2.hip)
+    const int64_t slot_ag = DROP ? blk : (int64_t)blockIdx.x;
+    agrad_partial[slot_ag * len + t] = ((sm[t] + sm[len + t]) + sm[2 * len + t]) + sm[3 * len + t];
   }
 }
 

@@ -819,13 +819,14 @@ void GAT_Aggregator::v2_check(int len, Graph& g) const {
   // option gatv2_wide: also column slabs of a multi-head row and one head of 256 or 512 columns
   const bool wide = gaib_host::option("gatv2_wide") == 1 && (S >= 2 || gaib_gat_fused_head_cpl(len, heads) > 0);
   if (!(S == 1 && w == len) && !wide) why = "this shape";
-  else if (attn_drop > 0.f) why = "attention dropout (score_drop > 0)";
+  // attention dropout runs inside the v2 sweeps (gaib_gatv2_forward_drop / gaib_gatv2_backward_drop) with option gat_fused_drop
+  else if (attn_drop > 0.f && !gat_fused_drop_option()) why = "attention dropout (score_drop > 0) without gat_fused_drop (GAIB_GAT_FUSED_DROP=1)";
   else if (g.gat_full_graph() || g.has_halo()) why = "a partitioned graph";
   else if (gat_bf16_tables()) why = "gat_bf16 (GAIB_GAT_DTYPE=bf16)";
   if (!why) return;
   fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1) does not cover %s (len %d, heads %d): GATv2 runs rows of 32, 64 or 128 columns "
           "with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with gatv2_wide (GAIB_GATV2_WIDE=1) also column slabs of such rows and one "
-          "head of 256 or 512 columns --, whole graphs, fp32 tables, no attention dropout\n", why, len, heads);
+          "head of 256 or 512 columns --, whole graphs, fp32 tables, attention dropout only with GAIB_GAT_FUSED_DROP=1\n", why, len, heads);
   exit(EXIT_FAILURE);
 }
 // bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32
@@ -848,9 +849,16 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     v2_check(len, g);
     grow(d_row_stats, stats_floats, (size_t)g.size() * heads * 2);
     OpTimer t(OP_SPARSEMM);
-    GAIB_OR_DIE(gaib_gatv2_forward(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, out, d_row_stats));
-    fuse_relu = false;
     stats_valid = dropped_last = drop_fused_last = fwd_bf16 = false;
+    if (dropping()) {  // (v2_check: option gat_fused_drop is on) the masks of the staged sequence's next seed, kept for backward
+      GAIB_OR_DIE(gaib_gatv2_forward_drop(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, attn_drop, attn_scale,
+                                          drop_seed, out, d_row_stats));
+      drop_seed_last = drop_seed++;
+      drop_fused_last = drop_sweep_ran = true;
+    } else {
+      GAIB_OR_DIE(gaib_gatv2_forward(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, out, d_row_stats));
+    }
+    fuse_relu = false;
     return;
   }
   if (g.gat_full_graph() && gat_bf16_tables()) no_gat_bf16_partition();
@@ -949,8 +957,13 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
     OpTimer t(OP_ATTN);
     const size_t need = (size_t)g.size() * len;
     grow(d_tbuf, tbuf_floats, need);
-    GAIB_OR_DIE(gaib_gatv2_backward(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon, d_tbuf,
-                                    d_alpha_lgrad));
+    if (drop_fused_last)  // the forward dropped inside the sweep: backward through the same masks, formed again from the kept seed
+      GAIB_OR_DIE(gaib_gatv2_backward_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon,
+                                           attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad));
+    else
+      GAIB_OR_DIE(gaib_gatv2_backward(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon, d_tbuf,
+                                      d_alpha_lgrad));
+    drop_fused_last = false;
     GAIB_OR_DIE(gaib_fill_f32(C(), length, 0.f, d_alpha_rgrad));
     fwd_out = NULL;
     fwd_out_given = false;

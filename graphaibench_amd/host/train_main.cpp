@@ -761,7 +761,9 @@ struct Trainer {
     std::vector<double> all_loss, all_acc;
     std::vector<double> subgraph_s;  // (GAIB_EPOCH_TIMES with sampling) seconds per epoch in subgraph_sampling
     // score_drop > 0 on GAT: which path the layers' training forwards of epoch 0 TOOK (asked of the aggregators, not predicted:
-    // GAIB_GAT_FUSED_DROP=1 keeps a layer in the one-sweep kernels only where they cover its shape and graph), printed once
+    // GAIB_GAT_FUSED_DROP=1 keeps a layer in the one-sweep kernels only where they cover its shape and graph), printed once.
+    // GATv2 layers (GAIB_GAT_V2=1) have no staged form: with GAIB_GAT_FUSED_DROP=1 every training forward is the dropped v2 sweep
+    // and the line reads "one sweep", beside "GAT scores: v2, one sweep"; without it the first forward ends the run with a message
     bool drop_path_said = !(ARCH == gnn_arch::GAT && score_drop > 0.f && root());
     auto say_drop_path = [&]() {
       if (drop_path_said) return;

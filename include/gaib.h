@@ -428,6 +428,29 @@ int gaib_gatv2_forward(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const f
 int gaib_gatv2_backward(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
                         const float* d_fwd_out, const float* d_a, const float* d_row_stats, float epsilon, float* d_grad_out,
                         float* d_a_grad);
+/* The two GATv2 calls under ATTENTION DROPOUT, the masks formed inside the sweeps (no [ne][heads] array; layer-library options
+ * "gat_v2" with "gat_fused_drop").  With e(i->j) the position of edge i -> j in the CSR, the weight of (edge, head) is
+ * w_ij^k = mask * scale, mask = u01(seed, e(i->j) * heads + k) > drop_rate: EXACTLY the mask gaib_dropout(n = ne * heads, scale,
+ * drop_rate, seed, ..) draws for that element (the index in 64 bits).
+ *   forward:   s, m, l and p as in gaib_gatv2_forward -- the softmax does not see the mask, d_row_stats holds the BITS the undropped
+ *              call writes --; d_out_i = act(sum_j p_ij w_ij h_j).
+ *   backward:  d_fwd_out is the DROPPED forward output; delta_i^k = <g_i, out_i>_k as before;
+ *              dp_ij^k = w_ij^k <g_i, h_j>_k       ds_ij^k = p_ij^k (dp_ij^k - delta_i^k)     (a dropped edge still enters through -p delta)
+ *              d_grad_out_jc = sum_{i in N(j)} [ p_ij^k w_ij^k g_ic + (ds_ij^k + ds_ji^k) a_c phi'(h_ic + h_jc) ]
+ *              d_a_grad_c    = sum_j sum_{i in N(j)} ds_ji^k phi(h_jc + h_ic)          (a self loop stands once and counts 2 ds_jj)
+ *              The two directions of an edge carry different masks, the score stays symmetric bit for bit: still ONE sweep over
+ *              row j's own edges, which takes w_ji from the edge's own index and w_ij through the reverse-edge permutation.
+ * With drop_rate = 0 and scale = 1 every output has the bits of the undropped calls.  No atomics, bit-identical from run to run.
+ * Cover and refusals are those of gaib_gatv2_forward / gaib_gatv2_backward, "gatv2_wide" = 1 for the wide shapes included (slab
+ * s reads the masks of its own heads in the full row's mask array).  Further: drop_rate outside [0, 1) -> GAIB_ERR_INVALID; a
+ * graph whose reverse-edge permutation cannot be built -> that error, from forward and backward alike; a rectangular graph ->
+ * GAIB_ERR_UNSUPPORTED.  Refusals touch nothing.  Profile keys "gatv2_fwd" / "gatv2_bwd"; the backward's bytes count the
+ * reverse-edge id, 4 more per edge.  Speed: not measured yet. */
+int gaib_gatv2_forward_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_h, const float* d_a, float epsilon,
+                            int relu, float drop_rate, float scale, uint64_t seed, float* d_out, float* d_row_stats);
+int gaib_gatv2_backward_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
+                             const float* d_fwd_out, const float* d_a, const float* d_row_stats, float epsilon, float drop_rate,
+                             float scale, uint64_t seed, float* d_grad_out, float* d_a_grad);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
  * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
@@ -1109,8 +1132,10 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * attention dropout holds neither that array nor mask nor dropped attention; with "gat_bf16" = 1 as well the _bf16 calls (with all
  * three, the _drop_bf16 calls) run them on bf16 tables; partitions stay as they are;
  * "gat_v2" (default 0; readable): 1 = the layer library's GAT aggregation computes GATv2 (gaib_gatv2_forward / gaib_gatv2_backward):
- * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover, attention dropout, a
- * partitioned graph and "gat_bf16" = 1 are refused there with a message, not served by another path;
+ * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover, a partitioned graph
+ * and "gat_bf16" = 1 are refused there with a message, not served by another path; so is attention dropout, unless "gat_fused_drop"
+ * = 1 as well: a training forward then runs gaib_gatv2_forward_drop under the staged sequence of seeds and its backward
+ * gaib_gatv2_backward_drop under the kept seed (no mask array; a test-phase forward drops nothing);
  * "gatv2_wide" (default 0; readable): 1 = gaib_gatv2_forward / gaib_gatv2_backward also run multi-head rows wider than 128 columns
  * as column slabs (gaib_gat_fused_slabs gives S >= 2) and a single head of 256 or 512 columns (gaib_gat_fused_head_cpl) in sweeps
  * of its own; the layer library's "gat_v2" layers accept those shapes then; 0 = GAIB_ERR_UNSUPPORTED there, as before;

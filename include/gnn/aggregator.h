@@ -232,6 +232,10 @@ class GAT_Aggregator : public aggregator {
   // a partitioned graph, "gat_bf16" = 1 and a backward without the layer's forward output end the process with a message.
   // With context option "gatv2_wide" = 1 (GAIB_GATV2_WIDE=1) v2_check() also accepts what the two calls then cover: multi-head
   // rows wider than 128 columns that gaib_gat_fused_slabs cuts into slabs, and one head of 256 or 512 columns.
+  // Attention dropout under the option: with "gat_fused_drop" = 1 as well, a training forward with attn_drop > 0 is
+  // gaib_gatv2_forward_drop under seed = drop_seed++ (the staged sequence, first seed 0xA77E0000) and keeps the seed
+  // (drop_seed_last, drop_fused_last); d_aggregate() is gaib_gatv2_backward_drop under the kept seed.  A test-phase forward drops
+  // nothing.  With "gat_fused_drop" = 0 the process still ends, and the message names GAIB_GAT_FUSED_DROP=1.
   static bool gat_v2_option();
   void v2_check(int len, Graph& g) const;
   void grow_edge_arrays(size_t ne);

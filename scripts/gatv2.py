@@ -10,10 +10,13 @@ rate of the run beside them:
 The two legs compute different models: the comparison says what the dynamic score costs, not which path to take.
 Rows wider than 128 columns (256x1, 512x1, 256x8 = 8 heads x 32: DESIGN.md 3.3.6) run both legs on their opt-in one-sweep paths:
 gat_fused_head = gat_fused_wide = 1 for the static scores, gatv2_wide = 1 for GATv2, set for the whole child and recorded.
+--drop RATE: both legs under attention dropout kept in the sweep -- gat_fused_drop = 1 and layers with score_drop
+= RATE, the calls alone through gaib_gat_*_fused_drop and gaib_gatv2_*_drop under one seed.  Not measured yet.
 A shape whose child fails or runs into its time limit ends the run: no further child is started.
 
     python scripts/gatv2.py OUT.json [--iters 20] [--shapes 64x8,64x1] [--timeout 600]
     python scripts/gatv2.py OUT.json --shapes 256x1,512x1,256x8
+    python scripts/gatv2.py OUT.json --shapes 64x8,256x1,256x8 --drop 0.3
 """
 import argparse
 import json
@@ -27,7 +30,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "scripts"))
 
 
-def child(shape, iters, out_path):
+def child(shape, iters, out_path, drop=0.0):
     import torch
 
     from bf16_gat import time_legs
@@ -41,11 +44,14 @@ def child(shape, iters, out_path):
     nv, ne = g.nv, g.ne
     rp, ci = g.rowptr(), g.colidx()
     D, H = (int(v) for v in shape.split("x"))
-    r = dict(len=D, heads=H, nv=nv, ne=ne, iters=iters, stream_copy_gbs_before=ctx.probe_stream_copy())
+    r = dict(len=D, heads=H, nv=nv, ne=ne, iters=iters, drop=drop, stream_copy_gbs_before=ctx.probe_stream_copy())
+    r["options"] = {}
     if D > 128:  # the wide rows' one-sweep paths of both models, before a layer is built
-        r["options"] = dict(gat_fused_head=1, gat_fused_wide=1, gatv2_wide=1)
-        for k, v in r["options"].items():
-            ctx.set_option(k, v)
+        r["options"].update(gat_fused_head=1, gat_fused_wide=1, gatv2_wide=1)
+    if drop > 0:  # attention dropout stays in the sweeps of both models
+        r["options"].update(gat_fused_drop=1)
+    for k, v in r["options"].items():
+        ctx.set_option(k, v)
     gen = torch.Generator(device="cuda").manual_seed(1)
     h = torch.randn(nv, D, device="cuda", generator=gen)
     grad = torch.randn(nv, D, device="cuda", generator=gen)
@@ -54,7 +60,7 @@ def child(shape, iters, out_path):
     def make_layer(v2):
         ctx.set_option("gat_v2", v2)
         lg_graph = L.LGraph.adopt(ctx.graph(rp, ci))
-        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True)
+        ld = L.Layer(L.GAT, 1, nv, D, D, lg_graph, True, score_drop=drop)
         ld.set_heads(H)
         ld.write(L.FEAT_IN, h)
         ld.write(L.GRAD_IN, grad)  # (the layer's d_relu masks it in place by the forward output)
@@ -77,7 +83,13 @@ def child(shape, iters, out_path):
     al, ar = (0.05 * torch.randn(D, device="cuda", generator=gen) for _ in range(2))
     stats, lg_, rg_ = torch.empty(nv, H, 2, device="cuda"), torch.empty(D, device="cuda"), torch.empty(D, device="cuda")
     ok = lambda done: done or sys.exit("a call was refused")  # noqa: E731
+    seed = 0x5EED0001
     r["calls"] = time_legs({
+        "v1_forward": lambda: ok(ctx.gat_forward_fused_drop(g, h, al, ar, lout, stats, drop, seed, heads=H)),
+        "v2_forward": lambda: ok(ctx.gatv2_forward_drop(g, h, al, lout, stats, drop, seed, heads=H)),
+        "v1_backward": lambda: ok(ctx.gat_backward_fused_drop(g, h, grad, lout, al, ar, lgo, lg_, rg_, stats, drop, seed, heads=H)),
+        "v2_backward": lambda: ok(ctx.gatv2_backward_drop(g, h, grad, lout, al, stats, lgo, lg_, drop, seed, heads=H)),
+    } if drop > 0 else {
         "v1_forward": lambda: ok(ctx.gat_forward_fused(g, h, al, ar, lout, stats, heads=H)),
         "v2_forward": lambda: ok(ctx.gatv2_forward(g, h, al, lout, stats, heads=H)),
         "v1_backward": lambda: ok(ctx.gat_backward_fused(g, h, grad, lout, al, ar, None, lgo, lg_, rg_, heads=H, row_stats=stats)),
@@ -95,10 +107,11 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default="64x8,64x1")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per shape (its child process)")
+    ap.add_argument("--drop", type=float, default=0.0, help="attention dropout rate of both legs, kept in the sweeps (0: none)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child(args.child, args.iters, args.out)
+        child(args.child, args.iters, args.out, args.drop)
         return
     rec = dict(what="GAT layer step and the two calls alone: GATv2 scores in one sweep (gat_v2 = 1) next to the one-sweep GAT "
                     "(gat_v2 = 0) of the same tree", graph="reddit synth (seed 7) + self loops", shapes=[])
@@ -106,7 +119,7 @@ def main():
         for shape in args.shapes.split(","):
             part = Path(tmp) / f"{shape}.json"
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, str(Path(__file__).resolve()), str(part), "--child", shape,
-                   "--iters", str(args.iters)]
+                   "--iters", str(args.iters), "--drop", str(args.drop)]
             rc = subprocess.run(cmd).returncode
             if rc != 0:  # a fault, an abort or the time limit: nothing more is started on the device
                 rec["stopped"] = dict(shape=shape, exit_status=rc)
