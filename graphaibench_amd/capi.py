@@ -122,6 +122,10 @@ SIGNATURES = {
     "gaib_gatv2_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "gaib_gatv2_forward_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
     "gaib_gatv2_backward_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp]),
+    "gaib_gatv2_forward_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "gaib_gatv2_backward_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "gaib_gatv2_forward_drop_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
+    "gaib_gatv2_backward_drop_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _u64, _vp, _vp]),
     "gaib_gat_forward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "gaib_gat_backward_fused_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "gaib_gat_forward_fused_drop": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _f, _f, _u64, _vp, _vp]),
@@ -994,6 +998,68 @@ class Context:
         if rc == -5:
             return False
         _check(rc, "gaib_gatv2_backward_drop")
+        return True
+
+    def gatv2_forward_bf16(self, g, h, a, out, row_stats, eps: float = 0.2, heads: int = 1, relu: bool = False) -> bool:
+        """gatv2_forward over a torch.bfloat16 table h [nv, len]: the bits of the fp32 call on the widened table (with option
+        gatv2_wide also on the wide shapes).  False = outside the cover (nothing touched)"""
+        import torch
+
+        assert h.dtype == torch.bfloat16 and h.dim() == 2
+        rc = self.lib.gaib_gatv2_forward_bf16(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(a), eps, int(relu), _ptr(out),
+                                              _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_forward_bf16")
+        return True
+
+    def gatv2_backward_bf16(self, g, feat, grad, fwd_out, a, row_stats, grad_out, a_grad, eps: float = 0.2, heads: int = 1) -> bool:
+        """gatv2_backward over torch.bfloat16 tables feat and grad [nv, len]: the exact gradient of gatv2_forward_bf16, the bits
+        of the fp32 call on the widened tables.  False = outside the cover (nothing touched)"""
+        import torch
+
+        assert feat.dtype == torch.bfloat16 and grad.dtype == torch.bfloat16 and feat.dim() == 2
+        rc = self.lib.gaib_gatv2_backward_bf16(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out), _ptr(a),
+                                               _ptr(row_stats), eps, _ptr(grad_out), _ptr(a_grad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_backward_bf16")
+        return True
+
+    def gatv2_forward_drop_bf16(self, g, h, a, out, row_stats, rate: float, seed: int, scale=None, eps: float = 0.2, heads: int = 1,
+                                relu: bool = False) -> bool:
+        """gatv2_forward_drop over a torch.bfloat16 table h [nv, len]: the bits of the fp32 _drop call on the widened table for
+        the same rate, scale and seed.  False = outside the cover (nothing touched)"""
+        import torch
+
+        assert h.dtype == torch.bfloat16 and h.dim() == 2
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gatv2_forward_drop_bf16(self.h, g.h, h.shape[1], heads, _ptr(h), _ptr(a), eps, int(relu), rate, scale,
+                                                   seed, _ptr(out), _ptr(row_stats))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_forward_drop_bf16")
+        return True
+
+    def gatv2_backward_drop_bf16(self, g, feat, grad, fwd_out, a, row_stats, grad_out, a_grad, rate: float, seed: int, scale=None,
+                                 eps: float = 0.2, heads: int = 1) -> bool:
+        """gatv2_backward_drop over torch.bfloat16 tables feat and grad [nv, len], through the masks of gatv2_forward_drop_bf16
+        with the same rate and seed.  False = outside the cover (nothing touched)"""
+        import torch
+
+        assert feat.dtype == torch.bfloat16 and grad.dtype == torch.bfloat16 and feat.dim() == 2
+        if scale is None:
+            import numpy as np
+
+            scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+        rc = self.lib.gaib_gatv2_backward_drop_bf16(self.h, g.h, feat.shape[1], heads, _ptr(feat), _ptr(grad), _ptr(fwd_out),
+                                                    _ptr(a), _ptr(row_stats), eps, rate, scale, seed, _ptr(grad_out), _ptr(a_grad))
+        if rc == -5:
+            return False
+        _check(rc, "gaib_gatv2_backward_drop_bf16")
         return True
 
     def gat_forward_fused_bf16(self, g, h, alpha_l, alpha_r, out, row_stats, eps: float = 0.2, heads: int = 1,

@@ -1,5 +1,5 @@
 // gatv2_head_kernels.h -- the one-sweep GATv2 for ONE head of 256 or 512 columns (option gatv2_wide; gatv2_head.hip instantiates
-// these kernels, gatv2.hip holds the host sequence).  Column slabs cannot cut a head: s_ij = sum_c a_c phi(h_ic + h_jc) runs over the
+// these kernels, gatv2_seq.h holds the host sequence).  Column slabs cannot cut a head: s_ij = sum_c a_c phi(h_ic + h_jc) runs over the
 // whole of it.  The layout is gat_head_kernels.h's, and its pieces are used as they are: one wave per 64-edge chunk, four chunks per
 // workgroup, the per_xcd walk (head_chunk); a lane owns CPL = len / 64 columns as Q = CPL / 4 pieces of 16 bytes at columns
 // q 256 + 4 lane (HeadRow, head_load); the chunk's ids are fetched once and handed out with readlane, so a row's base address is
@@ -23,13 +23,16 @@
 // gatv2_head.hip: the sweeps for ONE head of 256 or 512 columns (cpl = gaib_gat_fused_head_cpl; gatv2_head_kernels.h) with their
 // per-row reductions.  forward: d_out and d_row_stats [nv][1][2]; backward: d_grad_out and the workgroups' partial vectors of a's
 // gradient, agrad_partial [grid][len], for gatv2_agrad_strip_kernel.  drop: NULL, or rate, scale and seed of the call (its window
-// fields are not read: one head); backward under dropout reads g->rev
-int gatv2_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* h, const float* a,
+// fields are not read: one head); backward under dropout reads g->rev.  E: the element type of the tables h, feat and grad (float,
+// uint16_t = raw bf16 bits: both instantiated in gatv2_head.hip and nowhere else)
+template <typename E>
+int gatv2_head_forward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const E* h, const float* a,
                            float eps, int relu, float* out_partial, float2* ms_partial, float* out, float* row_stats,
                            const DropWin* drop);
-int gatv2_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const float* feat,
-                            const float* grad, const f4* rec, const float* a, float eps, float* out_partial, float* agrad_partial,
-                            float* grad_out, const DropWin* drop);
+template <typename E>
+int gatv2_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const E* feat, const E* grad,
+                            const f4* rec, const float* a, float eps, float* out_partial, float* agrad_partial, float* grad_out,
+                            const DropWin* drop);
 
 namespace {
 
@@ -60,10 +63,12 @@ __device__ __forceinline__ float gatv2_head_score(const HeadRow<Q>& a, const Hea
 // DROP: out_i = act(sum_j p_ij w_ij h_j), w = mask . scale of element e of the [ne] array gaib_dropout fills (head_drop_mask: one
 // hash per lane and chunk, then a ballot); the weight of a step is a wave-uniform scalar, and m, l and the row statistics do not
 // see it.  The three trailing arguments are the DROP form's.
-template <int CPL, int U, bool DROP = false>
+// E: the element type of feat.  A bf16 row is Q loads of 8 bytes (head_load_raw: a load instruction of the wave covers 512
+// contiguous bytes), waits packed and is widened exactly (head_widen) behind the batch's sched_barrier; the chunk's own row once.
+template <int CPL, int U, bool DROP = false, typename E = float>
 __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                    const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                                   const float* feat, const float* a, float eps, float* out_partial,
+                                                                   const E* feat, const float* a, float eps, float* out_partial,
                                                                    float2* ms_partial, int per_xcd, float drop_rate = 0.0f,
                                                                    float drop_scale = 1.0f, uint64_t drop_seed = 0) {
   static_assert((CPL == 4 || CPL == 8) && U % 4 == 0 && 64 % U == 0, "one head of 256 or 512 columns, four scores per wave sum");
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
   const int loff = 4 * lane;
   const int cl = (int)col[ck.eb + (lane < n ? lane : 0)];  // (lanes past the end: the chunk's first edge)
   const HeadRow<Q> a4 = head_load<Q>(a + loff);
-  const HeadRow<Q> hi = head_load<Q>(feat + ck.row * (int64_t)LEN + loff);
+  const HeadRow<Q> hi = head_widen<Q, E>(head_load_raw<Q, E>(feat + ck.row * (int64_t)LEN + loff));
   uint64_t mb = 0;  // DROP: the masks of the chunk's edges, bit t = step t
   if constexpr (DROP) mb = head_drop_mask(lane, n, (uint64_t)(ck.eb + lane), drop_seed, drop_rate);
   float m = GAT_NEG, l = 0.f;
@@ -84,18 +89,18 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
 #pragma unroll
   for (int j = 0; j < 64; j += U) {
     if (j >= n) continue;  // (wave-uniform: no edge of the chunk is left)
-    HeadRow<Q> xh[U];
+    HeadRaw<Q, E> xh_raw[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane(cl, j + u);
-      xh[u] = head_load<Q>(feat + (int64_t)cj * LEN + loff);
+      xh_raw[u] = head_load_raw<Q, E>(feat + (int64_t)cj * LEN + loff);
     }
     __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first one is consumed
     float s[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       HeadRow<Q> z, pz;
-      s[u] = gatv2_head_score<Q>(a4, hi, xh[u], eps, z, pz);
+      s[u] = gatv2_head_score<Q>(a4, hi, head_widen<Q, E>(xh_raw[u]), eps, z, pz);
     }
 #pragma unroll
     for (int u = 0; u < U; u += 4) head_sum4(s[u], s[u + 1], s[u + 2], s[u + 3]);
@@ -114,10 +119,11 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
         l += e;  // (undropped under DROP too)
         float ew = e;
         if constexpr (DROP) ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);  // (a scalar bit test and select)
+        const HeadRow<Q> xh = head_widen<Q, E>(xh_raw[u]);  // (bf16: a second widening, not a copy kept across the batch's maximum)
 #pragma unroll
         for (int q = 0; q < Q; ++q)
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(ew, xh[u].p[q][k], acc.p[q][k]);
+          for (int k = 0; k < 4; ++k) acc.p[q][k] = __builtin_fmaf(ew, xh.p[q][k], acc.p[q][k]);
       }
     }
     m = mx;
@@ -142,10 +148,11 @@ __global__ __launch_bounds__(256) void gatv2_head_fwd_chunk_kernel(int64_t n_chu
 // to the chunk's own row (a scalar select of the row id ahead of the load, a resident line; the loads of a batch stay
 // unconditional), dp_ij is SELECTED to 0 and the p w g term is skipped -- no product with what the redirected load returned
 // reaches a result.  The four trailing arguments are the DROP form's.
-template <int CPL, int U, bool DROP = false>
+// E: the element type of feat and grad, as in the forward (bf16 at 512 columns: every edge in flight 8 VGPRs instead of 16).
+template <int CPL, int U, bool DROP = false, typename E = float>
 __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                                    const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                                   const float* feat, const float* grad, const f4* rec, const float* a,
+                                                                   const E* feat, const E* grad, const f4* rec, const float* a,
                                                                    float eps, float* out_partial, float* agrad_partial, int per_xcd,
                                                                    const uint32_t* rev = nullptr, float drop_rate = 0.0f,
                                                                    float drop_scale = 1.0f, uint64_t drop_seed = 0) {
@@ -162,8 +169,8 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
     const int n = ck.n;
     const int cl = (int)col[ck.eb + (lane < n ? lane : 0)];  // (lanes past the end: the chunk's first edge)
     const HeadRow<Q> a4 = head_load<Q>(a + loff);
-    const HeadRow<Q> hi = head_load<Q>(feat + ck.row * (int64_t)LEN + loff);
-    const HeadRow<Q> gi = head_load<Q>(grad + ck.row * (int64_t)LEN + loff);
+    const HeadRow<Q> hi = head_widen<Q, E>(head_load_raw<Q, E>(feat + ck.row * (int64_t)LEN + loff));
+    const HeadRow<Q> gi = head_widen<Q, E>(head_load_raw<Q, E>(grad + ck.row * (int64_t)LEN + loff));
     const f4 ri = rec[ck.row];  // (delta_j, m_j, 1 / l_j)
     uint64_t mb_e = 0, mb_r = 0;  // DROP: the masks of the chunk's edges and of their reverse edges, bit t = step t
     if constexpr (DROP) {
@@ -176,23 +183,24 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
 #pragma unroll
     for (int j = 0; j < 64; j += U) {
       if (j >= n) continue;  // (wave-uniform: no edge of the chunk is left)
-      HeadRow<Q> xh[U], xg[U];
+      HeadRaw<Q, E> xh_raw[U], xg_raw[U];
       f4 rc[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane(cl, j + u);
         uint32_t cg = cj;  // DROP: a dropped reverse edge gathers the chunk's own grad row (see above)
         if constexpr (DROP) cg = ((mb_r >> (j + u)) & 1u) ? cj : (uint32_t)ck.row;
-        xh[u] = head_load<Q>(feat + (int64_t)cj * LEN + loff);
-        xg[u] = head_load<Q>(grad + (int64_t)cg * LEN + loff);
+        xh_raw[u] = head_load_raw<Q, E>(feat + (int64_t)cj * LEN + loff);
+        xg_raw[u] = head_load_raw<Q, E>(grad + (int64_t)cg * LEN + loff);
         rc[u] = rec[cj];
       }
       __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first one is consumed
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         HeadRow<Q> z, pz;
-        float s = gatv2_head_score<Q>(a4, hi, xh[u], eps, z, pz);  // the forward's bits, from either end
-        float dp_ji = head_dot<Q>(gi, xh[u]), dp_ij = head_dot<Q>(xg[u], hi), none = 0.f;
+        const HeadRow<Q> xh = head_widen<Q, E>(xh_raw[u]), xg = head_widen<Q, E>(xg_raw[u]);
+        float s = gatv2_head_score<Q>(a4, hi, xh, eps, z, pz);  // the forward's bits, from either end
+        float dp_ji = head_dot<Q>(gi, xh), dp_ij = head_dot<Q>(xg, hi), none = 0.f;
         head_sum4(s, dp_ji, dp_ij, none);
         bool keep_ij = true;
         if constexpr (DROP) {
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
           for (int q = 0; q < Q; ++q)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              if (keep_ij) acc.p[q][k] = __builtin_fmaf(pw_ij, xg[u].p[q][k], acc.p[q][k]);  // (wave-uniform)
+              if (keep_ij) acc.p[q][k] = __builtin_fmaf(pw_ij, xg.p[q][k], acc.p[q][k]);  // (wave-uniform)
               acc.p[q][k] = __builtin_fmaf(z.p[q][k] > 0.0f ? ds : dse, a4.p[q][k], acc.p[q][k]);
               ag.p[q][k] = __builtin_fmaf(ds_ji, pz.p[q][k], ag.p[q][k]);
             }
@@ -228,7 +236,7 @@ __global__ __launch_bounds__(256) void gatv2_head_bwd_chunk_kernel(int64_t n_chu
   for (int q = 0; q < Q; ++q) *reinterpret_cast<f4*>(sm + wv * LEN + q * 256 + loff) = ag.p[q];
   __syncthreads();
   // DROP: the vector is stored at the index of the workgroup's CHUNKS (head_chunk's blk), so a's sum does not depend on the per_xcd
-  // walk (gatv2.hip)
+  // walk (gatv2_seq.h)
   int64_t slot_ag = blockIdx.x;
   if constexpr (DROP)
     if (per_xcd > 0) slot_ag = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);

@@ -1,10 +1,11 @@
 // gatv2_kernels.h -- the one-sweep GATv2 (dynamic attention, Brody / Alon / Yahav): the score moves the leaky relu INSIDE the dot
 // product,
 //   s_ij^k = sum_{c in C_k} a_c phi(h_ic + h_jc),     phi(x) = x > 0 ? x : eps x
-// with ONE shared vector a, so s_ij = s_ji.  gatv2.hip instantiates the two sweeps and holds the host sequences; the chunk list,
+// with ONE shared vector a, so s_ij = s_ji.  gatv2.hip (fp32 tables) and gatv2_bf16.hip (bf16 tables) instantiate the two sweeps
+// through the host sequences of gatv2_seq.h; the chunk list,
 // the XCD walk, ChunkLanes<G>, rowdot_kernel, gat_rec_kernel and the chunk-order row reductions are gat_kernels.h's, unchanged.
 //
-// Lanes (gat_fused_shape): a row is G = len / 4 lanes of 4 columns (one 16-byte gather per lane and edge), a wave works on
+// Lanes (gat_fused_shape): a row is G = len / 4 lanes of 4 columns (one gather per lane and edge: 16 bytes of fp32, 8 of bf16), a wave works on
 // NG = 64 / G edges per step, head k owns LH = G / H consecutive lanes.  The score needs no gathered byte the aggregation does not
 // gather anyway: the row h_j is in registers when its score is formed.
 //
@@ -32,9 +33,11 @@ __device__ __forceinline__ float gatv2_score(const f4& a4, const f4& hi, const f
   return lanes_sum_w<LH>(t);
 }
 
-// a lane's 16 bytes of row v of a table below 4 GB: one 32-bit byte offset per edge (a VALU multiply instead of a 64-bit chain)
-__device__ __forceinline__ f4 gatv2_row4(const char* tab, uint32_t v, uint32_t row_bytes, uint32_t lane_off) {
-  return *reinterpret_cast<const f4*>(tab + (size_t)(v * row_bytes + lane_off));
+// a lane's four columns of row v AS LOADED (Row4<E>::Raw: 16 bytes of fp32, 8 bytes of raw bf16 bits) from a table whose fp32 form is
+// below 4 GB: one 32-bit byte offset per edge (a VALU multiply instead of a 64-bit chain).  The 16-byte records are E = float
+template <typename E>
+__device__ __forceinline__ typename Row4<E>::Raw gatv2_row4(const char* tab, uint32_t v, uint32_t row_bytes, uint32_t lane_off) {
+  return load_row4(reinterpret_cast<const E*>(tab + (size_t)(v * row_bytes + lane_off)));
 }
 
 // ---- forward: scores, ONLINE softmax and aggregation of a 64-edge chunk --------------------------------------------------------
@@ -51,15 +54,19 @@ __device__ __forceinline__ f4 gatv2_row4(const char* tab, uint32_t v, uint32_t r
 // head window mask_heads / mask_head0 of the full row).  The softmax does not see the mask: the maximum, l and so the row
 // statistics are the undropped sweep's; only the accumulator's weight e becomes e w, a bit test and a select.  The five trailing
 // arguments are read behind the flag only.
-template <int G, int H, int U, bool WIDE = false, bool DROP = false>
+// E: the element type of feat (float; uint16_t = raw bf16 bits, gatv2_bf16.hip).  The chunk's own row is widened once, a gathered
+// row waits as loaded and is widened (Row4<E>::widen: exact, the identity for float) on the consume side of the batch's
+// sched_barrier; everything behind the widening is one text, so the bf16 sweep has the bits of the fp32 sweep on the widened table.
+template <int G, int H, int U, bool WIDE = false, bool DROP = false, typename E = float>
 __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                              const float* feat, const float* a, float eps, float* out_partial,
+                                                              const E* feat, const float* a, float eps, float* out_partial,
                                                               float2* ms_partial, int per_xcd, int ld = 0, float drop_rate = 0.0f,
                                                               float drop_scale = 1.0f, uint64_t drop_seed = 0, int mask_heads = 0,
                                                               int mask_head0 = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
+  using R4 = Row4<E>;
   constexpr int NG = CL::NG;
   int64_t blk = blockIdx.x;  // (per_xcd: see gat_bwd_fused_chunk_kernel)
   if (per_xcd > 0) blk = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
@@ -79,8 +86,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
   const int coff = sl * 4, head = sl / LH;
   const char* tab = reinterpret_cast<const char*>(feat);
   // (WIDE: the FULL row's bytes -- v * row_bytes + lane_off is below nv * ld * 4, which the host holds under 4 GB)
-  const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * 4u, lane_off = (uint32_t)coff * 4u;
-  const f4 hi = gatv2_row4(tab, (uint32_t)row, row_bytes, lane_off);
+  const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * (uint32_t)sizeof(E), lane_off = (uint32_t)coff * (uint32_t)sizeof(E);
+  const f4 hi = R4::widen(gatv2_row4<E>(tab, (uint32_t)row, row_bytes, lane_off));
   const f4 a4 = *reinterpret_cast<const f4*>(a + coff);
   uint32_t mb = 0;  // DROP: the masks of the chunk's edges for this lane's head, bit t = step t
   if constexpr (DROP) mb = gat_drop_bits<G, H, false, WIDE>(lane, n, eb, nullptr, drop_seed, drop_rate, mask_heads, mask_head0);
@@ -89,15 +96,15 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
 #pragma unroll
   for (int j = 0; j < G; j += U) {
     if (j * NG >= n) break;  // (wave-uniform)
-    f4 xh[U];
+    typename R4::Raw xr[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) xh[u] = gatv2_row4(tab, (uint32_t)CL::step_value((int)cl, (int)cl1, lane, j + u), row_bytes, lane_off);
+    for (int u = 0; u < U; ++u) xr[u] = gatv2_row4<E>(tab, (uint32_t)CL::step_value((int)cl, (int)cl1, lane, j + u), row_bytes, lane_off);
     __builtin_amdgcn_sched_barrier(0);  // all gathers of the batch are issued before the first one is consumed
     float s[U], mx = m;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       f4 z, pz;
-      s[u] = gatv2_score<LH>(a4, hi, xh[u], eps, z, pz);
+      s[u] = gatv2_score<LH>(a4, hi, R4::widen(xr[u]), eps, z, pz);
       // (lanes past the end of a short chunk looked at the chunk's first edge: its score takes no part)
       if (CL::step_edge(lane, j + u) < n) mx = s[u] > mx ? s[u] : mx;
     }
@@ -110,8 +117,9 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
       l += e;  // (undropped under DROP too)
       float ew = e;
       if constexpr (DROP) ew = e * (((mb >> (j + u)) & 1u) ? drop_scale : 0.0f);
+      const f4 xh = R4::widen(xr[u]);  // (bf16: widened a second time, two VALU per column, not kept across the batch's maximum)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = __builtin_fmaf(ew, xh[u][q], acc[q]);
+      for (int q = 0; q < 4; ++q) acc[q] = __builtin_fmaf(ew, xh[q], acc[q]);
     }
     m = mx;
   }
@@ -154,16 +162,19 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunk_kernel(int64_t n_chunks, 
 // side of gat_drop_bits, whose key advances by addition) and w_ij element rev[e] heads + k (rev read at the lane's own steps, 256
 // contiguous bytes per chunk).  Two bit words per chunk, formed ahead of the edge loop; in the loop two bit tests and selects.
 // The six trailing arguments are read behind the flag only.
-template <int G, int H, int U, bool WIDE = false, bool DROP = false>
+// E: the element type of feat and grad, as in the forward: h_j and g_j are widened once per chunk, the gathered h_i and g_i wait as
+// loaded (bf16: 2 + 2 + 4 registers per edge in flight instead of 4 + 4 + 4) and are widened behind the sched_barrier.
+template <int G, int H, int U, bool WIDE = false, bool DROP = false, typename E = float>
 __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, const uint32_t* chunk_row, const uint32_t* chunk_ebase,
                                                               const uint32_t* chunk_start, const int64_t* rowptr, const uint32_t* col,
-                                                              const float* feat, const float* grad, const f4* rec, const float* a,
+                                                              const E* feat, const E* grad, const f4* rec, const float* a,
                                                               float eps, float* out_partial, float* agrad_partial, int per_xcd,
                                                               int ld = 0, const uint32_t* rev = nullptr, float drop_rate = 0.0f,
                                                               float drop_scale = 1.0f, uint64_t drop_seed = 0, int mask_heads = 0,
                                                               int mask_head0 = 0) {
   constexpr int LH = G / H, len = 4 * G;
   using CL = ChunkLanes<G>;
+  using R4 = Row4<E>;
   constexpr int NG = CL::NG;
   __shared__ float sm[4 * len];
   int64_t blk = blockIdx.x;
@@ -187,11 +198,11 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
     const char* ftab = reinterpret_cast<const char*>(feat);
     const char* gtab = reinterpret_cast<const char*>(grad);
     const char* rtab = reinterpret_cast<const char*>(rec);
-    const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * 4u, lane_off = (uint32_t)coff * 4u;
+    const uint32_t row_bytes = (uint32_t)(WIDE ? ld : len) * (uint32_t)sizeof(E), lane_off = (uint32_t)coff * (uint32_t)sizeof(E);
     const uint32_t rec_bytes = (uint32_t)H * 16u, rec_off = (uint32_t)head * 16u;
-    const f4 hi = gatv2_row4(ftab, (uint32_t)row, row_bytes, lane_off);
-    const f4 gi = gatv2_row4(gtab, (uint32_t)row, row_bytes, lane_off);
-    const f4 ri = gatv2_row4(rtab, (uint32_t)row, rec_bytes, rec_off);  // (delta_j, m_j, 1 / l_j)
+    const f4 hi = R4::widen(gatv2_row4<E>(ftab, (uint32_t)row, row_bytes, lane_off));
+    const f4 gi = R4::widen(gatv2_row4<E>(gtab, (uint32_t)row, row_bytes, lane_off));
+    const f4 ri = gatv2_row4<float>(rtab, (uint32_t)row, rec_bytes, rec_off);  // (delta_j, m_j, 1 / l_j)
     const f4 a4 = *reinterpret_cast<const f4*>(a + coff);
     const f4 ae4 = a4 * eps;  // a phi' where z <= 0
     uint32_t mb_e = 0, mb_r = 0;  // DROP: the masks of the chunk's edges (w_ji) and of their reverse edges (w_ij), bit t = step t
@@ -206,21 +217,23 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
 #pragma unroll
     for (int j = 0; j < G; j += U) {
       if (j * NG >= n) break;  // (wave-uniform)
-      f4 xh[U], xg[U], rc[U];
+      typename R4::Raw xh_raw[U], xg_raw[U];
+      f4 rc[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t cj = (uint32_t)CL::step_value((int)cl, (int)cl1, lane, j + u);
-        xh[u] = gatv2_row4(ftab, cj, row_bytes, lane_off);
-        xg[u] = gatv2_row4(gtab, cj, row_bytes, lane_off);
-        rc[u] = gatv2_row4(rtab, cj, rec_bytes, rec_off);
+        xh_raw[u] = gatv2_row4<E>(ftab, cj, row_bytes, lane_off);
+        xg_raw[u] = gatv2_row4<E>(gtab, cj, row_bytes, lane_off);
+        rc[u] = gatv2_row4<float>(rtab, cj, rec_bytes, rec_off);
       }
       __builtin_amdgcn_sched_barrier(0);  // all gathers of the batch are issued before the first one is consumed
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         f4 z, pz;
-        const float s = gatv2_score<LH>(a4, hi, xh[u], eps, z, pz);  // the forward's bits, from either end
-        float dp_ji = lanes_sum_w<LH>(d4(gi, xh[u]));
-        float dp_ij = lanes_sum_w<LH>(d4(xg[u], hi));
+        const f4 xh = R4::widen(xh_raw[u]), xg = R4::widen(xg_raw[u]);
+        const float s = gatv2_score<LH>(a4, hi, xh, eps, z, pz);  // the forward's bits, from either end
+        float dp_ji = lanes_sum_w<LH>(d4(gi, xh));
+        float dp_ij = lanes_sum_w<LH>(d4(xg, hi));
         float w_ij = 1.0f;
         if constexpr (DROP) {  // (the sums are scaled after they met: with rate 0 and scale 1 the undropped bits)
           dp_ji *= ((mb_e >> (j + u)) & 1u) ? drop_scale : 0.0f;
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
         if (CL::step_edge(lane, j + u) < n) {  // (lanes past the end of a short chunk looked at its first edge: nothing is added)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            acc[q] = __builtin_fmaf(pw_ij, xg[u][q], acc[q]);
+            acc[q] = __builtin_fmaf(pw_ij, xg[q], acc[q]);
             acc[q] = __builtin_fmaf(ds, z[q] > 0.0f ? a4[q] : ae4[q], acc[q]);
             ag[q] = __builtin_fmaf(ds_ji, pz[q], ag[q]);
           }
@@ -260,7 +273,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_chunk_kernel(int64_t n_chunks, 
   __syncthreads();
   if (threadIdx.x < len) {
     const int t = threadIdx.x;
-    // DROP: the vector is stored at the index of the workgroup's CHUNKS, so a's sum does not depend on the per_xcd walk (gatv2.hip)
+    // DROP: the vector is stored at the index of the workgroup's CHUNKS, so a's sum does not depend on the per_xcd walk (gatv2_seq.h)
     const int64_t slot_ag = DROP ? blk : (int64_t)blockIdx.x;
     agrad_partial[slot_ag * len + t] = ((sm[t] + sm[len + t]) + sm[2 * len + t]) + sm[3 * len + t];
   }

@@ -822,11 +822,11 @@ void GAT_Aggregator::v2_check(int len, Graph& g) const {
   // attention dropout runs inside the v2 sweeps (gaib_gatv2_forward_drop / gaib_gatv2_backward_drop) with option gat_fused_drop
   else if (attn_drop > 0.f && !gat_fused_drop_option()) why = "attention dropout (score_drop > 0) without gat_fused_drop (GAIB_GAT_FUSED_DROP=1)";
   else if (g.gat_full_graph() || g.has_halo()) why = "a partitioned graph";
-  else if (gat_bf16_tables()) why = "gat_bf16 (GAIB_GAT_DTYPE=bf16)";
   if (!why) return;
   fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1) does not cover %s (len %d, heads %d): GATv2 runs rows of 32, 64 or 128 columns "
           "with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with gatv2_wide (GAIB_GATV2_WIDE=1) also column slabs of such rows and one "
-          "head of 256 or 512 columns --, whole graphs, fp32 tables, attention dropout only with GAIB_GAT_FUSED_DROP=1\n", why, len, heads);
+          "head of 256 or 512 columns --, whole graphs, fp32 or bf16 (GAIB_GAT_DTYPE=bf16) tables, attention dropout only with "
+          "GAIB_GAT_FUSED_DROP=1\n", why, len, heads);
   exit(EXIT_FAILURE);
 }
 // bf16 tables on a partitioned GAT graph would need a bf16 exchange of h, grad and record rows: refused, not served in fp32
@@ -849,15 +849,26 @@ void GAT_Aggregator::aggregate(int len, Graph& g, const float* in, float* out) {
     v2_check(len, g);
     grow(d_row_stats, stats_floats, (size_t)g.size() * heads * 2);
     OpTimer t(OP_SPARSEMM);
-    stats_valid = dropped_last = drop_fused_last = fwd_bf16 = false;
+    stats_valid = dropped_last = drop_fused_last = false;
+    // bf16 tables (option gat_bf16): the sweep gathers the aggregator's own bf16 copy of h, kept for backward.  The cover is the
+    // fp32 calls' own, so there is no second attempt in fp32
+    fwd_bf16 = gat_bf16_tables();
+    const uint16_t* hb = fwd_bf16 ? cast_hb16((size_t)g.size() * len, in) : NULL;
     if (dropping()) {  // (v2_check: option gat_fused_drop is on) the masks of the staged sequence's next seed, kept for backward
-      GAIB_OR_DIE(gaib_gatv2_forward_drop(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, attn_drop, attn_scale,
-                                          drop_seed, out, d_row_stats));
+      if (hb)
+        GAIB_OR_DIE(gaib_gatv2_forward_drop_bf16(C(), dev(g), len, heads, hb, d_alpha_l, epsilon, fuse_relu ? 1 : 0, attn_drop,
+                                                 attn_scale, drop_seed, out, d_row_stats));
+      else
+        GAIB_OR_DIE(gaib_gatv2_forward_drop(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, attn_drop, attn_scale,
+                                            drop_seed, out, d_row_stats));
       drop_seed_last = drop_seed++;
       drop_fused_last = drop_sweep_ran = true;
+    } else if (hb) {
+      GAIB_OR_DIE(gaib_gatv2_forward_bf16(C(), dev(g), len, heads, hb, d_alpha_l, epsilon, fuse_relu ? 1 : 0, out, d_row_stats));
     } else {
       GAIB_OR_DIE(gaib_gatv2_forward(C(), dev(g), len, heads, in, d_alpha_l, epsilon, fuse_relu ? 1 : 0, out, d_row_stats));
     }
+    if (fwd_bf16) last_graph = &g, last_in = in, last_len = len;  // (what d_hb16 holds; stats_valid stays false: v2 scores)
     fuse_relu = false;
     return;
   }
@@ -957,12 +968,28 @@ void GAT_Aggregator::d_aggregate(int len, Graph& g, const float* feat_in, const 
     OpTimer t(OP_ATTN);
     const size_t need = (size_t)g.size() * len;
     grow(d_tbuf, tbuf_floats, need);
-    if (drop_fused_last)  // the forward dropped inside the sweep: backward through the same masks, formed again from the kept seed
-      GAIB_OR_DIE(gaib_gatv2_backward_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon,
-                                           attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad));
-    else
+    // bf16 tables: the forward ran on d_hb16; the kept copy is reused where it is the copy of feat_in (cast again otherwise), one
+    // cast of grad_in is made
+    const uint16_t *hb = NULL, *gb = NULL;
+    if (fwd_bf16) {
+      const bool kept = feat_in == last_in && &g == last_graph && len == last_len;
+      hb = kept ? d_hb16 : cast_hb16(need, feat_in);
+      gb = to_bf16(g.size(), len, grad_in);
+    }
+    if (drop_fused_last) {  // the forward dropped inside the sweep: backward through the same masks, formed again from the kept seed
+      if (hb)
+        GAIB_OR_DIE(gaib_gatv2_backward_drop_bf16(C(), dev(g), len, heads, hb, gb, fwd_out, d_alpha_l, d_row_stats, epsilon, attn_drop,
+                                                  attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad));
+      else
+        GAIB_OR_DIE(gaib_gatv2_backward_drop(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon,
+                                             attn_drop, attn_scale, drop_seed_last, d_tbuf, d_alpha_lgrad));
+    } else if (hb) {
+      GAIB_OR_DIE(gaib_gatv2_backward_bf16(C(), dev(g), len, heads, hb, gb, fwd_out, d_alpha_l, d_row_stats, epsilon, d_tbuf,
+                                           d_alpha_lgrad));
+    } else {
       GAIB_OR_DIE(gaib_gatv2_backward(C(), dev(g), len, heads, feat_in, grad_in, fwd_out, d_alpha_l, d_row_stats, epsilon, d_tbuf,
                                       d_alpha_lgrad));
+    }
     drop_fused_last = false;
     GAIB_OR_DIE(gaib_fill_f32(C(), length, 0.f, d_alpha_rgrad));
     fwd_out = NULL;

@@ -217,7 +217,8 @@ struct Trainer {
         std::cerr << "GAIB_GAT_V2=1 (gat_v2) runs on one GPU only: the one-sweep GATv2 kernels take whole graphs\n";
         exit(EXIT_FAILURE);
       }
-      std::cout << "GAT scores: v2, one sweep\n";
+      // (with GAIB_GAT_DTYPE=bf16 the v2 sweeps gather the layers' bf16 copies: the _bf16 forms of the same calls)
+      std::cout << "GAT scores: v2, one sweep" << (gaib_host::option("gat_bf16") ? ", bf16 tables" : "") << "\n";
     }
     init_comm();
     if (ARCH == gnn_arch::GAT) {

@@ -451,6 +451,33 @@ int gaib_gatv2_forward_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, co
 int gaib_gatv2_backward_drop(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const float* d_feat, const float* d_grad,
                              const float* d_fwd_out, const float* d_a, const float* d_row_stats, float epsilon, float drop_rate,
                              float scale, uint64_t seed, float* d_grad_out, float* d_a_grad);
+/* The four GATv2 calls over bf16 TABLES (layer-library options "gat_v2" with "gat_bf16"; with "gat_fused_drop" the _drop pair).
+ * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and of the incoming
+ * gradient is taken from them and widened exactly (a shift / a mask): the sweeps' own rows h_i and g_i, the gathered rows, grad in
+ * the row dots <g_v, out_v>, h wherever a's gradient reads phi(h_j + h_i).  Everything else -- d_a, the forward output, the row
+ * statistics, the records and partial sums inside the calls, every output -- is fp32.
+ * Outputs: BIT-IDENTICAL to gaib_gatv2_forward / gaib_gatv2_backward (the _drop forms: to gaib_gatv2_forward_drop /
+ * gaib_gatv2_backward_drop) called on the tables widened to fp32 (gaib_cast_bf16_f32), under the same options ("gat_chunk_xcd",
+ * "gatv2_wide") and the same (drop_rate, scale, seed): the kernels are the fp32 kernels with another load, lane maps and the order of
+ * every sum unchanged.  The function is therefore exactly fp32 GATv2 on the rounded table, and the backward the exact gradient of
+ * that forward; z = h_i + h_j on widened values is commutative as before, so the score stays symmetric bit for bit.
+ * A gathered row is 2 len bytes instead of 4 len.  Slab s of a wide row ("gatv2_wide") starts 2 s w bytes into a row of the tables,
+ * a multiple of 64 for every slab width; the single head of 256 or 512 columns loads 8 bytes per lane and piece.
+ * Cover and refusals are EXACTLY the fp32 calls', the bound nv * len * 4 < 4 GB included (on the fp32 form's bytes: the two forms
+ * always decide alike); a bf16 table off an 8-byte boundary, or another buffer off a 16-byte one, is GAIB_ERR_INVALID.  Refusals
+ * touch nothing.  Profile keys "gatv2_fwd" / "gatv2_bwd" with the fp32 calls' byte formulas (a work rate in dense bytes).
+ * Speed: DESIGN.md 3.3.8 and LEDGER.md 36 (undropped, four reddit shapes); under dropout not measured yet. */
+int gaib_gatv2_forward_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_h_bf16, const float* d_a,
+                            float epsilon, int relu, float* d_out, float* d_row_stats);
+int gaib_gatv2_backward_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_feat_bf16,
+                             const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_a, const float* d_row_stats,
+                             float epsilon, float* d_grad_out, float* d_a_grad);
+int gaib_gatv2_forward_drop_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_h_bf16, const float* d_a,
+                                 float epsilon, int relu, float drop_rate, float scale, uint64_t seed, float* d_out,
+                                 float* d_row_stats);
+int gaib_gatv2_backward_drop_bf16(gaib_ctx* ctx, gaib_graph* g, int len, int heads, const uint16_t* d_feat_bf16,
+                                  const uint16_t* d_grad_bf16, const float* d_fwd_out, const float* d_a, const float* d_row_stats,
+                                  float epsilon, float drop_rate, float scale, uint64_t seed, float* d_grad_out, float* d_a_grad);
 /* The one-sweep forward and backward over bf16 TABLES (layer-library option "gat_bf16").
  * Tables: d_h_bf16 / d_feat_bf16 / d_grad_bf16 hold raw bf16 bits, [nv x len], 8-byte aligned.  EVERY read of h and grad is taken
  * from them and widened exactly: own rows and gathered rows in the sweep, grad in the row dots <grad_v, out_v>, h in the alpha
@@ -1132,10 +1159,11 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * attention dropout holds neither that array nor mask nor dropped attention; with "gat_bf16" = 1 as well the _bf16 calls (with all
  * three, the _drop_bf16 calls) run them on bf16 tables; partitions stay as they are;
  * "gat_v2" (default 0; readable): 1 = the layer library's GAT aggregation computes GATv2 (gaib_gatv2_forward / gaib_gatv2_backward):
- * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover, a partitioned graph
- * and "gat_bf16" = 1 are refused there with a message, not served by another path; so is attention dropout, unless "gat_fused_drop"
+ * its first attention vector is a, the second and its gradient stay zero; a shape outside those calls' cover and a partitioned
+ * graph are refused there with a message, not served by another path; so is attention dropout, unless "gat_fused_drop"
  * = 1 as well: a training forward then runs gaib_gatv2_forward_drop under the staged sequence of seeds and its backward
- * gaib_gatv2_backward_drop under the kept seed (no mask array; a test-phase forward drops nothing);
+ * gaib_gatv2_backward_drop under the kept seed (no mask array; a test-phase forward drops nothing); with "gat_bf16" = 1 as well
+ * the layer casts h into its bf16 copy and the incoming gradient into another and runs the _bf16 forms of those calls;
  * "gatv2_wide" (default 0; readable): 1 = gaib_gatv2_forward / gaib_gatv2_backward also run multi-head rows wider than 128 columns
  * as column slabs (gaib_gat_fused_slabs gives S >= 2) and a single head of 256 or 512 columns (gaib_gat_fused_head_cpl) in sweeps
  * of its own; the layer library's "gat_v2" layers accept those shapes then; 0 = GAIB_ERR_UNSUPPORTED there, as before;

@@ -195,6 +195,8 @@ class GAT_Aggregator : public aggregator {
   // it lives from a layer's forward to its backward while other layers run.  It grows on demand like d_tbuf, which has to
   // happen outside a capture.  A partitioned GAT graph refuses the option.  (norm_scores_ptr() after such a forward forms the
   // attention array from the fp32 `in`, like the staged path it serves: within the bf16 rounding of what the sweep used.)
+  // With gat_v2 = 1 as well the same copy serves the GATv2 calls' _bf16 forms (gaib_gatv2_forward_bf16 / _backward_bf16, under
+  // attention dropout with gat_fused_drop the _drop_bf16 pair): their cover is the fp32 calls' own, nothing runs in fp32 then.
   static bool gat_bf16_tables();
   uint16_t* d_hb16 = NULL;
   const uint16_t* cast_hb16(size_t elems, const float* in);
