@@ -126,6 +126,7 @@ struct gaib_ctx {
   int gat_fused_head;        // 1: gaib_gat_forward_fused / gaib_gat_backward_fused (row statistics) run ONE head of 256 or 512 columns in the one-sweep kernels of gat_head.hip (gaib_gat_fused_head_cpl), 0 (default) = GAIB_ERR_UNSUPPORTED there; the _drop calls with gat_fused_drop = 1 as well, the _bf16 calls with gat_bf16 = 1 as well, _drop_bf16 with all three
   int gat_v2;                // 1: the layer library's GAT aggregation computes GATv2 scores a . phi(h_i + h_j) with the one-sweep kernels of gatv2.hip (gaib_gatv2_forward / gaib_gatv2_backward), 0 (default) = the static scores of GAT; read by the layer library alone
   int gatv2_wide;            // 1: gaib_gatv2_forward / gaib_gatv2_backward also run multi-head rows wider than 128 columns as column slabs (gaib_gat_fused_slabs) and ONE head of 256 or 512 columns in the sweeps of gatv2_head.hip (gaib_gat_fused_head_cpl), 0 (default) = GAIB_ERR_UNSUPPORTED there
+  int gat_fused_narrow;      // 1: the one-sweep GAT and GATv2 calls (row-statistics forms; plain, _drop, _bf16, _drop_bf16) also run rows of 16 columns (1, 2 or 4 heads) and 8 columns (1 or 2 heads) in the instances of gat_narrow.hip (gat_narrow_shape), 0 (default) = GAIB_ERR_UNSUPPORTED there
   int gat_chunk_xcd;         // one-sweep GAT kernels: 1 = every XCD walks a contiguous eighth of the column-block-ordered chunk list, 0 = round robin
   int graph_rev_search;      // 1 = reverse-edge permutation by per-edge binary search (the reference's way) instead of the sort
   int sampler_device;        // read by the trainer: 1 = sampled subgraphs are induced on the device (gaib_graph_induce), 0 (default) = on the host

@@ -47,6 +47,9 @@
 // the narrow fp32 calls could run the strided forms too is a speed question with its own measurement; nothing here decides it.
 // The helper kernels follow `strided` (slab and window calls): the WIDE rowdot, records, reduce and alpha_partial kernels there,
 // the plain ones in the narrow calls.  gat_bwd_pk and gat_interleave are read by the narrow undropped row-statistics calls only.
+// ROWS OF 16 / 8 COLUMNS (option gat_fused_narrow; gat_narrow_route): the same chunk kernels at G = 4, 2 with the whole chunk as ONE
+// batch (U = G), <G,H,G,E,DROP> forward and <G,H,G,true,E,DROP> backward for both element types, instantiated by gat_narrow.hip;
+// sequences of their own below, row statistics only; _rect, _drop_win and the attention-array backward answer as without the option.
 // The single wide head (gat_head_route) is a sequence of its own below: kernels with another lane layout (gat_head_kernels.h,
 // instantiated by gat_head.hip) and reduce kernels to match, between the narrow calls' plain rowdot, record and alpha kernels.
 #pragma once
@@ -65,6 +68,27 @@ template <typename E>
 int gat_head_backward_run(gaib_ctx* ctx, const gaib_graph* g, int cpl, unsigned grid, int per_xcd, const E* feat, const E* grad,
                           int ld, const float* rec, int rec_ld, const float* alpha_l, const float* alpha_r, float eps,
                           float* out_partial, float* rc_partial, float* grad_out, float* rs, float* cs, const DropWin* drop);
+
+// gat_narrow.hip (option gat_fused_narrow): the sweeps at rows of 16 or 8 columns (gat_narrow_shape) with their per-row reductions,
+// on contiguous tables of element type E (float, uint16_t: instantiated there and nowhere else).  The workspace pieces are the
+// narrow calls' at (len, heads); rec: the records [nv][heads]; drop as above with the window (heads, 0).  The gatv2 pair is
+// what gatv2_seq.h runs between its own prologue and a-gradient kernels
+template <typename E>
+int gat_narrow_forward_run(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, unsigned grid, int per_xcd, const E* h,
+                           const float* alpha_l, const float* alpha_r, float eps, int relu, float* out_partial, float* ms_partial,
+                           float* out, float* row_stats, const DropWin* drop);
+template <typename E>
+int gat_narrow_backward_run(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, unsigned grid, int per_xcd, const E* feat,
+                            const E* grad, const float* rec, const float* alpha_l, const float* alpha_r, float eps, float* out_partial,
+                            float* rc_partial, float* grad_out, float* rs, float* cs, const DropWin* drop);
+template <typename E>
+int gatv2_narrow_forward_run(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, unsigned grid, int per_xcd, const E* h,
+                             const float* a, float eps, int relu, float* out_partial, float* ms_partial, float* out, float* row_stats,
+                             const DropWin* drop);
+template <typename E>
+int gatv2_narrow_backward_run(gaib_ctx* ctx, const gaib_graph* g, int len, int heads, unsigned grid, int per_xcd, const E* feat,
+                              const E* grad, const float* rec, const float* a, float eps, float* out_partial, float* agrad_partial,
+                              float* grad_out, const DropWin* drop);
 
 namespace {
 
@@ -188,6 +212,12 @@ bool gat_head_applies(const gaib_graph* g, int knob, uintptr_t align_or) {
   return g->nc == g->nv && g->ne > 0 && (align_or & 15) == 0 && knob != 0;
 }
 
+// option gat_fused_narrow: rows of 16 or 8 columns (gat_narrow_shape) in the instances of gat_narrow.hip -- the plain, _drop, _bf16
+// and _drop_bf16 calls alike, on the one switch.  `other` as in gat_head_route: those calls answer as without the option
+bool gat_narrow_route(const gaib_ctx* ctx, int len, int heads, bool other) {
+  return ctx->gat_fused_narrow == 1 && !other && gat_narrow_shape(len, heads);
+}
+
 // four chunks per workgroup (0 on a rank whose rows have no edges: nothing to sweep); option gat_chunk_xcd: see the kernels' per_xcd
 void chunk_grid(const gaib_ctx* ctx, const gaib_graph* g, bool xcd_walk, unsigned* grid, int* per_xcd) {
   *grid = (unsigned)cdiv64(g->n_chunks, 4);
@@ -307,6 +337,24 @@ int gat_head_forward_seq(gaib_ctx* ctx, gaib_graph* g, const GatFwd<E>& a, int c
                                  reinterpret_cast<float*>(ws.ms_partial), a.out, a.row_stats, 1, a.drop);
 }
 
+// rows of 16 or 8 columns (option gat_fused_narrow): the narrow call's conditions, workspace and profile entry at (len, heads)
+// around the sweep and row combine of gat_narrow.hip.  gat_fused_unroll has no part: the chunk is one batch
+template <typename E>
+int gat_narrow_forward_seq(gaib_ctx* ctx, gaib_graph* g, const GatFwd<E>& a) {
+  const uintptr_t align_or = table_align(a.h) | (uintptr_t)a.out | (uintptr_t)a.row_stats | (uintptr_t)a.alpha_l | (uintptr_t)a.alpha_r;
+  if (!gat_head_applies(g, ctx->gat_fused_fwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  if (a.drop) GAIB_TRY(gaib_graph_ensure_rev(ctx, g));  // (not read here: forward and backward must decide alike)
+  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
+  FwdWs ws;
+  GAIB_TRY(gat_forward_ws(ctx, g, a.len, a.heads, &ws));
+  ProfScope ps(ctx, "gat_fwd_fused", gat_prof_bytes_fwd(g, a.len, a.heads, 1), 4.0 * (double)g->ne * a.len);
+  unsigned grid;
+  int per_xcd;
+  chunk_grid(ctx, g, true, &grid, &per_xcd);
+  return gat_narrow_forward_run<E>(ctx, g, a.len, a.heads, grid, per_xcd, a.h, a.alpha_l, a.alpha_r, a.eps, a.relu, ws.out_partial,
+                                   reinterpret_cast<float*>(ws.ms_partial), a.out, a.row_stats, a.drop);
+}
+
 // a public forward call: a.len / a.heads are the full row's
 template <typename E>
 int gat_forward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatFwd<E> a) {
@@ -323,6 +371,7 @@ int gat_forward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatFwd<E> a) {
   GAIB_HIP(hipSetDevice(ctx->device));
   if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win, a.drop != nullptr, !std::is_same<E, float>::value))
     return gat_head_forward_seq(ctx, g, a, cpl);
+  if (gat_narrow_route(ctx, len, heads, a.rect || a.win)) return gat_narrow_forward_seq(ctx, g, a);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win) ? 1 : gat_wide_route(ctx, len, heads, &w);  // whole graphs only: _rect keeps its answer
   const int Hs = heads / S;
@@ -474,6 +523,27 @@ int gat_head_backward_seq(gaib_ctx* ctx, gaib_graph* g, const GatBwd<E>& a, int 
   return launch_alpha_grads<E, false>(ctx, g->nv, a.len, 1, a.feat, ws.rs, ws.cs, ws.partial, a.alpha_lgrad, a.alpha_rgrad);
 }
 
+// rows of 16 or 8 columns (option gat_fused_narrow), from the row statistics: the narrow call's workspace, rowdot, records and
+// alpha reduction at (len, heads) around the sweep and row sums of gat_narrow.hip.  gat_bwd_pk, gat_interleave and gat_fused_unroll
+// have no part here
+template <typename E>
+int gat_narrow_backward_seq(gaib_ctx* ctx, gaib_graph* g, const GatBwd<E>& a) {
+  const uintptr_t align_or = table_align(a.feat) | table_align(a.grad) | (uintptr_t)a.row_stats | (uintptr_t)a.grad_out;
+  if (!gat_head_applies(g, ctx->gat_fused_bwd, align_or)) return gat_refuse(a.who, a.len, a.heads);
+  if (a.drop) GAIB_TRY(gaib_graph_ensure_rev(ctx, g));  // the reverse edges' masks
+  GAIB_TRY(gaib_graph_ensure_chunks(ctx, g));
+  BwdWs ws;
+  GAIB_TRY(gat_backward_ws(ctx, g, a.len, a.heads, true, 0, &ws));
+  ProfScope ps(ctx, "gat_bwd_fused", gat_prof_bytes_bwd(g, a.len, a.heads, 1), 8.0 * (double)g->ne * a.len);
+  unsigned grid;
+  int per_xcd;
+  chunk_grid(ctx, g, true, &grid, &per_xcd);
+  GAIB_TRY((gat_bwd_prologue<E, false>(ctx, g->nv, a.len, a.heads, a.len, a.heads, a.grad, a.fwd_out, a.row_stats, ws.rowdot, ws.rec)));
+  GAIB_TRY(gat_narrow_backward_run<E>(ctx, g, a.len, a.heads, grid, per_xcd, a.feat, a.grad, reinterpret_cast<const float*>(ws.rec),
+                                      a.alpha_l, a.alpha_r, a.eps, ws.out_partial, ws.rc_partial, a.grad_out, ws.rs, ws.cs, a.drop));
+  return launch_alpha_grads<E, false>(ctx, g->nv, a.len, a.heads, a.feat, ws.rs, ws.cs, ws.partial, a.alpha_lgrad, a.alpha_rgrad);
+}
+
 // a public backward call: a.len / a.heads are the full row's
 template <typename E>
 int gat_backward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatBwd<E> a) {
@@ -494,6 +564,7 @@ int gat_backward_fused_seq(gaib_ctx* ctx, gaib_graph* g, GatBwd<E> a) {
   GAIB_HIP(hipSetDevice(ctx->device));
   if (const int cpl = gat_head_route(ctx, len, heads, a.rect || a.win || !a.row_stats, a.drop != nullptr, !fp32))
     return gat_head_backward_seq(ctx, g, a, cpl);
+  if (gat_narrow_route(ctx, len, heads, a.rect || a.win || !a.row_stats)) return gat_narrow_backward_seq(ctx, g, a);
   int w = len, rc = GAIB_OK;
   const int S = (a.rect || a.win || !a.row_stats) ? 1 : gat_wide_route(ctx, len, heads, &w);  // the row-statistics form only
   const int Hs = heads / S;

@@ -157,10 +157,14 @@ __global__ void gat_rec_kernel(int64_t n, const float* rowdot, const float2* sta
 //   G = 32: 2 groups of two DPP rows.  (group g, step t) = edge t*2 + g; every lane of the group's two rows holds TWO ids,
 //           edges p*2 + g and (p + 16)*2 + g (both rows load the same lines), so steps 0..15 come from the first, 16..31
 //           from the second.
+//   G =  4: 16 groups, four per DPP row (quarter q = (lane >> 2) & 3).  Same holding; (group (r, q), step t) = edge
+//           (4t + q)*4 + r: four row-shares with constant lane numbers and a select on q.  4 steps per chunk.
+//   G =  2: 32 groups, eight per DPP row (q = (lane >> 1) & 7).  Same holding; (group (r, q), step t) = edge (8t + q)*4 + r,
+//           t = 0, 1: eight row-shares and a select on q.  (G = 4, 2: option gat_fused_narrow, instantiated by gat_narrow.hip.)
 // In every layout the edges of step t are t*NG .. t*NG + NG - 1: a chunk of n edges takes ceil(n / NG) steps.
 template <int G>
 struct ChunkLanes {
-  static_assert(G == 8 || G == 16 || G == 32, "len = 32, 64 or 128");
+  static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32, "len = 8, 16, 32, 64 or 128");
   static constexpr int NG = 64 / G;
   // the edge whose id this lane holds (which = 1: the second one, G = 32 only)
   static __device__ __forceinline__ int held_edge(int lane, int which) {
@@ -172,15 +176,29 @@ struct ChunkLanes {
   static __device__ __forceinline__ int step_edge(int lane, int t) {
     if constexpr (G == 32) return t * 2 + (lane >> 5);
     else if constexpr (G == 16) return t * 4 + (lane >> 4);
-    else return (2 * t + ((lane >> 3) & 1)) * 4 + (lane >> 4);
+    else if constexpr (G == 8) return (2 * t + ((lane >> 3) & 1)) * 4 + (lane >> 4);
+    else if constexpr (G == 4) return (4 * t + ((lane >> 2) & 3)) * 4 + (lane >> 4);
+    else return (8 * t + ((lane >> 1) & 7)) * 4 + (lane >> 4);
   }
   // its held value (a column id, a reverse-edge id): t is a compile-time constant after unrolling
   static __device__ __forceinline__ int step_value(int v0, int v1, int lane, int t) {
     if constexpr (G == 32) return t < 16 ? row_lane(v0, t) : row_lane(v1, t - 16);
     else if constexpr (G == 16) return row_lane(v0, t);
-    else {
+    else if constexpr (G == 8) {
       const int a = row_lane(v0, 2 * t), b = row_lane(v0, 2 * t + 1);
       return ((lane >> 3) & 1) ? b : a;
+    } else if constexpr (G == 4) {
+      const int a = row_lane(v0, 4 * t), b = row_lane(v0, 4 * t + 1), c = row_lane(v0, 4 * t + 2), d = row_lane(v0, 4 * t + 3);
+      const int lo = (lane & 4) ? b : a, hi = (lane & 4) ? d : c;
+      return (lane & 8) ? hi : lo;
+    } else {  // a select tree over the eight positions of the step, on the three bits of q
+      int w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[k] = row_lane(v0, 8 * t + k);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = (lane & 2) ? w[2 * k + 1] : w[2 * k];
+      const int lo = (lane & 4) ? w[1] : w[0], hi = (lane & 4) ? w[3] : w[2];
+      return (lane & 8) ? hi : lo;
     }
   }
 };
@@ -911,6 +929,12 @@ static bool gat_fused_shape(int len, int heads) {
   if (!(len == 32 || len == 64 || len == 128)) return false;
   if (!(heads == 1 || heads == 2 || heads == 4 || heads == 8 || heads == 16)) return false;
   return heads * 4 <= len;
+}
+// option gat_fused_narrow: len = 16 (4 lanes per row) with 1, 2 or 4 heads, len = 8 (2 lanes) with 1 or 2 -- the rule above
+// (heads * 4 <= len) continued downwards; whole graphs, row-statistics forms only.  The gates consult it only under the option
+static bool gat_narrow_shape(int len, int heads) {
+  if (!(len == 16 || len == 8)) return false;
+  return (heads == 1 || heads == 2 || heads == 4) && heads * 4 <= len;
 }
 // M(G, H) for the kernel instance of a shape gat_fused_shape() admits
 #define GAIB_GAT_BY_HEADS(G, M, WITH16) \

@@ -17,6 +17,8 @@
 //     into a row, a multiple of 64 for every slab width: the 8-byte loads stay aligned;
 //   * one head of 256 or 512 columns (gaib_gat_fused_head_cpl): the sweeps of gatv2_head.hip between the narrow call's rowdot,
 //     record and a-gradient kernels at (len, 1).
+// With option gat_fused_narrow = 1 also rows of 16 columns (1, 2 or 4 heads) and 8 columns (1 or 2 heads): the same two sweeps at
+// G = 4, 2 with the whole chunk as one batch, instantiated by gat_narrow.hip, between this file's prologue and a-gradient kernels.
 // ATTENTION DROPOUT (the _drop calls): the SAME two host sequences with the sweeps' DROP instantiations -- the undropped calls are
 // those sequences with drop = NULL.  The masks are formed inside the sweeps (no [ne][heads] array); slab s passes the head window
 // (heads, s Hs) of the full row's mask array; the backward reads g->rev for the reverse edges' masks, and the forward asks for
@@ -32,27 +34,29 @@
 namespace {
 
 // how a call runs: S slabs of w columns and Hs heads (S = 1: the narrow call), or cpl != 0: one head of 64 cpl columns
+// narrow != 0 (option gat_fused_narrow): rows of 16 or 8 columns in the sweeps of gat_narrow.hip, S = 1
 struct V2Route {
-  int S, w, Hs, cpl;
+  int S, w, Hs, cpl, narrow;
 };
 
 // what both calls refuse before they touch anything: 0 = go on.  align_or: the fp32 buffers, and a table's part by table_align
 // (gat_fused_seq.h: an fp32 table as it is, a bf16 table off an 8-byte boundary as a miss of the 16)
 int gatv2_route(const char* who, gaib_ctx* ctx, gaib_graph* g, int len, int heads, uintptr_t align_or, V2Route* r) {
-  *r = V2Route{1, len, heads, 0};
+  *r = V2Route{1, len, heads, 0, 0};
   bool ok = gat_fused_shape(len, heads);
+  if (!ok && ctx->gat_fused_narrow == 1 && gat_narrow_shape(len, heads)) r->narrow = 1, ok = true;
   if (!ok && ctx->gatv2_wide == 1) {
     int w = 0;
     const int S = gaib_gat_fused_slabs(len, heads, &w);
     if ((r->cpl = gaib_gat_fused_head_cpl(len, heads)) != 0) ok = true;
-    else if (S >= 2) *r = V2Route{S, w, heads / S, 0}, ok = true;
+    else if (S >= 2) *r = V2Route{S, w, heads / S, 0, 0}, ok = true;
   }
   // (the sweeps' 32-bit byte offsets run over the caller's full rows: the bound is on nv * len, slabs or not, and on the fp32
   // form's bytes whatever the element type)
   if (!ok || g->nc != g->nv || (uint64_t)g->nv * (uint64_t)len * 4u >= ((uint64_t)1 << 32)) {
     gaib_set_error("%s: covers len 32, 64 or 128 with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with option gatv2_wide = 1 also "
-                   "column slabs of those shapes (gaib_gat_fused_slabs) and one head of 256 or 512 columns -- on a whole graph over "
-                   "tables below 4 GB (len %d, heads %d, %lld x %lld)", who, len, heads, (long long)g->nv, (long long)g->nc);
+                   "column slabs of those shapes (gaib_gat_fused_slabs) and one head of 256 or 512 columns, with option gat_fused_narrow = 1 also "
+                   "len 16 (1, 2 or 4 heads) and len 8 (1 or 2 heads) -- on a whole graph over tables below 4 GB (len %d, heads %d, %lld x %lld)", who, len, heads, (long long)g->nv, (long long)g->nc);
     return GAIB_ERR_UNSUPPORTED;
   }
   GAIB_CHECK((align_or & 15) == 0, "%s: buffers must be 16-byte aligned (bf16 tables: 8-byte)", who);
@@ -220,6 +224,14 @@ int v2_forward_seq(const char* who, gaib_ctx* ctx, gaib_graph* g, int len, int h
   }
   DropWin dw = drop ? *drop : DropWin{0.f, 1.f, 0, 0, 0};
   dw.mask_heads = heads;
+  if (r.narrow) {
+    unsigned grid;
+    int per_xcd;
+    chunk_grid(ctx, g, true, &grid, &per_xcd);
+    dw.mask_head0 = 0;
+    return gatv2_narrow_forward_run<E>(ctx, g, len, heads, grid, per_xcd, d_h, d_a, eps, relu, ws.out_partial,
+                                       reinterpret_cast<float*>(ws.ms_partial), d_out, d_row_stats, drop ? &dw : nullptr);
+  }
   if (r.S == 1) {
     dw.mask_head0 = 0;
     return drop ? v2_forward_sweep<E, false, true>(ctx, g, len, heads, len, heads, d_h, d_a, eps, relu, ws, d_out, d_row_stats, dw)
@@ -269,6 +281,13 @@ int v2_backward_seq(const char* who, gaib_ctx* ctx, gaib_graph* g, int len, int 
   }
   DropWin dw = drop ? *drop : DropWin{0.f, 1.f, 0, 0, 0};
   dw.mask_heads = heads;
+  if (r.narrow) {
+    dw.mask_head0 = 0;
+    GAIB_TRY((gat_bwd_prologue<E, false>(ctx, g->nv, len, heads, len, heads, d_grad, d_fwd_out, d_row_stats, ws.rowdot, ws.rec)));
+    GAIB_TRY(gatv2_narrow_backward_run<E>(ctx, g, len, heads, ws.grid, ws.per_xcd, d_feat, d_grad, reinterpret_cast<const float*>(ws.rec),
+                                          d_a, eps, ws.out_partial, ws.ag_partial, d_grad_out, drop ? &dw : nullptr));
+    return v2_agrad(ctx, ws, len, d_a_grad);
+  }
   if (r.S == 1) {
     dw.mask_head0 = 0;
     return drop ? v2_backward_sweep<E, false, true>(ctx, g, len, heads, len, heads, d_feat, d_grad, d_fwd_out, d_a, d_row_stats, eps, ws,

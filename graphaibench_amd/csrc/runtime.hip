@@ -102,6 +102,7 @@ extern "C" int gaib_ctx_create(int device, void* stream, gaib_ctx** out) {
   c->gat_bf16 = 0;
   c->gat_fused_head = 0;  // (ships off: flipped by a change of its own once the layer step is measured faster)
   c->gatv2_wide = 0;      // (ships off: GATv2 past 128 columns is unmeasured)
+  c->gat_fused_narrow = 0;  // (ships off: rows of 16 and 8 columns are unmeasured against the staged path)
   c->gat_v2 = 0;          // (a different model, not a faster path: the caller's choice)
   c->gat_fused_wide = 0;  // (ships off: flipped by a change of its own once the layer step is measured faster)
   c->drop_seed_dev = 0;   // (not measured yet: DESIGN 3.5.3)
@@ -554,6 +555,7 @@ extern "C" int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value)
   else if (!strcmp(key, "gat_fused_drop")) *h_value = ctx->gat_fused_drop;
   else if (!strcmp(key, "gat_fused_wide")) *h_value = ctx->gat_fused_wide;
   else if (!strcmp(key, "gat_fused_head")) *h_value = ctx->gat_fused_head;
+  else if (!strcmp(key, "gat_fused_narrow")) *h_value = ctx->gat_fused_narrow;
   else if (!strcmp(key, "gat_v2")) *h_value = ctx->gat_v2;
   else if (!strcmp(key, "gatv2_wide")) *h_value = ctx->gatv2_wide;
   else if (!strcmp(key, "gemm_bf16")) *h_value = ctx->gemm_bf16;
@@ -654,6 +656,9 @@ extern "C" int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value) {
   } else if (!strcmp(key, "gat_fused_head")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_fused_head must be 0 (a single head of 256 or 512 columns staged) or 1 (one sweep, the wave on one edge)");
     ctx->gat_fused_head = (int)value;
+  } else if (!strcmp(key, "gat_fused_narrow")) {
+    GAIB_CHECK(value == 0 || value == 1, "gat_fused_narrow must be 0 (rows of 16 or 8 columns: GAT staged, GATv2 refused) or 1 (one sweep)");
+    ctx->gat_fused_narrow = (int)value;
   } else if (!strcmp(key, "gat_v2")) {
     GAIB_CHECK(value == 0 || value == 1, "gat_v2 must be 0 (GAT: static scores) or 1 (GATv2: a . phi(h_i + h_j), one sweep)");
     ctx->gat_v2 = (int)value;

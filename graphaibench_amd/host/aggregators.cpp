@@ -663,7 +663,14 @@ bool GAT_Aggregator::wide_rows_expected() const {
   // (gat_fused_drop: the _drop calls take the shape only then)
   if (gaib_host::option("gat_fused_head") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_head_cpl(length, heads) > 0)
     return true;
+  // option gat_fused_narrow: rows of 16 or 8 columns, under the same condition on attention dropout
+  if (gaib_host::option("gat_fused_narrow") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && narrow_shape(length, heads))
+    return true;
   return gaib_host::option("gat_fused_wide") == 1 && (attn_drop == 0.f || gat_fused_drop_option()) && gaib_gat_fused_slabs(length, heads, NULL) >= 2;
+}
+// the shapes of option gat_fused_narrow (include/gaib.h): 16 columns with 1, 2 or 4 heads, 8 columns with 1 or 2
+bool GAT_Aggregator::narrow_shape(int len, int heads) {
+  return (len == 16 || len == 8) && (heads == 1 || heads == 2 || heads == 4) && heads * 4 <= len;
 }
 
 // the [ne][heads] arrays of the staged kernels, for a graph of ne edges: grown where a graph is larger than the one the layer
@@ -818,14 +825,17 @@ void GAT_Aggregator::v2_check(int len, Graph& g) const {
   const int S = gaib_gat_fused_slabs(len, heads, &w);
   // option gatv2_wide: also column slabs of a multi-head row and one head of 256 or 512 columns
   const bool wide = gaib_host::option("gatv2_wide") == 1 && (S >= 2 || gaib_gat_fused_head_cpl(len, heads) > 0);
-  if (!(S == 1 && w == len) && !wide) why = "this shape";
+  // option gat_fused_narrow: also rows of 16 or 8 columns
+  const bool narrow = gaib_host::option("gat_fused_narrow") == 1 && narrow_shape(len, heads);
+  if (!(S == 1 && w == len) && !wide && !narrow) why = "this shape";
   // attention dropout runs inside the v2 sweeps (gaib_gatv2_forward_drop / gaib_gatv2_backward_drop) with option gat_fused_drop
   else if (attn_drop > 0.f && !gat_fused_drop_option()) why = "attention dropout (score_drop > 0) without gat_fused_drop (GAIB_GAT_FUSED_DROP=1)";
   else if (g.gat_full_graph() || g.has_halo()) why = "a partitioned graph";
   if (!why) return;
   fprintf(stderr, "GPU error: gat_v2 (GAIB_GAT_V2=1) does not cover %s (len %d, heads %d): GATv2 runs rows of 32, 64 or 128 columns "
           "with 1, 2, 4, 8 or 16 heads of at least 4 columns -- with gatv2_wide (GAIB_GATV2_WIDE=1) also column slabs of such rows and one "
-          "head of 256 or 512 columns --, whole graphs, fp32 or bf16 (GAIB_GAT_DTYPE=bf16) tables, attention dropout only with "
+          "head of 256 or 512 columns, with gat_fused_narrow (GAIB_GAT_NARROW=1) also rows of 16 columns (1, 2 or 4 heads) and 8 columns (1 or 2 "
+          "heads) --, whole graphs, fp32 or bf16 (GAIB_GAT_DTYPE=bf16) tables, attention dropout only with "
           "GAIB_GAT_FUSED_DROP=1\n", why, len, heads);
   exit(EXIT_FAILURE);
 }

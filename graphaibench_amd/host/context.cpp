@@ -160,6 +160,16 @@ void gpu_context::set(int device, void* hip_stream) {
     }
     check(gaib_set_option(g_ctx, "gatv2_wide", v), "gaib_set_option (GAIB_GATV2_WIDE)");
   }
+  // GAT and GATv2 layers of 16 or 8 columns (the reference's default hidden width and the one below it) in the one-sweep kernels
+  // (option gat_fused_narrow; off by default)
+  if (const char* d = getenv("GAIB_GAT_NARROW")) {
+    const int v = parse_switch(d);
+    if (v < 0) {
+      fprintf(stderr, "GAIB_GAT_NARROW=%s: expected 0 or 1\n", d);
+      exit(EXIT_FAILURE);
+    }
+    check(gaib_set_option(g_ctx, "gat_fused_narrow", v), "gaib_set_option (GAIB_GAT_NARROW)");
+  }
   // the same switch for GAT (option gat_bf16): its one-sweep forward and backward gather bf16 copies of h and grad
   if (const char* d = getenv("GAIB_GAT_DTYPE")) {
     const std::string dt(d);

@@ -553,6 +553,15 @@ struct Trainer {
         const bool bf16 = sweep && gaib_host::option("gat_bf16") == 1;
         std::cout << "GAT single wide head: " << (sweep ? (bf16 ? "one sweep, bf16 tables" : "one sweep") : "staged") << "\n";
       }
+      // option gat_fused_narrow (GAIB_GAT_NARROW=1): hidden layers of 16 columns (1, 2 or 4 heads) or 8 columns (1 or 2 heads) in
+      // the one-sweep kernels (whole graphs; under attention dropout only with option gat_fused_drop as well), else staged
+      if (gaib_host::option("gat_fused_narrow") == 1 && root()) {
+        const char* hs = getenv("GAIB_GAT_HEADS");
+        const int h = hs ? atoi(hs) : 1;
+        const bool shape = (dim_hid == 16 || dim_hid == 8) && (h == 1 || h == 2 || h == 4) && h * 4 <= dim_hid;
+        const bool sweep = shape && (score_drop == 0.f || drop_sweep == 1) && world == 1;
+        std::cout << "GAT narrow rows: " << (sweep ? "one sweep" : "staged") << "\n";
+      }
     }
 #endif
     if (use_l2norm) l2 = new l2norm_layer(nv, dim_hid);

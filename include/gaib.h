@@ -1167,6 +1167,14 @@ int gaib_probe_peer_copy(int src_dev, int dst_dev, size_t bytes, int iters, int 
  * "gatv2_wide" (default 0; readable): 1 = gaib_gatv2_forward / gaib_gatv2_backward also run multi-head rows wider than 128 columns
  * as column slabs (gaib_gat_fused_slabs gives S >= 2) and a single head of 256 or 512 columns (gaib_gat_fused_head_cpl) in sweeps
  * of its own; the layer library's "gat_v2" layers accept those shapes then; 0 = GAIB_ERR_UNSUPPORTED there, as before;
+ * "gat_fused_narrow" (default 0; readable): 1 = the one-sweep calls also run rows of 16 columns (1, 2 or 4 heads) and of 8 columns
+ * (1 or 2 heads), the widths below len 32: gaib_gat_forward_fused / gaib_gat_backward_fused (row-statistics form) and their _drop,
+ * _bf16 and _drop_bf16 forms, gaib_gatv2_forward / gaib_gatv2_backward and theirs -- whole graphs, the calls' alignment rules,
+ * profile keys and byte formulas at (len, heads); a 64-edge chunk is one batch there, so "gat_fused_unroll", "gat_bwd_pk" and
+ * "gat_interleave" are not read ("gat_chunk_xcd" is).  NOT covered: the _rect and _drop_win calls, gaib_gat_score_signs, the backward
+ * from the attention array, column slabs of such widths (gaib_gat_fused_slabs answers as ever).  The layer library then holds no
+ * [ne][heads] array for such a layer (without attention dropout, or with "gat_fused_drop" = 1), and its "gat_v2" layers accept the
+ * shapes; partitions stay staged (GAT) or refused (GATv2).  0 = GAIB_ERR_UNSUPPORTED there, nothing touched, as before;
  * "drop_seed_dev" (default 0; readable): 1 = the layer library's feature dropout (dropout_gpu) and its staged GAT attention dropout
  * keep their mask seeds in device memory and draw with gaib_dropout_dev, so that a trainer can record an epoch under dropout; the
  * seeds are the host counters', call for call; read where a seed slot is first needed: set it before the first layer is built;
@@ -1187,7 +1195,7 @@ int gaib_set_option(gaib_ctx* ctx, const char* key, int64_t value);
  * "spmm_fuse_cus", "spmm_flat_ring", "num_cus", "agg_bf16", "agg_fp8", "gat_bf16", "spmm_bf16_layout", "spmm_bf16_fuse_u",
  * "spmm_bf16_pad", "agg_bf16_ld_last", "agg_zs", "agg_zs_wide", "agg_zs_paused", "capturing", "gemm_bf16", "gemm_bf16_kernel",
  * "sgemm_split", "sgemm_split_kernel", "sgemm_split_tn", "sampler_device", "gat_fused_drop", "gat_fused_wide", "gat_fused_head",
- * "drop_seed_dev", "gat_v2", "gatv2_wide" */
+ * "drop_seed_dev", "gat_v2", "gatv2_wide", "gat_fused_narrow" */
 int gaib_get_option(gaib_ctx* ctx, const char* key, int64_t* h_value);
 
 #ifdef __cplusplus

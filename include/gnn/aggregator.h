@@ -225,7 +225,15 @@ class GAT_Aggregator : public aggregator {
   // accept the shape.  wide_rows_expected() also holds with that option at a shape with gaib_gat_fused_head_cpl > 0 and no
   // attention dropout; init() then drops the [ne] arrays it made for the single head a layer starts with.  Attention dropout,
   // bf16 tables and partitions stay as they are at these widths.
+  // extension: rows of 16 columns (1, 2 or 4 heads) and 8 columns (1 or 2 heads) -- the reference's default hidden width and the
+  // one below it -- in the one-sweep kernels (context option "gat_fused_narrow" = 1, or GAIB_GAT_NARROW=1, set BEFORE the layer
+  // is built).  Nothing changes in aggregate() / d_aggregate(): the one-sweep calls (plain, _drop, _bf16, _drop_bf16) accept the
+  // shape instead of answering GAIB_ERR_UNSUPPORTED.  wide_rows_expected() also holds with that option at such a shape
+  // (narrow_shape) without attention dropout or with "gat_fused_drop" = 1, so the [ne][heads] arrays are not held;
+  // grow_edge_arrays() allocates them if a staged piece is needed after all.  Partitions stay staged.  Under "gat_v2" = 1
+  // v2_check() accepts these shapes with the option (partitions stay refused); its message names the switch.
   bool wide_rows_expected() const;
+  static bool narrow_shape(int len, int heads);
   // extension: GATv2 scores s_ij = a . phi(h_i + h_j) (context option "gat_v2" = 1, or GAIB_GAT_V2=1; read per call).  aggregate()
   // and d_aggregate() are gaib_gatv2_forward / gaib_gatv2_backward: d_alpha_l holds a, d_alpha_r and its gradient stay zero (init()
   // under the option does not draw it) and update_weights() steps a alone.  Only the row statistics are kept; no [ne][heads] array
